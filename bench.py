@@ -1,16 +1,20 @@
 #!/usr/bin/env python
 """bench.py -- SparseVFC EM-iteration throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...)
 
 A "step" is ONE full SparseVFC EM iteration (E-step, weighted Gram + rhs, all-reduce, Cholesky solve, field
 application, sigma^2 / gamma update - SURVEY.md Appendix A step 5) over the whole synthetic point cloud, with the
 inputs resident in HBM.  Workload: BASELINE config 4 = 8 M cells, M = 3000 control points, float32 cells; it fits one
 MI355X, so the same total problem is run at every N (cells block-sharded across ranks: strong scaling).
-Rank 0 prints ONE JSON line.  Extra objects: ``roofline`` (dominant kernel = the MFMA Gram kernel, timed with HIP
-events on its launch stream; ``traffic`` = the PMC figure parsed from the committed ``profiles/r04_pmc_traffic.json``),
-``solve`` (the coefficient solve: path, Jacobi sweeps, ms, MFMA-tile TFLOP/s), ``f64`` (the SAME workload in float64
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line with the headline and
+the ``roofline`` / ``solve`` objects of those K steps (``traffic`` = the PMC figure parsed from the committed
+``profiles/r04_pmc_traffic.json``).  ``--dump-outputs DIR`` writes what the last timed step computed, as a caller of the
+engine receives it, to DIR/*.npy (see ``dump_outputs``).  Everything else is measured only with ``--full``:
+``roofline.traffic`` measured in the run, ``solve.warm_host_ms``, and the extra objects below.
+Objects: ``roofline`` (dominant kernel = the MFMA Gram kernel, timed with HIP events on its launch stream), ``solve``
+(the coefficient solve: path, Jacobi sweeps, ms, MFMA-tile TFLOP/s); with ``--full`` also ``f64`` (the SAME workload in float64
 mode - the mode the 1e-5 parity clause is about - with its own roofline; N = 1 only), ``con_k`` (the materialised-kernel
 HBM-write bandwidth), ``eval`` (the fused evaluator kernel and the wall time of Jacobian + curl on a 64^3 grid at the API), ``cpu_baseline`` (the float64 NumPy oracle on the host cores at N_cpu = 200 k and 100 k cells; its
 ``value`` is the rate its fitted t(N) = a N + b gives at the bench's own cell count; N = 1 only) and ``parity`` (the GPU
@@ -170,6 +174,25 @@ def _eigh_solver(lhs, rhs, method=None):
 
 
 PARITY_STEPS = 10  # EM iterations of the parity leg (>= 10; the timing legs keep their 3)
+
+DUMP_ROWS = 1 << 20   # cells sampled into the --dump-outputs files (V, P): 32 MB of float64 at most
+DUMP_SEED = 20240601  # fixed: two builds given the same arguments dump the same cells
+
+
+def dump_outputs(out_dir, V, P, C, sigma2, energy):
+    """What the timed path computed in its last step, as a caller of the engine receives it (``results()``): the field V
+    and the posterior P on a fixed, seeded sample of DUMP_ROWS cells (all cells when there are fewer, in cell order), the
+    coefficients C and sigma^2 / the energy E.  float64 .npy files; returns their names."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(V)
+    if n > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_ROWS, replace=False))
+        V, P = V[rows], P[rows]
+    arrays = {"V_sample": V, "P_sample": np.asarray(P).reshape(-1), "C": C,
+              "sigma2": np.array([sigma2]), "energy": np.array([energy])}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
 
 
 def _cpu_steps(M, lambda_, n_cpu, steps, keep=False):
@@ -338,7 +361,16 @@ def main():
     ap.add_argument("--no-organs32", action="store_true", help="skip the 32-organ run of BASELINE config 5")
     ap.add_argument("--no-rccl-world1", action="store_true",
                     help="skip the extra N = 1 runs that execute the step's collectives on a one-rank RCCL communicator")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (field and posterior on a fixed sample of "
+                         f"{DUMP_ROWS} cells, coefficients, sigma^2, energy) to DIR/<name>.npy in float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: solve behind a warm host, float64 mode, BASELINE "
+                         "config 3, the one-rank RCCL legs, con_K, evaluators, configs 2 / 5 and whole calls, the HBM traffic "
+                         "measured in this run, the CPU baseline and the parity leg (the --no-* options skip parts of it)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     # ONE JSON line on stdout: RCCL prints a version banner on STDOUT when a communicator is created (seen on the first RCCL
     # execution of this code, round 5) and other native libraries may do the same, so the process's fd 1 is pointed at stderr
@@ -486,9 +518,10 @@ def main():
             os.environ["MASTER_PORT"] = str(port)
             dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device(device))
 
-    def run_mode(dtype, steps, warmup, force=False, collective="torch", data=None):
+    def run_mode(dtype, steps, warmup, force=False, collective="torch", data=None, dump_dir=None):
         """W warm-up + K timed EM iterations of the whole workload in one cell dtype; returns the timing record.
-        data = (Xv, Yv, ctrl, beta): another single-rank workload through the same code (BASELINE config 3)."""
+        data = (Xv, Yv, ctrl, beta): another single-rank workload through the same code (BASELINE config 3).
+        dump_dir: write the last timed step's outputs there (dump_outputs) before anything else runs on the engine."""
         kern = HipKernels(device, dtype)
         cache_u = {"auto": "auto", "on": True, "off": False}[args.cache_u]
         if force and collective == "torch":
@@ -520,7 +553,8 @@ def main():
 
         eng._solve_all = timed_solve
         try:
-            return _timed_steps(eng, kern, solve_events, dtype, steps, warmup, force, collective, N_r, n_loc_r, Mc_r)
+            return _timed_steps(eng, kern, solve_events, dtype, steps, warmup, force, collective, N_r, n_loc_r, Mc_r,
+                                dump_dir)
         finally:  # (the RCCL communicator of the engine is destroyed on every path, not only on success)
             if eng.comm is not None:
                 eng.comm.close()
@@ -528,7 +562,7 @@ def main():
             del eng, kern
             torch.cuda.empty_cache()
 
-    def _timed_steps(eng, kern, solve_events, dtype, steps, warmup, force, collective, N_r, n_loc_r, Mc_r):
+    def _timed_steps(eng, kern, solve_events, dtype, steps, warmup, force, collective, N_r, n_loc_r, Mc_r, dump_dir=None):
         for _ in range(warmup):
             eng.em_step(**step_kw)
         kern.gram_events = []
@@ -538,7 +572,7 @@ def main():
         barrier()
         t_start = time.perf_counter()
         for _ in range(steps):
-            eng.em_step(**step_kw)
+            E_last, _ = eng.em_step(**step_kw)
         barrier()
         elapsed = time.perf_counter() - t_start
         if distributed:
@@ -548,12 +582,19 @@ def main():
         gram_ms = [e0.elapsed_time(e1) for e0, e1 in kern.gram_events]
         solve_ms = [e0.elapsed_time(e1) for e0, e1 in solve_events]
         kern.gram_events = None
-        # The same solve behind a WARM host (untimed extra iterations): the bracket above starts on the device when the Gram stage
-        # ends, while the host thread has been parked in the solve's first status read for the length of that stage (a second at
-        # the headline) and wakes up late and cold; here the host synchronises first and the call is timed by the wall clock
-        # (the call is host-synchronous).  Both are reported; `avg_ms` stays the bracket inside the timed steps.
+        dumped = None
+        if dump_dir is not None:  # (every rank takes part: results() gathers the cell rows on rank 0)
+            V_d, P_d, C_d = eng.results()
+            if rank == 0:
+                dumped = dump_outputs(dump_dir, V_d, P_d, C_d, eng.sigma2, E_last)
+            del V_d, P_d, C_d
+        # The same solve behind a WARM host (untimed extra iterations, --full only): the bracket above starts on the device
+        # when the Gram stage ends, while the host thread has been parked in the solve's first status read for the length of
+        # that stage (a second at the headline) and wakes up late and cold; here the host synchronises first and the call is
+        # timed by the wall clock (the call is host-synchronous).  Both are reported; `avg_ms` stays the bracket inside the
+        # timed steps.
         warm_ms = []
-        if not eng.multi:
+        if args.full and not eng.multi:
             timed = eng._solve_all
 
             def warm_solve(ls2):
@@ -688,12 +729,15 @@ def main():
                                    "its interval spans the rhs / quadform kernels and the [R | stats] all-reduce"}
         if eng.comm is not None:
             rec["rccl_ranks_mvf_comm_info"] = int(eng.comm.info()[0])  # ncclCommCount of the engine's communicator
+        if dumped is not None:
+            rec["dumped"] = dumped
         return rec
 
     try:
         if args.force_collectives and world != 1:
             raise SystemExit("--force-collectives is an N = 1 option (with N > 1 the collectives run anyway)")
-        main_rec = run_mode(args.dtype, args.steps, args.warmup, force=args.force_collectives, collective=args.collective)
+        main_rec = run_mode(args.dtype, args.steps, args.warmup, force=args.force_collectives, collective=args.collective,
+                            dump_dir=args.dump_outputs)
     except Exception as exc:
         # one JSON line per failing rank on stderr (which rank, what, where), then the error itself
         import traceback
@@ -736,6 +780,8 @@ def main():
         # what the container grants the host side: thread pools (BLAS, torch) are sized to it, and the CPU baseline runs on it
         "host": {"cpus_visible": n_aff, "cfs_quota_cpus": cpu_quota, "threads_used": cpu_use, "throttle_at_start": throttle0},
     }
+    if "dumped" in main_rec:
+        out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": main_rec["dumped"]}
     if "comm" in main_rec and not distributed:
         out["per_rank"], out["comm"] = main_rec["per_rank"], main_rec["comm"]
         out["config"]["force_collectives"] = True
@@ -747,7 +793,7 @@ def main():
                                         f"agreement); redundant coefficient solve on every rank")
 
     # ---------------------------------------------------------------- the same workload in float64 mode (N = 1)
-    if world == 1 and args.dtype == "float32" and not args.no_f64:
+    if args.full and world == 1 and args.dtype == "float32" and not args.no_f64:
         k64, w64 = max(2, min(args.steps, 5)), 1
         r64 = run_mode("float64", k64, w64)
         out["f64"] = {"metric": out["metric"], "unit": "cells/s", "dtype": "f64", "value": r64["value"],
@@ -766,7 +812,7 @@ def main():
     out["config"]["rccl_ranks"] = rccl_ranks if distributed else None   # (N = 1: filled by the rccl_world1 leg below)
 
     # ---------------------------------------------------------------- BASELINE config 3 (2 M x 2000) through the same code (N = 1)
-    if rank == 0 and world == 1 and not args.no_c3 and args.cells >= 2_000_000:
+    if args.full and rank == 0 and world == 1 and not args.no_c3 and args.cells >= 2_000_000:
         X3, V3, M3 = make_config("C3")
         _, X3v, Y3v, _, ctrl3, beta3 = sparsevfc_preprocess(X3, V3, M=M3, seed=0)
         del X3, V3
@@ -781,7 +827,7 @@ def main():
         del X3v, Y3v
 
     # ---------------------------------------------------------------- the step's collectives on RCCL with one rank (N = 1)
-    if world == 1 and not args.no_rccl_world1 and not args.force_collectives:
+    if args.full and world == 1 and not args.no_rccl_world1 and not args.force_collectives:
         # The exchange of the multi-GPU path, executed: force_collectives runs the multi-rank protocol (split Gram stages,
         # asynchronous all-reduce of tri(G) overlapped with the rhs kernels, [R | stats], the E-step MIN and the closing
         # 14-double collective) on a communicator of ONE rank - RCCL accepts that on a one-GPU box - through both back ends.
@@ -809,7 +855,7 @@ def main():
             dist.destroy_process_group()
 
     # ---------------------------------------------------------------- con_K HBM bandwidth (N = 1, rank 0)
-    if rank == 0 and world == 1 and not args.no_conk:
+    if args.full and rank == 0 and world == 1 and not args.no_conk:
         # BASELINE config 3: con_K roofline run (16 GB of float32 output); clipped to the workload when a developer run is smaller
         nk, mk = min(2_000_000, len(Xv)), min(2000, len(ctrl))
         xs = torch.from_numpy((Xv[:nk] - ctrl.mean(0)).astype(np.float32)).to(device)
@@ -842,7 +888,7 @@ def main():
                         "frac": nbytes / (ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, "bound": "hbm (write)"}
 
     # ---------------------------------------------------------------- evaluator path (N = 1, rank 0): BASELINE config 2's shape
-    if rank == 0 and world == 1 and not args.no_conk:
+    if args.full and rank == 0 and world == 1 and not args.no_conk:
         from spateo_amd import _lib as _l
         from spateo_amd.vectorfield import SvcVectorField, _EVAL_ALL, clear_eval_cache
 
@@ -900,7 +946,7 @@ def main():
         out["config"]["eval_api_wall_ms"] = out["eval"]["float32" if args.dtype == "float32" else "float64"]["jacobian_plus_curl_api_wall_ms"]
 
     # ---------------------------------------------------------------- BASELINE configs 2 and 5 (N = 1): ms per EM iteration
-    if rank == 0 and world == 1 and not args.no_whole_fit:
+    if args.full and rank == 0 and world == 1 and not args.no_whole_fit:
         def small(cfg_name, n_small, m_small, seed_small):
             Xs, Vs, _ = make_config(cfg_name, N=n_small, seed=seed_small)
             _, Xsv, Ysv, _, ctrl_s, beta_s = sparsevfc_preprocess(Xs, Vs, M=m_small, seed=0)
@@ -982,7 +1028,7 @@ def main():
             del organs32, res32
 
     # ---------------------------------------------------------------- whole calls: host arrays in -> host dict out (N = 1)
-    if rank == 0 and world == 1 and not args.no_whole_fit:
+    if args.full and rank == 0 and world == 1 and not args.no_whole_fit:
         import spateo_amd._runtime as _rtm
         import spateo_amd.vectorfield as vfm
 
@@ -1016,7 +1062,7 @@ def main():
     del X, V
 
     # ---------------------------------------------------------------- HBM traffic of the dominant kernel, measured (N = 1)
-    if rank == 0 and world == 1 and not args.no_measure_traffic and not args.force_collectives:
+    if args.full and rank == 0 and world == 1 and not args.no_measure_traffic and not args.force_collectives:
         torch.cuda.empty_cache()
         mt = measured_traffic(N, Mc, args.dtype, args.lambda_)
         if mt is not None:
@@ -1029,7 +1075,7 @@ def main():
             rl["traffic_over_algorithmic_bytes"] = mt["bytes"] / (2.0 * (4 if args.dtype == "float32" else 8) * N * Mc)
 
     # ---------------------------------------------------------------- CPU baseline (N = 1, rank 0, bounded sample)
-    if rank == 0 and world == 1 and args.cpu_cells > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_cells > 0:
         cb, sample = cpu_baseline(Mc, args.lambda_, args.cpu_cells, N)
         out["cpu_baseline"] = cb
         # against the fitted t(N) at the bench's own cell count (the lstsq constant amortised), not the small sample

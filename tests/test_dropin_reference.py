@@ -1,4 +1,5 @@
-"""Drop-in proof (runs where /root/reference exists, i.e. in the build container; skipped on the GPU box).
+"""Drop-in proof (runs where build() staged the reference modules under oracle/_ref - oracle/ref_stage.py - i.e. where the
+reference checkout was readable; skipped elsewhere).
 
 The REAL reference files ``spateo/tdr/morphometrics/morphofield/sparsevfc.py``,
 ``.../morphofield_dg/differential_geometry.py`` and ``spateo/tdr/interpolations/interpolation_sparseVFC.py`` are loaded
@@ -17,10 +18,12 @@ import numpy as np
 import pandas as pd
 import pytest
 
-REF = "/root/reference/spateo"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree only exists in the build container")
-
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+
+from oracle import ref_stage  # noqa: E402  (the reference modules build() staged under oracle/_ref)
+
+pytestmark = pytest.mark.skipif(not ref_stage.staged(), reason="build() staged no reference modules under oracle/_ref "
+                                                                "(the reference checkout was not readable)")
 
 
 @pytest.fixture
@@ -32,6 +35,7 @@ def reference_with_our_engine(monkeypatch):
     from spateo_amd import vectorfield as vfm
 
     before = set(sys.modules)
+    monkeypatch.setattr(mg, "REF", ref_stage.STAGE)
     monkeypatch.setattr(vfm._rt, "_make_kernels", lambda device, dtype: CpuKernels(device, dtype))
     mg.install_stubs()
     sv = types.ModuleType("dynamo.vectorfield.scVectorField")

@@ -1,11 +1,13 @@
 """bench.py's output contract on a small workload (subprocess, one GPU): ONE JSON line on stdout with the driver's keys, the
 `roofline` and `cpu_baseline` objects of this tier, this repository's extras (`parity`, `f64`, `env`) and the figures `config`
-carries for the driver's parsed record (`f64_value`, `eval_frac`, `c5_32_organs_wall_s`, `rccl_ranks`, ...)."""
+carries for the driver's parsed record (`f64_value`, `eval_frac`, `c5_32_organs_wall_s`, `rccl_ranks`, ...) - all of it with
+`--full`; a plain run carries the headline alone and `--dump-outputs` writes what its last timed step computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -14,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_contract():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cells", "150000",
-           "--ctrl", "1100", "--cpu-cells", "6000"]
+           "--ctrl", "1100", "--cpu-cells", "6000", "--full"]
     env = {k: v for k, v in os.environ.items() if not k.startswith("MVF_")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -70,3 +72,36 @@ def test_bench_line_contract():
         pr = rc[coll]["per_rank"][0]
         assert pr["allreduce_ms"] > 0 and pr["rhs_stats_allreduce_ms"] > 0 and pr["scalar_allreduce_ms"] > 0
     assert "nccl" in rc["torch"]["comm"]["backend"] and "mvf_allreduce_stats" in rc["mvf"]["comm"]["backend"]
+
+
+def _plain_run(out_dir):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--cells", "150000",
+           "--ctrl", "1100", "--dump-outputs", str(out_dir)]
+    env = {k: v for k, v in os.environ.items() if not k.startswith("MVF_")}
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """Without --full: the headline line alone (none of the extra legs), --steps timed steps, and the last step's outputs
+    as float64 .npy files (field and posterior of every cell here: fewer cells than the dump's sample)."""
+    d = _plain_run(tmp_path / "a")
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["metric"] == "cells/s per SparseVFC EM iter" and d["unit"] == "cells/s"
+    assert abs(d["value"] - d["config"]["cells"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert d["roofline"]["launches"] >= 3 and d["solve"]["warm_host_ms"] is None
+    for key in ("f64", "c3", "rccl_world1", "con_k", "eval", "small_configs", "whole_fit", "cpu_baseline", "parity"):
+        assert key not in d, key
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(f"{n}.npy" for n in d["dumped_outputs"]["files"]) == ["C.npy", "P_sample.npy", "V_sample.npy",
+                                                                                  "energy.npy", "sigma2.npy"]
+    arr = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype == np.float64 for a in arr.values())
+    assert sum(a.nbytes for a in arr.values()) <= 64 << 20
+    n = d["config"]["cells"]
+    assert arr["V_sample"].shape == (n, 3) and arr["P_sample"].shape == (n,) and arr["C"].shape == (d["config"]["ctrl_points"], 3)
+    assert np.all(np.isfinite(arr["V_sample"])) and np.all((arr["P_sample"] >= 0) & (arr["P_sample"] <= 1))
+    assert float(arr["sigma2"][0]) == d["config"]["sigma2_after"] > 0

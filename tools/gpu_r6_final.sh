@@ -10,7 +10,7 @@ timeout 3000 python -m pytest tests -q -m gpu -x -s > $OUT/gpu_tests.txt 2>&1; e
 python tools/parity_table.py $OUT/gpu_tests.txt > $OUT/parity_table.md 2>/dev/null; wc -l $OUT/parity_table.md
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $OUT/smoke.log
 S=$(date +%s)
-timeout 1500 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? in $(( $(date +%s) - S )) s"
+timeout 1500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? in $(( $(date +%s) - S )) s"
 python - <<PY
 import json
 d=json.load(open('$OUT/bench.json'))
@@ -24,7 +24,7 @@ for N in 2 4; do
   python -c "import json;d=json.load(open('$OUT/bench_${N}ranks_one_device.json'));print(d['n_gpus'],d['value'],d['ms_per_step'],d['config'].get('collectives_per_step'))" 2>&1 | tail -1
 done
 cd /tmp
-timeout 1200 rocprofv3 --kernel-trace --stats -d $OUT/prof -o p -- python $R/bench.py --no-conk --cpu-cells 0 --no-measure-traffic --no-whole-fit --no-rccl-world1 > $OUT/bench_under_rocprof.json 2> $OUT/prof.log; echo "rocprof bench rc=$?"
+timeout 1200 rocprofv3 --kernel-trace --stats -d $OUT/prof -o p -- python $R/bench.py --full --no-conk --cpu-cells 0 --no-measure-traffic --no-whole-fit --no-rccl-world1 > $OUT/bench_under_rocprof.json 2> $OUT/prof.log; echo "rocprof bench rc=$?"
 DB=$(find $OUT/prof -name "*.db" | head -1)
 python $R/tools/rocpd_summary.py $DB > $OUT/bench_kernel_stats.md 2> $OUT/bench_kernel_stats.err
 python $R/tools/rocpd_summary.py $DB --by-grid > $OUT/bench_kernel_stats_by_grid.md 2>> $OUT/bench_kernel_stats.err
