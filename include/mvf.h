@@ -402,9 +402,36 @@ int mvf_eval_affine(const void* x4, int64_t n, const void* ctrl4, int64_t m, dou
  * One launch, one lane per trajectory, control points staged in LDS.  A negative dt integrates backwards.
  * Replaces the field evaluations inside dynamo `fate` as driven by `morphopath`
  * (spateo/tdr/morphometrics/morphofield/trajectory.py:61-109).  The integrator itself is this repo's (fixed-step RK4,
- * uniform time sampling): dynamo's adaptive RK45 + arc-length resampling lives outside the reference tree. */
+ * uniform time sampling); mvf_integrate_rk45 below is the adaptive RK45 + arc-length resampling dynamo `fate` runs. */
 int mvf_integrate(const void* x4, int64_t n, const void* ctrl4, int64_t m, double beta, const double* C,
                   const double* affine, double dt, int substeps, int n_out, double* traj, mvf_dtype dtype, void* stream);
+
+/* Sampling of mvf_integrate_rk45 */
+typedef enum { MVF_RK45_UNIFORM_TIME = 0, MVF_RK45_ARC_LENGTH = 1 } mvf_rk45_sampling;
+
+/* Adaptive integration of dx/dt = v(x), v as in mvf_integrate, with SciPy 1.15.3's RK45 (`solve_ivp(method="RK45")`)
+ * step for step: Dormand-Prince 5(4) with FSAL, select_initial_step, the step-size controller (SAFETY 0.9, factors
+ * [0.2, 10], h in [10 ulp(t), max_step], clipped to t_bound), the RMS error norm over the first `d` components, the
+ * quartic dense output, and a terminal event where every |v_i| (i < d) < 1e-5, detected between accepted steps as a
+ * change of the event's sign and located on the dense output to 4 EPS; the path then ends at (root, sol(root)).
+ * Step control, the event and the arc length run in WORLD coordinates y = q * scale + offset per axis (q = the point as
+ * x4 holds it): `world` is a HOST array {scale[3], offset[3]} (scale non-zero).  t_bound is signed (< 0 = backwards),
+ * rtol / atol > 0, max_step > 0 (may be +inf), max_steps >= 1 caps the step attempts (accepted + rejected) per trajectory.
+ * sampling: MVF_RK45_UNIFORM_TIME = n_out samples at k t_bound / (n_out - 1) on the dense output (after a terminal event
+ * the remaining samples hold the event state); MVF_RK45_ARC_LENGTH = n_out points equally spaced in arc length along the
+ * polyline of accepted step points, their times by linear interpolation along it (np.interp; uniform times over
+ * [0, t_end] when the path has length 0), their states on the dense output (two passes over the same steps, no workspace).
+ * Outputs (DEVICE, float64 unless stated): t = [n][n_out], traj = [n][n_out][3] (world coordinates, sample 0 = start),
+ * stats = int32 [n][4] = {accepted steps, rejected steps, field evaluations, status}; status 0 = reached t_bound,
+ * 1 = terminal event, -1 = step size below the spacing of t (SciPy's failure; the partial path is kept and the remaining
+ * samples hold its last point), -2 = max_steps reached (same), -3 = non-finite start row (t and traj are NaN).
+ * n == 0 launches nothing; invalid arguments are rejected before any HIP call.
+ * Replaces: dynamo `fate` as `morphopath` drives it, spateo/tdr/morphometrics/morphofield/trajectory.py:61-110
+ * (solve_ivp RK45 per cell, max_step = t_end / interpolation_num, dense output, arc-length resampling). */
+int mvf_integrate_rk45(const void* x4, int64_t n, const void* ctrl4, int64_t m, double beta, const double* C,
+                       const double* affine, int d, const double* world, double t_bound, double rtol, double atol,
+                       double max_step, int max_steps, int sampling, int n_out, double* t, double* traj, int* stats,
+                       mvf_dtype dtype, void* stream);
 
 #ifdef __cplusplus
 }

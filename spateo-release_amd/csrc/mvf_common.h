@@ -111,6 +111,30 @@ __device__ __forceinline__ double block_min(double v, double* sm) {
     return t;
 }
 
+// v_out = alpha * (K @ C) + A q + b  (q = the UNSCALED, centred query point as passed in x4);  J_out = jmul * J.
+// Identity for the sparsevfc field; the affine part carries the GP variant's norm_dict scaling and rigid transform
+// (spateo/tdr/morphometrics/morphofield/gaussian_process.py:102-127, GPVectorField.py:158-159,190).
+struct EvalAffine {
+    double alpha[3], jmul;  // alpha per output component (the GP variant's scale_fixed may be per axis)
+    double A[9];
+    double b[3];
+};
+
+// the host array {alpha[3], jmul, A[9] row-major, b[3]} of mvf_eval_affine (NULL = identity)
+inline EvalAffine eval_affine_from_host(const double* affine) {
+    EvalAffine af;
+    af.alpha[0] = af.alpha[1] = af.alpha[2] = 1.0, af.jmul = 1.0;
+    for (int i = 0; i < 9; ++i) af.A[i] = 0.0;
+    for (int i = 0; i < 3; ++i) af.b[i] = 0.0;
+    if (affine) {
+        for (int i = 0; i < 3; ++i) af.alpha[i] = affine[i];
+        af.jmul = affine[3];
+        for (int i = 0; i < 9; ++i) af.A[i] = affine[4 + i];
+        for (int i = 0; i < 3; ++i) af.b[i] = affine[13 + i];
+    }
+    return af;
+}
+
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -13,15 +13,6 @@
 namespace mvf {
 
 
-// v_out = alpha * (K @ C) + A q + b  (q = the UNSCALED, centred query point as passed in x4);  J_out = jmul * J.
-// Identity for the sparsevfc field; the affine part carries the GP variant's norm_dict scaling and rigid transform
-// (spateo/tdr/morphometrics/morphofield/gaussian_process.py:102-127, GPVectorField.py:158-159,190).
-struct EvalAffine {
-    double alpha[3], jmul;  // alpha per output component (the GP variant's scale_fixed may be per axis)
-    double A[9];
-    double b[3];
-};
-
 // Everything that is derived from v and the Jacobian sums of ONE query point (lane-local, float64 registers).
 // Jraw[f][i] = sum_m K_m C[m, f] (p - c_m)_i on the SCALED coordinates; J = Jraw * jscale * af.jmul.
 struct EvalOut {

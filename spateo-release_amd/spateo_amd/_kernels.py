@@ -584,6 +584,32 @@ class HipKernels:
         return traj
 
     @_on_device
+    def integrate_rk45(self, x4, ctrl4, beta, C, d, world, t_bound, rtol, atol, max_step, max_steps, sampling, n_out,
+                       affine=None):
+        """SciPy-RK45 trajectories of dx/dt = v(x) (mvf.h: mvf_integrate_rk45).  `world` = (scale (3,), offset (3,)) maps
+        the x4 coordinates to the caller's (y = q * scale + offset), `sampling` = _lib.RK45_UNIFORM_TIME | RK45_ARC_LENGTH.
+        Returns host arrays (t (n, n_out), traj (n, n_out, 3) in world coordinates, stats (n, 4) int32 = accepted,
+        rejected, field evaluations, status), copied back in one transfer."""
+        import ctypes
+
+        n, m = x4.shape[0], ctrl4.shape[0]
+        # one device buffer: t | traj | stats (n x 4 int32 = n x 2 float64), so that one copy brings everything back
+        buf = torch.empty(n * (4 * n_out + 2), dtype=torch.float64, device=self.device)
+        t = buf[: n * n_out].view(n, n_out)
+        traj = buf[n * n_out : 4 * n * n_out].view(n, n_out, 3)
+        stats = buf[4 * n * n_out :].view(torch.int32).view(n, 4)
+        scale, offset = world
+        w = (ctypes.c_double * 6)(*[float(v) for v in np.asarray(scale, dtype=np.float64).reshape(3)],
+                                  *[float(v) for v in np.asarray(offset, dtype=np.float64).reshape(3)])
+        _lib.check(self.lib.mvf_integrate_rk45(_ptr(x4), n, _ptr(ctrl4), m, float(beta), _ptr(C), self._affine_buf(affine),
+                                               int(d), w, float(t_bound), float(rtol), float(atol), float(max_step),
+                                               int(max_steps), int(sampling), int(n_out), _ptr(t), _ptr(traj),
+                                               _ptr(stats), self.cdtype, self._stream()), "mvf_integrate_rk45")
+        (host,) = self.to_host([buf], own_pinned=False)
+        return (host[: n * n_out].reshape(n, n_out), host[n * n_out : 4 * n * n_out].reshape(n, n_out, 3),
+                host[4 * n * n_out :].view(np.int32).reshape(n, 4))
+
+    @_on_device
     def eval(self, x4, ctrl4, beta, C, flags, affine=None):
         """Fused evaluator.  Returns a dict of float64 device tensors for the requested MVF_EVAL_* flags.
         `affine` = (alpha, jmul, A (3x3), b (3)) applies v = alpha K@C + A q + b, J = jmul J (GP variant)."""

@@ -29,6 +29,7 @@ MVF_ESTEP_MIN_DOUBLES = 4098
 MVF_COMM_ID_BYTES = 128
 RED_SUM, RED_MIN = 0, 1
 GRAM_TILES, GRAM_RHS, GRAM_REDUCE, GRAM_REDUCE_RHS = 1, 2, 4, 8
+RK45_UNIFORM_TIME, RK45_ARC_LENGTH = 0, 1
 EVAL_V, EVAL_JAC, EVAL_DIV, EVAL_CURL, EVAL_ACC, EVAL_CURV, EVAL_TORS, EVAL_JDET = 1, 2, 4, 8, 16, 32, 64, 128
 
 _p, _i64, _i, _d, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_size_t
@@ -87,6 +88,8 @@ SIGNATURES = {
     "mvf_eval_affine": (_i, [_p, _i64, _p, _i64, _d, _p, C.POINTER(C.c_double), _i, _p, _p, _p, _p, _p, _p, _p, _p, _i,
                              _p]),
     "mvf_integrate": (_i, [_p, _i64, _p, _i64, _d, _p, C.POINTER(C.c_double), _d, _i, _i, _p, _i, _p]),
+    "mvf_integrate_rk45": (_i, [_p, _i64, _p, _i64, _d, _p, C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _d, _d,
+                                _d, _d, _i, _i, _i, _p, _p, _p, _i, _p]),
 }
 
 _lib = None

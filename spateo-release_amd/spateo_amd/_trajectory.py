@@ -56,15 +56,21 @@ def _arc_length_resample(tk, xk, vk, n_out, stop_tol=1e-5):
 
 def integrate_field(vf_dict, init_states, t_end=None, interpolation_num=250, direction="forward", average=False,
                     nonrigid_only=False, substeps=4, dtype=None, device=None, max_cells_per_launch=1 << 16,
-                    sampling="arc_length"):
-    """Integrate dx/dt = v(x) from every row of ``init_states`` on the GPU (fused RK4 kernel).
+                    sampling="arc_length", integrator="rk4", rtol=1e-3, atol=1e-6, max_steps=100_000):
+    """Integrate dx/dt = v(x) from every row of ``init_states`` on the GPU (fused RK4 kernel, or SciPy's RK45).
 
     Returns ``(t, prediction)``: lists with one entry per trajectory, ``t[i]`` (n_t,), ``prediction[i]`` (n_t, d).
     ``sampling="arc_length"`` (dynamo ``fate``'s default, which ``morphopath`` inherits): ``interpolation_num`` points
     equally spaced in arc length along each path (twice as many for ``direction="both"``), every trajectory with its own
     times; the path ends early where the field is at rest (all |v| < 1e-5).  ``"uniform_time"``: ``interpolation_num``
     uniform times over [0, t_end] ("forward"), [-t_end, 0] ("backward") or both.
-    ``average``: False | "origin" (one trajectory from the mean start) | "trajectory" / True (mean over cells per sample)."""
+    ``average``: False | "origin" (one trajectory from the mean start) | "trajectory" / True (mean over cells per sample).
+    ``integrator``: "rk4" (default): fixed-step RK4, ``substeps`` steps per output interval (8 per interval of a 4x
+    finer dense plan in arc-length mode), the arc-length resampling on the host.  "rk45": dynamo ``fate``'s own procedure,
+    SciPy ``solve_ivp(method="RK45", rtol, atol, max_step=t_end / interpolation_num, dense_output=True)`` with the
+    terminal at-rest event, mirrored step for step in one kernel (``mvf_integrate_rk45``) that also samples the path;
+    ``substeps`` is ignored.  ``max_steps`` caps the step attempts per trajectory (SciPy has no cap): reaching it raises
+    MVFError; a step size below the spacing of t (SciPy's failure status) warns and keeps the partial path."""
     dtype = dtype or _rt._DEFAULT_DTYPE
     X0 = np.asarray(init_states, dtype=np.float64)
     if X0.ndim == 1:
@@ -73,6 +79,14 @@ def integrate_field(vf_dict, init_states, t_end=None, interpolation_num=250, dir
         raise ValueError("direction must be one of 'forward', 'backward', 'both'")
     if sampling not in ("arc_length", "uniform_time"):
         raise ValueError("sampling must be 'arc_length' or 'uniform_time'")
+    if integrator not in ("rk4", "rk45"):
+        raise ValueError(f"integrator must be 'rk4' or 'rk45', got {integrator!r}")
+    if integrator == "rk45":
+        for name, v in (("rtol", rtol), ("atol", atol)):
+            if not (isinstance(v, (int, float, np.floating)) and np.isfinite(v) and v > 0):
+                raise ValueError(f"{name} must be a finite number > 0, got {v!r}")
+        if int(max_steps) != max_steps or max_steps < 1 or max_steps > np.iinfo(np.int32).max:
+            raise ValueError(f"max_steps must be a positive integer, got {max_steps!r}")
     method = vf_dict.get("method", "sparsevfc")
     if t_end is None:
         t_end = _default_t_end(np.asarray(vf_dict["X"], dtype=float), vf_dict["V"])
@@ -80,6 +94,8 @@ def integrate_field(vf_dict, init_states, t_end=None, interpolation_num=250, dir
     n_t = int(interpolation_num)
     if n_t < 2:
         raise ValueError("interpolation_num must be >= 2")
+    if integrator == "rk45" and not (np.isfinite(t_end) and t_end > 0):
+        raise ValueError(f"t_end must be finite and > 0 for integrator='rk45', got {t_end!r}")
     if average == "origin":
         X0 = X0.mean(0, keepdims=True)
     d = X0.shape[1]
@@ -107,6 +123,7 @@ def integrate_field(vf_dict, init_states, t_end=None, interpolation_num=250, dir
         start = (X0 - mean_t) / stt
         to_world = lambda q: q * stt + mean_t  # noqa: E731
         vscale = stt
+        world = (stt3, pad(center * stt + mean_t))  # the kernel's q = start - center -> world coordinates
     else:
         ctrl = np.asarray(vf_dict["X_ctrl"], dtype=np.float64)
         Cc = np.asarray(vf_dict["C"], dtype=np.float64)
@@ -115,6 +132,7 @@ def integrate_field(vf_dict, init_states, t_end=None, interpolation_num=250, dir
         start = X0
         to_world = lambda q: q  # noqa: E731
         vscale = 1.0
+        world = (np.ones(3), np.concatenate([center, np.zeros(3 - len(center))]))
     if ctrl.shape[1] > 3 or Cc.shape[1] != ctrl.shape[1]:
         raise NotImplementedError("trajectory integration needs a field with Dy == D <= 3")
     C3 = np.zeros((len(ctrl), 3))
@@ -123,12 +141,37 @@ def integrate_field(vf_dict, init_states, t_end=None, interpolation_num=250, dir
     c4 = k.to_x4(ctrl, center)
     beta = float(vf_dict["beta"])
     arc = sampling == "arc_length"
-    n_fine = 4 * n_t + 1 if arc else n_t  # dense RK4 samples the arc-length resampling works from
+    n_fine = 4 * n_t + 1 if arc and integrator == "rk4" else n_t  # dense RK4 samples the arc-length resampling works from
     dt = t_end / (n_fine - 1)
     tf = np.linspace(0.0, t_end, n_fine)
 
+    def run_rk45(sign):
+        """The same for the RK45 kernel: it samples the path itself, in world coordinates."""
+        ts, xs = [], []
+        for lo in range(0, len(start), max_cells_per_launch):
+            x4 = k.to_x4(start[lo : lo + max_cells_per_launch], center)
+            t, x, stats = k.integrate_rk45(x4, c4, beta, Cd, ctrl.shape[1], world, sign * t_end, rtol, atol, t_end / n_t,
+                                           int(max_steps), _lib.RK45_ARC_LENGTH if arc else _lib.RK45_UNIFORM_TIME,
+                                           n_t, affine=affine)
+            capped = np.nonzero(stats[:, 3] == -2)[0]
+            if len(capped):
+                raise _lib.MVFError(f"integrate_field(integrator='rk45'): trajectories {(capped + lo).tolist()[:20]} "
+                                    f"reached max_steps={int(max_steps)} before t_end (raise max_steps)")
+            failed = np.nonzero(stats[:, 3] == -1)[0]
+            if len(failed):
+                import warnings
+
+                warnings.warn(f"integrate_field(integrator='rk45'): trajectories {(failed + lo).tolist()[:20]}: required "
+                              "step size is less than spacing between numbers; the partial paths are kept",
+                              RuntimeWarning, stacklevel=3)
+            ts.append(t)
+            xs.append(x[:, :, :d])
+        return (np.concatenate(ts, axis=0) if arc else sign * tf), np.concatenate(xs, axis=0)
+
     def run(sign):
         """(times (n, n_t) or (n_fine,), states (n, n_t, d)) in world coordinates for one direction."""
+        if integrator == "rk45":
+            return run_rk45(sign)
         ts, xs = [], []
         for lo in range(0, len(start), max_cells_per_launch):
             x4 = k.to_x4(start[lo : lo + max_cells_per_launch], center)

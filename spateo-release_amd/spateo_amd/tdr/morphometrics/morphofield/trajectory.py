@@ -8,7 +8,10 @@ integration runs in ONE fused HIP kernel (``mvf_integrate``: classical RK4, one 
 interval) and the same semantics are applied to its finely sampled paths (``vectorfield.integrate_field``,
 ``sampling="arc_length"``; ``sampling="uniform_time"`` is available through ``**kwargs``).  dynamo's source is not
 available here, so its restatement (``oracle/trajectory_oracle.py``) is parity-unpinned; agreement is to the
-reference solver's own tolerance (rtol 1e-3).  Output slots are the reference's: ``uns[key_added]["t"][i]`` (times) and
+reference solver's own tolerance (rtol 1e-3).  ``integrator="rk45"`` (through ``**kwargs``, with ``rtol``, ``atol``,
+``max_steps``) opts into the procedure ``fate`` hands to SciPy: ``solve_ivp`` RK45 with its step control, dense output
+and the at-rest terminal event, reproduced step for step in one kernel (``mvf_integrate_rk45``) that also does the
+arc-length sampling; it matches SciPy to ~1e-9 of the data's extent instead of 1e-3.  Output slots are the reference's: ``uns[key_added]["t"][i]`` (times) and
 ``uns[key_added]["prediction"][i]`` ((n_t, d) states: the reference transposes dynamo ``fate``'s (d, n_t) arrays,
 ``trajectory.py:113``, and its consumer concatenates ``init_states[[i]]`` with it along axis 0,
 ``tdr/models/models_migration/morphopath_model.py:225``) per cell; ``init_cells`` = the cells' ``obs_names``."""
