@@ -396,6 +396,28 @@ int mvf_eval_affine(const void* x4, int64_t n, const void* ctrl4, int64_t m, dou
                     const double* affine, int flags, double* v, double* jac, double* div, double* curl, double* acc,
                     double* curv, double* tors, double* jdet, mvf_dtype dtype, void* stream);
 
+/* ---- fields in 4 to 8 dimensions (ABI 7) ----------------------------------------------------------------------
+ * The points are plain row-major n x d arrays of the cell dtype (NOT x4), centred by the caller, 4 <= d <= 8 (the bound of
+ * mvf_con_k).  K(x, c) is bit-identical to mvf_con_k at the same d.  Arguments are validated before any HIP call.
+ *
+ * mvf_ublk_build_d: the kernel-value cache of mvf_ublk_build (same layout Ublk[m/16][n][16], same zero padding, same size
+ * mvf_ublk_bytes) for d-dimensional cells x (n x d) and control points ctrl (m x d).  mvf_gram_cached's TILES and REDUCE
+ * stages, mvf_rhs_cached, mvf_apply_cached and the E-step read only the cache, P, Y and the coefficients, so an EM
+ * iteration runs unchanged on it.
+ * Replaces: `U = con_K(X, ctrl_pts, beta)` of dynamo SparseVFC with `_con_K`
+ * spateo/tdr/morphometrics/morphofield/gaussian_process.py:16-36 on d-column `obsm` coordinates
+ * (interpolations/interpolation_sparseVFC.py:45,63). */
+int mvf_ublk_build_d(const void* x, int64_t n, const void* ctrl, int64_t m, int d, double beta, void* ublk,
+                     size_t ublk_bytes, mvf_dtype dtype, void* stream);
+/* mvf_eval_d: the fused evaluator of mvf_eval for x (n x d), ctrl (m x d) and C (m x dy float64, row-major), 1 <= dy <= 8.
+ * Outputs float64, NULL if not requested: v n x dy;  jac (dy, d, n) = J[f][i][q] (the reference's layout);  and, for
+ * dy == d only, div n, acc = J v n x d, curv (formula 2) n x d.  flags: MVF_EVAL_V | _JAC | _DIV | _ACC | _CURV (curl,
+ * torsion and det are not defined here).  Deterministic; v alone is one 16-column MFMA product.
+ * Replaces: dynamo `vector_field_function` / `Jacobian_rkhs_gaussian` and compute_{acceleration,curvature,divergence} =
+ * morphofield_dg/GPVectorField.py:143-190 and :12-52, 97-121 at 4 <= d <= 8. */
+int mvf_eval_d(const void* x, int64_t n, const void* ctrl, int64_t m, int d, double beta, const double* C, int dy,
+               int flags, double* v, double* jac, double* div, double* acc, double* curv, mvf_dtype dtype, void* stream);
+
 /* ---- trajectory integration (morphopath) ------------------------------------------------------------------------
  * Integrates dx/dt = v(x), v as in mvf_eval_affine, from the n start points x4 with classical RK4: n_out samples per
  * trajectory, `dt` apart, `substeps` RK4 steps between samples; traj (float64) = [n][n_out][3], traj[:, 0] = start.

@@ -69,6 +69,20 @@ __device__ __forceinline__ T kernel_value(T px, T py, T pz, T cx, T cy, T cz) {
     return exp2_neg(-e);
 }
 
+// The same kernel value in D dimensions (4 <= D <= 8: mvf_ublk_build_d, mvf_eval_d), bit-identical to what conk_kernel
+// computes for a general d (mvf_conk.hip): p and c pre-scaled by sqrt(beta*log2e) in the cell dtype, the squared distance
+// accumulated as e = fma(t_k, t_k, e) in index order from 0.  The 3-D kernel_value above stays the one every x4 kernel uses.
+template <int D, typename T>
+__device__ __forceinline__ T kernel_value_d(const T (&p)[D], const T (&c)[D]) {
+    T e = T(0);
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const T t = p[k] - c[k];
+        e = fma(t, t, e);
+    }
+    return exp2_neg(-e);
+}
+
 // ---- wave / block reductions (wave64 shuffles, then LDS across waves) ----
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

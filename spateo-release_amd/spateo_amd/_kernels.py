@@ -75,6 +75,16 @@ class HipKernels:
         c = None if center is None else np.asarray(center, dtype=np.float64)[None, : a.shape[1]]
         return self.h2d_padded(a, 4, self.tdtype, minus=c)
 
+    @_on_device
+    def to_xd(self, arr, center=None):
+        """Host (n, d) float64 array, 4 <= d <= 8 -> device (n, d) tensor of the cell dtype (plain rows: what
+        mvf_ublk_build_d / mvf_eval_d read), optionally centred - the same float64 subtraction and rounding as to_x4."""
+        a = np.asarray(arr, dtype=np.float64)
+        if a.ndim != 2 or not (4 <= a.shape[1] <= 8):
+            raise ValueError(f"expected an (n, d) array with 4 <= d <= 8, got shape {a.shape}")
+        c = None if center is None else np.asarray(center, dtype=np.float64)[None, : a.shape[1]]
+        return self.h2d_padded(a, a.shape[1], self.tdtype, minus=c)
+
     # pinned staging: host arrays up to this size travel through page-locked tensors of torch's caching host allocator
     # (one DMA, no driver-side bounce copies); larger ones keep the pageable path so that a fit of 8 M cells does not
     # leave hundreds of MB of the host page-locked for the life of the process
@@ -346,6 +356,20 @@ class HipKernels:
                                            self.cdtype, self._stream()), "mvf_ublk_build")
         self._ublk_key = (x4.data_ptr(), ctrl4.data_ptr(), n, m, float(beta))
 
+    @_on_device
+    def build_ublk_d(self, xd, ctrld, beta):
+        """build_ublk for 4 <= d <= 8: xd (n, d), ctrld (m, d) from to_xd (mvf_ublk_build_d, same cache layout).  A `gram`
+        call with the same (xd, ctrld, beta) then runs its tile and reduce stages on the cache (neither reads the points)."""
+        n, m, d = xd.shape[0], ctrld.shape[0], xd.shape[1]
+        if ctrld.shape[1] != d:
+            raise ValueError(f"cells have {d} columns, control points {ctrld.shape[1]}")
+        need = self.ublk_bytes(n, m)
+        self._ublk = None
+        self._ublk = torch.empty(need // self._ublk_itemsize(), dtype=self.tdtype, device=self.device)
+        _lib.check(self.lib.mvf_ublk_build_d(_ptr(xd), n, _ptr(ctrld), m, d, float(beta), _ptr(self._ublk), need,
+                                             self.cdtype, self._stream()), "mvf_ublk_build_d")
+        self._ublk_key = (xd.data_ptr(), ctrld.data_ptr(), n, m, float(beta))
+
     def _ublk_itemsize(self):
         return 4 if self.tdtype == torch.float32 else 8
 
@@ -388,10 +412,12 @@ class HipKernels:
         self._ublk_key = None
 
     @_on_device
-    def gram(self, x4, P, y4, ctrl4, beta, G, R, rhs_only=False, tiles_only=False):
+    def gram(self, x4, P, y4, ctrl4, beta, G, R, rhs_only=False, tiles_only=False, cache_only=False):
         """G = U^T P U (m x m), R = U^T P Y (m x 3).  rhs_only: only R for this y4 (G unchanged) - for Y wider than 3,
         and the second half of a multi-rank step; tiles_only: only G (tile stage + its reduction) - the first half of a
-        multi-rank step, whose all-reduce of G then overlaps the rhs kernels."""
+        multi-rank step, whose all-reduce of G then overlaps the rhs kernels.  cache_only: raise unless the cache of
+        build_ublk / build_ublk_d for these (x4, ctrl4, beta) is there (4 <= D <= 8: x4 then holds plain (n, D) rows, which
+        the regenerating kernels would misread as x4 vectors)."""
         n, m = x4.shape[0], ctrl4.shape[0]
         key = (n, m, _lib.OPTION_EPOCH[0])
         need = self._gram_need.get(key)
@@ -403,6 +429,9 @@ class HipKernels:
         args = (_ptr(x4), _ptr(P), _ptr(y4), n, _ptr(ctrl4), m, float(beta), _ptr(G), _ptr(R), _ptr(self._gram_ws),
                 self._gram_ws.numel())
         cached = self._ublk is not None and self._ublk_key == (x4.data_ptr(), ctrl4.data_ptr(), n, m, float(beta))
+        if cache_only and not cached:
+            raise _lib.MVFError("gram: the kernel-value cache of these points is not built (no regenerating Gram kernel "
+                                "reads plain (n, D) rows)")
         if cached:
             def run(stages):
                 _lib.check(self.lib.mvf_gram_cached(stages, _ptr(self._ublk), *args, self.cdtype, self._stream()),
@@ -636,4 +665,26 @@ class HipKernels:
         _lib.check(self.lib.mvf_eval_affine(_ptr(x4), n, _ptr(ctrl4), m, float(beta), _ptr(C), aff, int(flags), _ptr(v),
                                             _ptr(jac), _ptr(div), _ptr(curl), _ptr(acc), _ptr(curv), _ptr(tors),
                                             _ptr(jdet), self.cdtype, self._stream()), "mvf_eval_affine")
+        return out
+
+    @_on_device
+    def eval_d(self, xd, ctrld, beta, C, flags):
+        """Fused evaluator for 4 <= d <= 8 (mvf_eval_d): xd (n, d), ctrld (m, d) from to_xd, C (m, dy) float64 device
+        tensor, dy <= 8.  Returns {flag: float64 device tensor}: v (n, dy), jac (dy, d, n), and for dy == d div (n,),
+        acc (n, d), curv (n, d)."""
+        n, d = xd.shape
+        m, dy = C.shape
+        if ctrld.dim() != 2 or ctrld.shape[1] != d or ctrld.shape[0] != m:
+            raise ValueError(f"eval_d: points (n, {d}), control points {tuple(ctrld.shape)} and coefficients {tuple(C.shape)} "
+                             f"disagree")
+        if xd.dtype != self.tdtype or ctrld.dtype != self.tdtype or C.dtype != torch.float64:
+            raise TypeError(f"eval_d: expected {self.tdtype} points and float64 coefficients, got {xd.dtype} / {ctrld.dtype} / "
+                            f"{C.dtype}")
+        C = C.contiguous()
+        f64 = torch.float64
+        shapes = {_lib.EVAL_V: (n, dy), _lib.EVAL_JAC: (dy, d, n), _lib.EVAL_DIV: (n,), _lib.EVAL_ACC: (n, d),
+                  _lib.EVAL_CURV: (n, d)}
+        out = {f: torch.empty(*s, dtype=f64, device=self.device) for f, s in shapes.items() if flags & f}
+        _lib.check(self.lib.mvf_eval_d(_ptr(xd), n, _ptr(ctrld), m, d, float(beta), _ptr(C), dy, int(flags),
+                                       *(_ptr(out.get(f)) for f in shapes), self.cdtype, self._stream()), "mvf_eval_d")
         return out

@@ -99,6 +99,10 @@ def integrate_field(vf_dict, init_states, t_end=None, interpolation_num=250, dir
     if average == "origin":
         X0 = X0.mean(0, keepdims=True)
     d = X0.shape[1]
+    ctrl_key, coef_key = ("inducing_variables", "Coff") if method == "gaussian_process" else ("X_ctrl", "C")
+    field_d = np.shape(vf_dict[ctrl_key])[-1]
+    if field_d > 3 or np.shape(vf_dict[coef_key])[-1] != field_d:  # (before the 3-wide padding below)
+        raise NotImplementedError("trajectory integration needs a field with Dy == D <= 3")
     k = _shared_kernels(device, dtype)
     if method == "gaussian_process":
         from .vectorfield import _gp_scalars  # (the GP variant's norm_dict rules live beside its evaluator)
@@ -133,8 +137,6 @@ def integrate_field(vf_dict, init_states, t_end=None, interpolation_num=250, dir
         to_world = lambda q: q  # noqa: E731
         vscale = 1.0
         world = (np.ones(3), np.concatenate([center, np.zeros(3 - len(center))]))
-    if ctrl.shape[1] > 3 or Cc.shape[1] != ctrl.shape[1]:
-        raise NotImplementedError("trajectory integration needs a field with Dy == D <= 3")
     C3 = np.zeros((len(ctrl), 3))
     C3[:, : Cc.shape[1]] = Cc
     Cd = k.h2d(C3)

@@ -28,7 +28,7 @@ from . import _lib
 from . import _runtime as _rt
 from ._runtime import (DEFLATED_MIN_M, _check_lstsq_method, _Phases, _shared_kernels, _TLS, _to_host,  # noqa: F401
                        clear_eval_cache, last_fit_profile, set_default_dtype)
-from .engine import SparseVFCEngine, _current_device, _dist_info, _gather_rows_np, shard_bounds  # noqa: F401
+from .engine import MAX_DIM, SparseVFCEngine, _current_device, _dist_info, _gather_rows_np, shard_bounds  # noqa: F401
 from .preprocess import (bandwidth_selector, finite_rows, sample_by_velocity, sparsevfc_preprocess, unique_rows,  # noqa: F401
                          _sample_by_norms, _sparsevfc_preprocess)
 
@@ -134,11 +134,12 @@ def _digest(X):
     return xxhash.xxh3_128_intdigest(np.ascontiguousarray(X))
 
 
-def _fused_eval(X, sig, flags, k, launch, rows3=False):
+def _fused_eval(X, sig, flags, k, launch, rows3=False, bytes_per_point=_EVAL_BYTES_PER_POINT, prefetch=_EVAL_ALL):
     """Host arrays {flag: ndarray} of the requested quantities; ``launch(flags) -> {flag: device tensor}``.
     rows3: every (n, 3) quantity comes back as (n, 3, 3) with its row repeated - the reference's ``zeros((n, 3, 3))`` quirk of
     curl and torsion - expanded on the DEVICE and copied once into page-locked memory (np.repeat on the host wrote the same
-    19 MB of the 64^3 grid at 16 GB/s: 1.2 ms of a 3.9 ms call pair)."""
+    19 MB of the 64^3 grid at 16 GB/s: 1.2 ms of a 3.9 ms call pair).  prefetch: what a launch may add to the request when
+    everything fits (the quantities that cost it no more than stores)."""
     sig = tuple(np.array(a, dtype=np.float64) if isinstance(a, (np.ndarray, list, tuple)) else a for a in sig)
     ent = _TLS.__dict__.get("fused")
     if ent is None or ent.k is not k or not ent.matches(X, sig):
@@ -146,7 +147,7 @@ def _fused_eval(X, sig, flags, k, launch, rows3=False):
         ent.k = k
     missing = flags & ~ent.flags
     if missing:
-        want = _EVAL_ALL if len(X) * _EVAL_BYTES_PER_POINT <= _EVAL_PREFETCH_CAP else missing
+        want = prefetch | missing if len(X) * bytes_per_point <= _EVAL_PREFETCH_CAP else missing
         want &= ~ent.flags
         ent.dev.update(launch(want))
         ent.flags |= want
@@ -166,8 +167,10 @@ def _field_on_device(x, vf_dict, flags, dtype=None, device=None, rows3=False):
     d = Xc.shape[1]
     if x.shape[1] != d:
         raise ValueError(f"query points have {x.shape[1]} dimensions, the vector field has {d}")
-    if d > 3 or Cc.shape[1] > 3:
-        raise NotImplementedError("the HIP evaluators support up to 3 dimensions")
+    if d > 3:
+        return _field_on_device_d(x, Xc, Cc, vf_dict, flags, dtype, device)
+    if Cc.shape[1] > 3:
+        raise NotImplementedError("the HIP evaluators support up to 3 output columns on fields of up to 3 dimensions")
     k = _shared_kernels(device, dtype)
     beta = float(vf_dict["beta"])
 
@@ -181,6 +184,44 @@ def _field_on_device(x, vf_dict, flags, dtype=None, device=None, rows3=False):
         return k.eval(x4, c4, beta, Cd, fl)
 
     return _fused_eval(x, ("svc", Xc, Cc, beta), flags, k, launch, rows3)
+
+
+_EVAL_D_FLAGS = _lib.EVAL_V | _lib.EVAL_JAC | _lib.EVAL_DIV | _lib.EVAL_ACC | _lib.EVAL_CURV
+
+
+def _field_on_device_d(x, Xc, Cc, vf_dict, flags, dtype, device):
+    """_field_on_device for 4 <= d <= 8 (mvf_eval_d on plain (n, d) rows): v for any number of output columns (groups of 8),
+    the Jacobian for up to 8, divergence / acceleration / curvature for dy == d.  Curl, torsion and det are 3-D quantities
+    (SvcVectorField refuses them before they get here, as the reference does)."""
+    d, dy = Xc.shape[1], Cc.shape[1]
+    if d > 8:
+        raise NotImplementedError(f"the HIP evaluators support 1 to 8 dimensions, the vector field has {d}")
+    if flags & ~_EVAL_D_FLAGS:
+        raise NotImplementedError("curl, torsion and the determinant are evaluated on 1- to 3-dimensional fields only")
+    if flags & ~_lib.EVAL_V and dy > 8:
+        raise NotImplementedError(f"the HIP Jacobian of a {d}-dimensional field supports up to 8 output columns, got {dy}")
+    if flags & (_lib.EVAL_DIV | _lib.EVAL_ACC | _lib.EVAL_CURV) and dy != d:
+        raise ValueError(f"divergence, acceleration and curvature need a field with as many output columns as dimensions "
+                         f"({dy} != {d})")
+    k = _shared_kernels(device, dtype)
+    beta = float(vf_dict["beta"])
+    # what one launch can answer for this field.  v alone is one 16-column product; once the Jacobian's columns are formed
+    # (any other quantity) the rest of what `can` holds costs only its stores, so such a call keeps all of it for the next
+    can = _EVAL_D_FLAGS if dy == d else (_lib.EVAL_V | _lib.EVAL_JAC if dy <= 8 else _lib.EVAL_V)
+    prefetch = _lib.EVAL_V if flags == _lib.EVAL_V else can
+
+    def launch(fl):
+        fl &= can
+        center = Xc.mean(0)
+        xd, cd = k.to_xd(x, center), k.to_xd(Xc, center)
+        Cd = k.h2d(np.ascontiguousarray(Cc))
+        if dy <= 8:
+            return k.eval_d(xd, cd, beta, Cd, fl)
+        return {_lib.EVAL_V: torch.cat([k.eval_d(xd, cd, beta, Cd[:, c0 : c0 + 8], _lib.EVAL_V)[_lib.EVAL_V]
+                                        for c0 in range(0, dy, 8)], dim=1)}
+
+    per_point = 8 * (dy + dy * d + 1 + 2 * d)
+    return _fused_eval(x, ("svc", Xc, Cc, beta), flags, k, launch, bytes_per_point=per_point, prefetch=prefetch)
 
 
 def vector_field_function(x, vf_dict, dim=None, *, dtype=None, device=None):
@@ -255,6 +296,8 @@ def SparseVFC(
     Y = np.asarray(Y, dtype=float)
     if X.ndim != 2 or Y.ndim != 2 or len(X) != len(Y):
         raise ValueError("X and Y must be 2-D arrays with the same number of rows")
+    if not 1 <= X.shape[1] <= MAX_DIM:
+        raise NotImplementedError(f"the HIP path supports 1-{MAX_DIM} spatial dimensions, got {X.shape[1]}")
     if gather not in ("root", "all"):
         raise ValueError("gather must be 'root' or 'all'")
     ph = _Phases(device)
@@ -262,6 +305,8 @@ def SparseVFC(
     rank, world = _dist_info(distributed, group)
     shard_sizes = None
     multi = world > 1 or (bool(force_collectives) and bool(distributed))
+    if multi and X.shape[1] > 3:  # (refused before the first collective: every rank raises alike)
+        raise NotImplementedError(f"multi-rank fits support 1-3 spatial dimensions, got {X.shape[1]}")
     if not multi:
         valid_ind, Xv, Yv, idx, ctrl_pts, beta = sparsevfc_preprocess(
             X, Y, M=M, beta=beta, velocity_based_sampling=velocity_based_sampling, seed=seed, device=device
@@ -434,6 +479,8 @@ class SvcVectorField:
         J = o[_lib.EVAL_JAC][:d, :d, :]
         if d == 3:
             return J, o[_lib.EVAL_JDET]
+        if d > 3:  # (the reference loops np.linalg.det over the cells, differential_geometry.py:336-338)
+            return J, np.linalg.det(np.ascontiguousarray(J.transpose(2, 0, 1)))
         # the kernel works on zero-padded 3-D points: the d x d determinant of a 1-D / 2-D field is taken on the host
         return J, (J[0, 0] * J[1, 1] - J[0, 1] * J[1, 0] if d == 2 else J[0, 0].copy())
 
