@@ -322,3 +322,98 @@ class CpuKernels:
             den = np.sum(v * v, 1) * np.sum(a * a, 1)
             out[EVAL_TORS] = v * (aJa / den)[:, None]
         return {k: torch.from_numpy(np.ascontiguousarray(val)) for k, val in out.items()}
+
+
+class CpuKernelsWide(CpuKernels):
+    """CpuKernels + the kernel-value cache and the wide entry points (mvf_ublk_build, mvf_rhs_cached, mvf_apply_cached as
+    include/mvf.h describes them), so that the engine's wide branch - the padded Yd / Vd / Cd buffers, the scatter of Rd into
+    the three-column groups, the multi-rank order of gram(tiles_only) / sym_pack / rhs_wide - runs on the CPU.  A subclass:
+    with `build_ublk` present the engine's default cache_u="auto" asks the device for its free memory, so engines on this
+    class are built with cache_u=True and every test on the plain CpuKernels keeps its path.
+
+    The products read Yd / Cd only inside the live extents (rows < n, rows < m, columns < dy) and write only there; a shape
+    that the C entry point refuses (or that would make it read outside its buffers) raises ValueError."""
+
+    def __init__(self, device=None, dtype="float64"):
+        super().__init__(device, dtype)
+        self._U = None
+        self._ublk_key = None
+        self.calls = {"build_ublk": 0, "rhs_wide": 0, "apply_wide": 0, "apply": 0, "apply_y": 0, "gram_rhs": 0}
+
+    @staticmethod
+    def wide_pads(n, m):
+        return -(-int(n) // 256) * 256, -(-int(m) // 128) * 128
+
+    def ublk_bytes(self, n, m):
+        n_pad, m_pad = self.wide_pads(n, m)
+        return 8 * n_pad * m_pad
+
+    def build_ublk(self, x4, ctrl4, beta):
+        X, ctrl = _np(x4)[:, :3], _np(ctrl4)[:, :3]
+        n, m = len(X), len(ctrl)
+        if n <= 0 or m <= 0:
+            raise ValueError("build_ublk: need n > 0, m > 0")
+        self._U = svo.con_K(X, ctrl, beta).reshape(n, m)
+        self._ublk_key = (x4.data_ptr(), ctrl4.data_ptr(), n, m, float(beta))
+        self.calls["build_ublk"] += 1
+
+    def drop_ublk(self):
+        self._U = None
+        self._ublk_key = None
+
+    def _wide_args(self, who, n, m, dy, Yd, ldc=None, ldr=None):
+        if self._U is None:
+            raise RuntimeError(f"{who} needs the kernel-value cache (build_ublk)")
+        if not (n > 0 and m > 0 and dy >= 1):
+            raise ValueError(f"{who}: need n > 0, m > 0, dy >= 1")
+        if self._U.shape != (n, m):
+            raise ValueError(f"{who}: the cache holds {self._U.shape}, the call says {(n, m)}")
+        n_pad, m_pad = self.wide_pads(n, m)
+        dp = -(-dy // 16) * 16
+        if Yd.dim() != 2 or not Yd.is_contiguous() or Yd.shape[1] < dp or Yd.shape[1] % 16 or Yd.shape[0] < n_pad:
+            raise ValueError(f"{who}: Yd must be contiguous, {n_pad} rows x a multiple of 16 >= {dp} columns, got "
+                             f"{tuple(Yd.shape)}")
+        if ldc is not None and (ldc[1] < dp or ldc[1] % 16 or ldc[0] < m_pad):
+            raise ValueError(f"{who}: C must be {m_pad} rows x a multiple of 16 >= {dp} columns, got {tuple(ldc)}")
+        if ldr is not None and (ldr[1] < dy or ldr[0] < m):
+            raise ValueError(f"{who}: R must be at least {m} x {dy}, got {tuple(ldr)}")
+
+    def rhs_wide(self, P, Yd, dy, m, R):
+        n, m, dy = int(P.shape[0]), int(m), int(dy)
+        self._wide_args("rhs_wide", n, m, dy, Yd, ldr=tuple(R.shape))
+        if R.dtype != torch.float64 or not R.is_contiguous():
+            raise ValueError("rhs_wide: R must be contiguous float64")
+        UP = self._U.T * _np(P).astype(np.float64)[None, :]
+        R[:m, :dy] = torch.from_numpy(UP @ _np(Yd)[:n, :dy].astype(np.float64))
+        self.calls["rhs_wide"] += 1
+
+    def apply_wide(self, Cd, dy, m, Yd, P, Vd, r, stats):
+        n, m, dy = int(Vd.shape[0]), int(m), int(dy)
+        self._wide_args("apply_wide", n, m, dy, Yd, ldc=tuple(Cd.shape))
+        if Cd.dtype != torch.float64 or not Cd.is_contiguous():
+            raise ValueError("apply_wide: C must be contiguous float64")
+        if Vd.shape[1] != Yd.shape[1] or not Vd.is_contiguous() or r.shape[0] != n:
+            raise ValueError("apply_wide: Vd shares Yd's leading dimension; r holds n values")
+        if P is not None and stats is None:
+            raise ValueError("apply_wide: P given but stats is null")
+        V = self._U @ _np(Cd)[:m, :dy]
+        Vd[:, :dy] = torch.from_numpy(V).to(Vd.dtype)
+        rr = np.sum((_np(Yd)[:n, :dy].astype(np.float64) - _np(Vd)[:, :dy].astype(np.float64)) ** 2, 1)
+        r.copy_(torch.from_numpy(rr).to(r.dtype))
+        if P is not None:
+            stats[0] += float(_np(P).astype(np.float64) @ _np(r).astype(np.float64))
+        self.calls["apply_wide"] += 1
+
+    def apply(self, x4, ctrl4, beta, C, y4=None, P=None, stats=None):
+        self.calls["apply"] += 1
+        self.calls["apply_y"] += y4 is not None
+        return super().apply(x4, ctrl4, beta, C, y4, P, stats)
+
+    def gram(self, x4, P, y4, ctrl4, beta, G, R, rhs_only=False, tiles_only=False, cache_only=False):
+        n, m = x4.shape[0], ctrl4.shape[0]
+        cached = self._U is not None and self._ublk_key == (x4.data_ptr(), ctrl4.data_ptr(), n, m, float(beta))
+        if cache_only and not cached:
+            raise RuntimeError("gram: the kernel-value cache of these points is not built")
+        if not tiles_only:
+            self.calls["gram_rhs"] += 1
+        super().gram(x4, P, y4, ctrl4, beta, G, R, rhs_only=rhs_only, tiles_only=tiles_only)

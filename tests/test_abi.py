@@ -81,6 +81,38 @@ def test_error_channel_without_launching_anything():
     assert lib.mvf_solve_workspace_bytes(3000, 3) >= 3008 * 3072 * 8
 
 
+def test_wide_entry_points_reject_bad_arguments_without_launching():
+    """mvf_rhs_cached / mvf_apply_cached: every refusal returns a status, names the entry point in mvf_last_error and launches
+    nothing (the pointers below are never dereferenced; tests/test_gpu_wide.py repeats the calls on real device buffers)."""
+    from spateo_amd import _lib
+
+    lib = _lib.load()
+    p = ctypes.c_void_p(1)
+    n, m, dy = 1000, 100, 20
+    ws = lib.mvf_wide_workspace_bytes(n, m)
+    assert ws == 128 * 128 * 8 + 256  # one slice x one row tile x 128 columns of float64 partials + 8 apply workgroups' sums
+    assert lib.mvf_wide_workspace_bytes(0, m) == 0 and lib.mvf_wide_workspace_bytes(n, 0) == 0
+
+    def rhs(n=n, m=m, dy=dy, ldy=32, ldr=20, ws_bytes=ws, dtype=_lib.MVF_F32, ublk=p, wsp=p):
+        return lib.mvf_rhs_cached(ublk, p, p, n, m, dy, ldy, p, ldr, wsp, ws_bytes, dtype, None)
+
+    def app(n=n, m=m, dy=dy, ldy=32, ldc=32, ws_bytes=ws, dtype=_lib.MVF_F64, P=p, stats=p, Vd=p, wsp=p):
+        return lib.mvf_apply_cached(p, n, m, p, ldc, dy, p, ldy, P, Vd, p, stats, wsp, ws_bytes, dtype, None)
+
+    refused = [
+        (rhs, dict(ldy=16)), (rhs, dict(ldy=30)), (rhs, dict(ldr=19)), (rhs, dict(ws_bytes=ws - 1)), (rhs, dict(wsp=None)),
+        (rhs, dict(n=0)), (rhs, dict(m=0)), (rhs, dict(dy=0)), (rhs, dict(dtype=7)), (rhs, dict(ublk=None)),
+        (app, dict(ldy=16)), (app, dict(ldc=16)), (app, dict(ws_bytes=ws - 1)), (app, dict(wsp=None)), (app, dict(n=0)),
+        (app, dict(m=0)), (app, dict(dy=0)), (app, dict(dtype=7)), (app, dict(Vd=None)), (app, dict(stats=None)),
+    ]
+    for fn, kw in refused:
+        name = b"mvf_rhs_cached" if fn is rhs else b"mvf_apply_cached"
+        assert fn(**kw) != 0 and name in lib.mvf_last_error(), (name, kw, lib.mvf_last_error())
+    assert app(stats=None) != 0 and b"P given but stats is null" in lib.mvf_last_error()
+    assert rhs(ws_bytes=ws - 1) != 0 and b"workspace too small" in lib.mvf_last_error()
+    assert rhs(dtype=7) != 0 and b"bad dtype" in lib.mvf_last_error()
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
 def test_gram_workspace_is_bounded_by_a_fraction_of_the_kernel_value_cache():
     """The Gram tile stage runs 8 k-cell slices in phases that REUSE one partial-tile buffer: the workspace stays within

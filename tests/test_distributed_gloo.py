@@ -31,15 +31,21 @@ def _worker(rank, world, port, case, out_dir, mode="all"):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         import spateo_amd as st
-        from _cpu_kernels import CpuKernels
+        from _cpu_kernels import CpuKernels, CpuKernelsWide
         from spateo_amd._synthetic import make_config
 
         X, V, _ = make_config("C2", N=601)  # odd: uneven shards
+        Base = CpuKernelsWide if case == "wide_twin" else CpuKernels
         if case == "zeros":
             V[598:] += 60.0  # gross outliers that live only in the LAST shard: exp(-r/2s2) underflows there only
 
-        class Recording(CpuKernels):
+        class Recording(Base):
             fills = []
+            made = []
+
+            def __init__(self, *a, **kw):
+                super().__init__(*a, **kw)
+                Recording.made.append(self)
 
             def estep_p(self, r, sigma2, gamma, a, dy, minP, theta, zero_fill, P_out, stats):
                 Recording.fills.append(zero_fill)
@@ -66,11 +72,17 @@ def _worker(rank, world, port, case, out_dir, mode="all"):
             _v.SparseVFCEngine.minnorm_method = "lowrank"  # the rank-revealing solve regardless of M
         Grid = X[::30]
         kw = dict(M=25, lambda_=3.0, lstsq_method="scipy", MaxIter=6, seed=0)
-        if case == "wide":
+        if case in ("wide", "wide_twin"):
             V = np.column_stack([V, np.sin(X[:, 0] / 70), np.cos(X[:, 1] / 50)])  # Dy = 5: two column groups
         calls = {"unique": 0}
         import spateo_amd.preprocess as pre
         import spateo_amd.vectorfield as vfm
+
+        if case == "wide_twin":
+            # the twin with the kernel-value cache and the wide entry points: the engine is asked for the cache outright
+            # (its default asks the device for its free memory), everything else is SparseVFC's own path
+            Engine = vfm.SparseVFCEngine
+            vfm.SparseVFCEngine = lambda *a, **kw_: Engine(*a, **{**kw_, "cache_u": True})
 
         orig_unique = pre.unique_rows
 
@@ -97,7 +109,9 @@ def _worker(rank, world, port, case, out_dir, mode="all"):
         np.savez(os.path.join(out_dir, f"rank{rank}.npz"), V=got["V"], P=got["P"], C=got["C"], grid_V=got["grid_V"],
                  sigma2=got["sigma2"], iteration=got["iteration"], E=got["E_traj"], fills=np.array(Recording.fills),
                  unique_calls=calls["unique"], valid_ind=got["valid_ind"], vfc=got["VFCIndex"],
-                 hints=np.array(Recording.hints, dtype=np.int64))
+                 hints=np.array(Recording.hints, dtype=np.int64),
+                 wide_calls=np.array([[k_.calls[c] for c in ("build_ublk", "rhs_wide", "apply_wide", "apply_y", "gram_rhs")]
+                                      for k_ in Recording.made if hasattr(k_, "calls")], dtype=np.int64).reshape(-1, 5))
     finally:
         dist.destroy_process_group()
 
@@ -137,6 +151,36 @@ def test_two_rank_gloo_matches_single_process(tmp_path, case):
         # (the first call has none; afterwards the previous factor's 25 rows)
         np.testing.assert_array_equal(r0["hints"], r1["hints"])
         assert len(r0["hints"]) == int(r0["iteration"]) + 1 and r0["hints"][0] == 0 and (r0["hints"][1:] == 25).all()
+
+
+def test_two_rank_gloo_wide_y_on_the_wide_twin(tmp_path):
+    """Dy = 5 on the CPU twin of the kernel-value cache and mvf_rhs_cached / mvf_apply_cached: the engine's wide branch in its
+    multi-rank order (gram(tiles_only) -> sym_pack -> the asynchronous all-reduce of tri(G) -> rhs_wide -> the scatter of Rd
+    into the all-reduced [R | stats] buffer).  Bit-equal across the ranks, equal to the one-process oracle fit, and every EM
+    step of both ranks went through rhs_wide / apply_wide and never through the three-column apply or rhs."""
+    sys.path.insert(0, HERE)
+    from oracle import sparsevfc_oracle as svo
+    from spateo_amd._synthetic import make_config
+
+    mp.spawn(_worker, args=(2, _free_port(), "wide_twin", str(tmp_path)), nprocs=2, join=True)
+    X, V, _ = make_config("C2", N=601)
+    V = np.column_stack([V, np.sin(X[:, 0] / 70), np.cos(X[:, 1] / 50)])
+    ref = svo.SparseVFC(X, V, X[::30], M=25, lambda_=3.0, lstsq_method="scipy", MaxIter=6, seed=0)
+    r0, r1 = np.load(tmp_path / "rank0.npz"), np.load(tmp_path / "rank1.npz")
+    for k in ("V", "P", "C", "grid_V", "sigma2", "E"):
+        np.testing.assert_array_equal(r0[k], r1[k])
+    steps = int(r0["iteration"]) + 1
+    for r in (r0, r1):
+        assert r["wide_calls"].shape == (1, 5)
+        built, rhs, app, apply_y, gram_rhs = r["wide_calls"][0]
+        assert built == 1 and rhs == steps and app == steps + 1 and apply_y == 0 and gram_rhs == 0
+    assert int(r0["iteration"]) == ref["iteration"] and r0["V"].shape == (601, 5) and r0["C"].shape == (25, 5)
+    scale = np.abs(ref["V"]).max()
+    assert np.abs(r0["V"] - ref["V"]).max() / scale < 1e-8
+    assert np.abs(r0["grid_V"] - ref["grid_V"]).max() / scale < 1e-8
+    np.testing.assert_allclose(r0["P"], ref["P"], rtol=1e-6, atol=1e-12)
+    np.testing.assert_allclose(r0["E"], ref["E_traj"], rtol=1e-8)
+    np.testing.assert_allclose(float(r0["sigma2"]), ref["sigma2"], rtol=1e-8)
 
 
 def test_two_rank_gloo_divergent_solver_branches_raise_instead_of_hanging(tmp_path):

@@ -653,6 +653,41 @@ def test_wide_y_through_the_cached_kernel_values(st, dtype):
     assert _rel(got["V"], narrow["V"]) < 0.1 * tol and np.abs(got["P"] - narrow["P"]).max() < tol
 
 
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_wide_y_beyond_one_column_chunk(st, dtype):
+    """Dy = 130: mvf_rhs_cached / mvf_apply_cached take their columns 128 at a time, so this fit runs the second trip of both
+    loops (the partial-tile buffer with another leading dimension, r read back and added to, sum P r formed by the last launch
+    only).  Against the oracle at the mode's tolerance, against the three-column path at a tenth of it, same iteration count all
+    three ways - the assertions of the Dy = 48 test above."""
+    import spateo_amd.vectorfield as vfm
+
+    rng = np.random.default_rng(13)
+    n, dy = 3000, 130
+    S = rng.uniform(-1, 1, (n, 3)) * 60
+    f = np.column_stack([np.sin(S[:, 0] / (9 + j)) * np.cos(S[:, 1] / (7 + 0.5 * j)) + 0.02 * j * S[:, 2] / 60 for j in range(dy)])
+    f += 0.01 * rng.standard_normal(f.shape)
+    f[rng.choice(n, n // 20, replace=False)] += rng.standard_normal((n // 20, dy))   # 5 % outliers
+    tgt = rng.uniform(-1, 1, (200, 3)) * 55
+    kw = dict(M=100, lambda_=3.0, lstsq_method="scipy", MaxIter=8, seed=0)
+    ref = svo.SparseVFC(S, f, tgt, **kw)
+    got = st.SparseVFC(S, f, tgt, dtype=dtype, device="cuda:0", **kw)
+    old = vfm.SparseVFCEngine.wide_y
+    vfm.SparseVFCEngine.wide_y = False
+    try:
+        narrow = st.SparseVFC(S, f, tgt, dtype=dtype, device="cuda:0", **kw)
+    finally:
+        vfm.SparseVFCEngine.wide_y = old
+    assert got["V"].shape == (n, dy) and got["C"].shape == (100, dy) and got["grid_V"].shape == (200, dy)
+    assert got["iteration"] == ref["iteration"] == narrow["iteration"]
+    tol = TOL[dtype]
+    print(f"wide Dy = {dy} {dtype}: V vs oracle {_rel(got['V'], ref['V']):.2e}, grid {_rel(got['grid_V'], ref['grid_V']):.2e}, "
+          f"sigma2 {abs(got['sigma2'] / ref['sigma2'] - 1):.2e}; vs the three-column path V {_rel(got['V'], narrow['V']):.2e}, "
+          f"P {np.abs(got['P'] - narrow['P']).max():.2e}")
+    assert _rel(got["V"], ref["V"]) < tol and _rel(got["grid_V"], ref["grid_V"]) < tol
+    assert abs(got["sigma2"] / ref["sigma2"] - 1) < tol and np.abs(got["P"] - ref["P"]).max() < 10 * tol
+    assert _rel(got["V"], narrow["V"]) < 0.1 * tol and np.abs(got["P"] - narrow["P"]).max() < tol
+
+
 # ------------------------------------------------------------------------------------------- alignment M-step
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
 def test_update_nonrigid_against_reference_goldens(st, golden_em, dtype):

@@ -889,3 +889,77 @@ def test_restart_loop_refits_per_seed_unless_the_memo_is_opted_into(cpu_kernels,
     calls.clear()
     st.tdr._morphofield_sparsevfc(X, V, reuse_identical_restarts=True, velocity_based_sampling=False, **kw)
     assert calls == [0, 100, 200]  # seeded permutation sampling: the seed reaches the fit, nothing to reuse
+
+
+# ------------------------------------------------------------------------------------------------ the engine's wide branch
+def _drive_engine(kernels, X, Y, M=30, MaxIter=12):
+    """The EM driver as vectorfield.SparseVFC runs it, on the given kernels with the kernel-value cache asked for."""
+    valid, Xv, Yv, idx, ctrl, beta = vfm.sparsevfc_preprocess(X, Y, M=M, seed=0)
+    eng = vfm.SparseVFCEngine(Xv, Yv, ctrl, beta, kernels=kernels, cache_u=True)
+    tecr, E = eng.fit(lambda_=3.0, MaxIter=MaxIter, lstsq_method="scipy")
+    V, P, C = eng.results()
+    return eng, dict(V=V, P=P, C=C, sigma2=eng.sigma2, E=E, iteration=eng.iteration - 1)
+
+
+@pytest.mark.parametrize("dy", [4, 15, 16, 17, 31, 32, 48, 130])
+def test_em_driver_wide_branch_equals_the_three_column_groups(dy):
+    """The host side of the engine's wide branch (padded Yd / Vd / Cd, Cd[:M, :Dy] = cat(C)[:, :Dy], the scatter of Rd into the
+    three-column groups R[g][:, :w], gram(tiles_only)) on the CPU twin of mvf_rhs_cached / mvf_apply_cached: equal to the
+    three-column path to float64 round-off and to the oracle.  Dy = 16, 32, 48: the padding to 16 is exact; 15, 17, 31: one
+    column off it; 16, 31, 32: 3 x the number of groups overshoots the padded width; 130: beyond one 128-column chunk."""
+    from _cpu_kernels import CpuKernelsWide
+
+    rng = np.random.default_rng(dy)
+    X, _ = _data(500)
+    Y = np.column_stack([np.sin(X[:, 0] / 80 + j) + 0.3 * np.cos(X[:, 1] / 60 * (1 + j % 7)) for j in range(dy)])
+    Y += 0.02 * rng.standard_normal(Y.shape)
+    kw, kn = CpuKernelsWide(), CpuKernels()
+    ew, wide = _drive_engine(kw, X, Y)
+    en, narrow = _drive_engine(kn, X, Y)
+    # the engine really took the wide branch, and only it
+    assert ew.wide is True and en.wide is False and ew.cached_u and not en.cached_u
+    assert kw.calls["build_ublk"] == 1 and kw.calls["rhs_wide"] == wide["iteration"] + 1
+    assert kw.calls["apply_wide"] >= wide["iteration"] + 2 and kw.calls["apply"] == 0 and kw.calls["gram_rhs"] == 0
+    dp = -(-dy // 16) * 16
+    assert ew.Yd.shape == (512, dp) and ew.Cd.shape == (128, dp) and ew.Vd.shape == (500, dp) and ew.Rd.shape == (30, dy)
+    assert not ew.Yd[500:].any() and not ew.Yd[:, dy:].any() and not ew.Cd[30:].any() and not ew.Cd[:, dy:].any()
+    assert wide["V"].shape == (500, dy) and wide["C"].shape == (30, dy)
+    assert wide["iteration"] == narrow["iteration"]
+    for key in ("V", "C", "sigma2", "P"):
+        np.testing.assert_allclose(wide[key], narrow[key], rtol=1e-10, err_msg=key)
+    ref = svo.SparseVFC(X, Y, None, M=30, lambda_=3.0, lstsq_method="scipy", MaxIter=12, seed=0)
+    assert wide["iteration"] == ref["iteration"]
+    assert _rel(wide["V"], ref["V"]) < 1e-8
+    np.testing.assert_allclose(wide["E"], ref["E_traj"], rtol=1e-8)
+    np.testing.assert_allclose(wide["sigma2"], ref["sigma2"], rtol=1e-8)
+    np.testing.assert_allclose(wide["P"], ref["P"], rtol=1e-6, atol=1e-12)
+
+
+def test_wide_twin_refuses_what_the_entry_points_refuse():
+    """The CPU twin raises on the shapes mvf_rhs_cached / mvf_apply_cached refuse or would read outside of (mvf.h)."""
+    import torch
+    from _cpu_kernels import CpuKernelsWide
+
+    k = CpuKernelsWide()
+    X, _ = _data(300)
+    x4, c4 = k.to_x4(X), k.to_x4(X[:20])
+    P, R = torch.ones(300, dtype=torch.float64), torch.zeros(20, 5, dtype=torch.float64)
+    Yd, Cd, Vd, r, st_ = k.zeros(512, 16), k.zeros(128, 16), k.zeros(300, 16), k.zeros(300), k.zeros(1)
+    with pytest.raises(RuntimeError, match="needs the kernel-value cache"):
+        k.rhs_wide(P, Yd, 5, 20, R)
+    k.build_ublk(x4, c4, 0.001)
+    k.rhs_wide(P, Yd, 5, 20, R)
+    k.apply_wide(Cd, 5, 20, Yd, P, Vd, r, st_)
+    for bad in (lambda: k.rhs_wide(P, k.zeros(300, 16), 5, 20, R),          # Yd not readable for the padded cell count
+                lambda: k.rhs_wide(P, Yd, 17, 20, k.zeros(20, 17)),         # ldy < dy padded to 16
+                lambda: k.rhs_wide(P, k.zeros(512, 20), 5, 20, R),          # ldy not a multiple of 16
+                lambda: k.rhs_wide(P, Yd, 5, 20, k.zeros(20, 4)),           # ldr < dy
+                lambda: k.rhs_wide(P, Yd, 0, 20, R),
+                lambda: k.apply_wide(k.zeros(20, 16), 5, 20, Yd, P, Vd, r, st_),   # C not readable for the padded control points
+                lambda: k.apply_wide(Cd, 17, 20, k.zeros(512, 32), P, k.zeros(300, 32), r, st_),  # ldc < dy padded to 16
+                lambda: k.apply_wide(Cd, 5, 20, Yd, P, Vd, r, None),        # P given but no stats
+                lambda: k.apply_wide(Cd, 5, 21, Yd, P, Vd, r, st_)):        # not the cached problem
+        with pytest.raises(ValueError):
+            bad()
+    with pytest.raises(RuntimeError, match="cache of these points is not built"):
+        k.gram(k.to_x4(X), P, None, c4, 0.001, k.zeros(20, 20), None, tiles_only=True, cache_only=True)
