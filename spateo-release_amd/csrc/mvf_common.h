@@ -69,6 +69,16 @@ __device__ __forceinline__ T kernel_value(T px, T py, T pz, T cx, T cy, T cz) {
     return exp2_neg(-e);
 }
 
+// Two kernel values at once, bit-identical to kernel_value per component (the same IEEE operations in the same order), issued
+// as packed float32 instructions (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32: two values per VALU issue slot).  What the
+// regenerating float32 kernels (rhs, apply) use for the two or more independent pairs a lane owns.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 kernel_value_pk(f32x2 px, f32x2 py, f32x2 pz, f32x2 cx, f32x2 cy, f32x2 cz) {
+    const f32x2 dx = px - cx, dy = py - cy, dz = pz - cz;
+    const f32x2 e = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
+    return f32x2{exp2_neg(-e.x), exp2_neg(-e.y)};
+}
+
 // The same kernel value in D dimensions (4 <= D <= 8: mvf_ublk_build_d, mvf_eval_d), bit-identical to what conk_kernel
 // computes for a general d (mvf_conk.hip): p and c pre-scaled by sqrt(beta*log2e) in the cell dtype, the squared distance
 // accumulated as e = fma(t_k, t_k, e) in index order from 0.  The 3-D kernel_value above stays the one every x4 kernel uses.

@@ -6,6 +6,7 @@
 // pair and cell) outweighs the LDS broadcast traffic.  Accumulation of V is float64 in every mode: the solve is
 // ill-conditioned, C can carry large cancelling coefficients, and the kernel is a ~1 % slice of an EM step anyway.
 #include "mvf_common.h"
+#include <type_traits>
 
 namespace mvf {
 
@@ -58,9 +59,22 @@ __global__ __launch_bounds__(256) void apply_kernel(const T* __restrict__ x4, in
         for (int j = 0; j < mc_pad; ++j) {
             const V4T cv = sc[j];
             const double4 cc = sC[j];
+            T kv[CPT];
+            if constexpr (std::is_same<T, float>::value && CPT >= 2) {
+                // two of the lane's cells per packed float32 instruction: every value keeps the bits of kernel_value
+#pragma unroll
+                for (int c = 0; c < CPT; c += 2) {
+                    const f32x2 k2 = kernel_value_pk(f32x2{px[c], px[c + 1]}, f32x2{py[c], py[c + 1]}, f32x2{pz[c], pz[c + 1]},
+                                                     f32x2{cv.x, cv.x}, f32x2{cv.y, cv.y}, f32x2{cv.z, cv.z});
+                    kv[c] = k2.x, kv[c + 1] = k2.y;
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < CPT; ++c) kv[c] = kernel_value(px[c], py[c], pz[c], cv.x, cv.y, cv.z);
+            }
 #pragma unroll
             for (int c = 0; c < CPT; ++c) {
-                const double k = (double)kernel_value(px[c], py[c], pz[c], cv.x, cv.y, cv.z);
+                const double k = (double)kv[c];
                 v0[c] = fma(k, cc.x, v0[c]);
                 v1[c] = fma(k, cc.y, v1[c]);
                 v2[c] = fma(k, cc.z, v2[c]);

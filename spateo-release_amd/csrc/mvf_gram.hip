@@ -332,6 +332,8 @@ constexpr int UG = MVF_UG;  // k-steps (of 4 cells) per software-pipeline group
 #endif
 template <typename T> struct CachedPipe { static constexpr int UGT = UG, NBUF = 2; };
 template <> struct CachedPipe<double> { static constexpr int UGT = MVF_DBL_UG, NBUF = MVF_DBL_NBUF; };
+// The cached kernels read P as float64 in both modes: the float32 mode's P is widened once per tile-stage phase (widen_p_kernel) instead
+// of once per wave and k-step of every tile pair - (double)P[i] is the same value either way, so G keeps its bits.
 
 // One wave's share of a tile: NA x NB blocks of 16 x 16 (TRI: only the blocks b >= a of a square arrangement) whose
 // first row block is `rb0` and first column block `cb0` (absolute 16-wide block indices into Ublk); results go to
@@ -342,7 +344,7 @@ template <> struct CachedPipe<double> { static constexpr int UGT = MVF_DBL_UG, N
 // PAIR2 (NA = 4, NB = 4): the row blocks a = 0, 1 belong to one tile (rb0, out) and a = 2, 3 to ANOTHER tile of the same tile
 // column (rb1, out1) - two narrow last-column tiles in one job of full length.
 template <typename T, int NA, int NB, bool TRI, int DW = -1, bool PAIR2 = false>
-__device__ __forceinline__ void cached_block(const T* __restrict__ ublk, const T* __restrict__ P, int64_t n,
+__device__ __forceinline__ void cached_block(const T* __restrict__ ublk, const double* __restrict__ P, int64_t n,
                                              int64_t n_pad, int64_t n0, int64_t n1, int64_t rb0, int64_t cb0,
                                              double* __restrict__ out, int orow0, int ocol0, int64_t rb1 = 0,
                                              double* __restrict__ out1 = nullptr) {
@@ -367,13 +369,33 @@ __device__ __forceinline__ void cached_block(const T* __restrict__ ublk, const T
 #pragma unroll
     for (int b = 0; b < NB; ++b) pb[b] = ublk + ((cb0 + b) * n_pad + n0 + lk) * UB + li;
 
+    // float32: the NA + NB operand streams differ only by a wave-uniform amount, so each gets a buffer resource (base and
+    // size in SGPRs: this slice of its panel, and nothing outside it is ever addressed) and all share ONE 32-bit lane offset;
+    // the advance per superblock is a scalar offset.  Per-lane 64-bit pointers cost ten 64-bit VALU adds per superblock
+    // and 20 VGPRs that this instantiation does not have (it spilled).  The float64 instantiation keeps its pointers.
+    constexpr bool BUF = sizeof(T) == 4;
+    constexpr int BUF_RSRC_WORD3 = 0x00020000;  // raw buffer of 32-bit data (gfx9 family), no swizzle
+    __amdgpu_buffer_rsrc_t ra[NA], rbuf[NB];
+    const int voff = (lk * UB + li) * (int)sizeof(T);
+    if constexpr (BUF) {
+        const int nbytes = (int)((n1 - n0) * UB * (int64_t)sizeof(T));  // (< 2^31: checked by the host)
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+            ra[a] = __builtin_amdgcn_make_buffer_rsrc(
+                (void*)(ublk + ((PAIR2 ? (a < 2 ? rb0 + a : rb1 + (a - 2)) : rb0 + rblk(a)) * n_pad + n0) * UB), (short)0, nbytes,
+                BUF_RSRC_WORD3);
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            rbuf[b] = __builtin_amdgcn_make_buffer_rsrc((void*)(ublk + ((cb0 + b) * n_pad + n0) * UB), (short)0, nbytes, BUF_RSRC_WORD3);
+    }
     f64x4 acc[NA][NB];
 #pragma unroll
     for (int a = 0; a < NA; ++a)
 #pragma unroll
         for (int b = 0; b < NB; ++b) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
 
-    T ua[NBUF][UGT][NA], ub[NBUF][UGT][NB], pp[NBUF][UGT];
+    T ua[NBUF][UGT][NA], ub[NBUF][UGT][NB];
+    double pp[NBUF][UGT];
     const int ngroups = (int)((n1 - n0) / (4 * UGT));  // slices are multiples of 256 cells
 
     // Address arithmetic is VALU work too (64-bit adds) and VALU time is additive to f64 MFMA time: the operand
@@ -381,9 +403,9 @@ __device__ __forceinline__ void cached_block(const T* __restrict__ ublk, const T
     // uses a compile-time immediate offset.  P is read branch-free: cached rows of padded cells are zero, so any finite
     // P does; only the remainder loop clamps its index.
     constexpr int SUPER = 4096 / (UGT * 4 * UB * (int)sizeof(T));  // groups per 4 KB of one pointer's stream
-    const T* pP = P + n0 + lk;
+    const double* pP = P + n0 + lk;
     const int pmax = (int)min((int64_t)0x3fffffff, n - 1 - n0 - lk);  // last valid index from pP (may be < 0: P[n-1])
-    auto load_group = [&](int64_t gbase, int s, bool in_tail, T(&A)[UGT][NA], T(&B)[UGT][NB], T(&Pq)[UGT]) {
+    auto load_group = [&](int64_t gbase, int s, bool in_tail, T(&A)[UGT][NA], T(&B)[UGT][NB], double(&Pq)[UGT]) {
         // group gbase + s; `s` is a compile-time constant after unrolling, gbase advances once per superblock
 #pragma unroll
         for (int q = 0; q < UGT; ++q) {
@@ -394,24 +416,35 @@ __device__ __forceinline__ void cached_block(const T* __restrict__ ublk, const T
 #pragma unroll
             for (int b = 0; b < NB; ++b) B[q][b] = (T)(0.25 + lane * 1e-3);
 #else
+            if constexpr (BUF) {
+                const int soff = __builtin_amdgcn_readfirstlane((int)(gbase * UGT) * (4 * UB) * (int)sizeof(T));
+                const int imm = (s * UGT + q) * (4 * UB) * (int)sizeof(T);
+#pragma unroll
+                for (int a = 0; a < NA; ++a)
+                    A[q][a] = __builtin_bit_cast(T, (int)__builtin_amdgcn_raw_buffer_load_b32(ra[a], voff + imm, soff, 0));
+#pragma unroll
+                for (int b = 0; b < NB; ++b)
+                    B[q][b] = __builtin_bit_cast(T, (int)__builtin_amdgcn_raw_buffer_load_b32(rbuf[b], voff + imm, soff, 0));
+            } else {
 #pragma unroll
             for (int a = 0; a < NA; ++a) A[q][a] = pa[a][off];
 #pragma unroll
             for (int b = 0; b < NB; ++b) B[q][b] = pb[b][off];
+            }
 #endif
 #if defined(MVF_PROBE_NO_LOAD) || defined(MVF_PROBE_NO_P)
-            Pq[q] = T(1);
+            Pq[q] = 1.0;
 #else
             const int64_t poff = (gbase * UGT) * 4 + (s * UGT + q) * 4;
             Pq[q] = in_tail ? pP[min((int)poff, pmax)] : pP[poff];
 #endif
         }
     };
-    auto compute_group = [&](const T(&A)[UGT][NA], const T(&B)[UGT][NB], const T(&Pq)[UGT]) {
+    auto compute_group = [&](const T(&A)[UGT][NA], const T(&B)[UGT][NB], const double(&Pq)[UGT]) {
 #pragma unroll
         for (int q = 0; q < UGT; ++q) {
             double fa[NA], fb[NB];
-            const double pd = (double)Pq[q];
+            const double pd = Pq[q];
 #pragma unroll
             for (int a = 0; a < NA; ++a) {
 #ifdef MVF_PROBE_NO_P
@@ -484,7 +517,7 @@ __device__ __forceinline__ void cached_block(const T* __restrict__ ublk, const T
 }
 
 template <typename T>
-__global__ __launch_bounds__(256, MVF_CACHED_WPS) void gram_cached_kernel(const T* __restrict__ ublk, const T* __restrict__ P,
+__global__ __launch_bounds__(256, MVF_CACHED_WPS) void gram_cached_kernel(const T* __restrict__ ublk, const double* __restrict__ P,
                                                              int64_t n, int64_t n_pad, int64_t m, int nt, int npairs,
                                                              int64_t slice_len, int64_t slice0,
                                                              double* __restrict__ partial, int njobs, int edge2) {
@@ -570,6 +603,14 @@ __global__ __launch_bounds__(256, MVF_CACHED_WPS) void gram_cached_kernel(const 
     }
 }
 
+// Pd[i - c0] = (double)P[i] for the cells c0 <= i < c1 of a phase (multiples of 256), 0 for the padded cells i >= n (whose
+// cached rows are zero as well)
+__global__ __launch_bounds__(256) void widen_p_kernel(const float* __restrict__ P, int64_t n, int64_t c0, int64_t c1,
+                                                      double* __restrict__ Pd) {
+    const int64_t i = c0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < c1) Pd[i - c0] = i < n ? (double)P[i] : 0.0;
+}
+
 // ----------------------------------------------------------------------------------------------------------------
 // rhs:  R[j, :] = sum_n K(x_n, c_j) P_n y_n   (VALU kernel; a lane owns RHS_CPT control points, cells broadcast
 // from LDS; float64 accumulation)
@@ -580,7 +621,9 @@ __global__ __launch_bounds__(256) void rhs_kernel(const T* __restrict__ x4, cons
                                                   int64_t m, T s, int64_t slice_len, double* __restrict__ rpart) {
     using V4T = typename Vec4<T>::type;
     __shared__ V4T sx[GCHUNK];
-    __shared__ V4T sw[GCHUNK];
+    // the weights y * p, rounded to T as the sum takes them and staged ALREADY widened: the lane that loads a cell converts
+    // its three weights once instead of every lane converting them again for every cell (12 of 20 v_cvt_f64_f32 per 8 pairs)
+    __shared__ double4 sw[GCHUNK];
     const int64_t slice = blockIdx.y;
     const int64_t n0 = slice * slice_len, n1 = min(n, n0 + slice_len);
     T cx[RHS_CPT], cy[RHS_CPT], cz[RHS_CPT];
@@ -604,10 +647,10 @@ __global__ __launch_bounds__(256) void rhs_kernel(const T* __restrict__ x4, cons
             const V4T yv = reinterpret_cast<const V4T*>(y4)[i];
             const T p = P[i];
             sx[threadIdx.x] = V4T{xv.x * s, xv.y * s, xv.z * s, 0};
-            sw[threadIdx.x] = V4T{yv.x * p, yv.y * p, yv.z * p, 0};
+            sw[threadIdx.x] = double4{(double)(T)(yv.x * p), (double)(T)(yv.y * p), (double)(T)(yv.z * p), 0.0};
         } else {
             sx[threadIdx.x] = V4T{0, 0, 0, 0};
-            sw[threadIdx.x] = V4T{0, 0, 0, 0};  // zero weight
+            sw[threadIdx.x] = double4{0.0, 0.0, 0.0, 0.0};  // zero weight
         }
         __syncthreads();
         // float64 accumulation on purpose: rounding noise in R is NOT of the form U^T P (dY), so the ill-conditioned
@@ -615,13 +658,24 @@ __global__ __launch_bounds__(256) void rhs_kernel(const T* __restrict__ x4, cons
 #pragma unroll 4
         for (int q = 0; q < GCHUNK; ++q) {
             const V4T xv = sx[q];
-            const V4T wv = sw[q];
+            const double4 wv = sw[q];
+            T kv[RHS_CPT];
+            if constexpr (std::is_same<T, float>::value) {
+                // the lane's two pairs of this cell in packed float32 arithmetic: every value keeps the bits of kernel_value
+                static_assert(RHS_CPT == 2, "one packed pair per cell");
+                const f32x2 k2 = kernel_value_pk(f32x2{xv.x, xv.x}, f32x2{xv.y, xv.y}, f32x2{xv.z, xv.z},
+                                                 f32x2{cx[0], cx[1]}, f32x2{cy[0], cy[1]}, f32x2{cz[0], cz[1]});
+                kv[0] = k2.x, kv[1] = k2.y;
+            } else {
+#pragma unroll
+                for (int c = 0; c < RHS_CPT; ++c) kv[c] = kernel_value(xv.x, xv.y, xv.z, cx[c], cy[c], cz[c]);
+            }
 #pragma unroll
             for (int c = 0; c < RHS_CPT; ++c) {
-                const double k = (double)kernel_value(xv.x, xv.y, xv.z, cx[c], cy[c], cz[c]);
-                r0[c] = fma(k, (double)wv.x, r0[c]);
-                r1[c] = fma(k, (double)wv.y, r1[c]);
-                r2[c] = fma(k, (double)wv.z, r2[c]);
+                const double k = (double)kv[c];
+                r0[c] = fma(k, wv.x, r0[c]);
+                r1[c] = fma(k, wv.y, r1[c]);
+                r2[c] = fma(k, wv.z, r2[c]);
             }
         }
     }
@@ -695,10 +749,19 @@ __global__ __launch_bounds__(256) void rhs_reduce_kernel(const double* __restric
 
 using namespace mvf;
 
+static inline int64_t ublk_npad(int64_t n) { return cdiv(n, GCHUNK) * GCHUNK; }
+static inline int64_t ublk_mpad(int64_t m) { return cdiv(m, GT) * GT; }
+// The widened P of the float32 cached tile stage, behind the partial tiles and the rhs partials: the cells of ONE phase (like
+// the partial tiles it is rewritten by every phase, so the workspace keeps its bound whatever the cell count).
+static inline int64_t phase_cells(const GramPlan& p, int64_t n) { return std::min(ublk_npad(n), p.phase_slices * p.slice_len); }
+static inline size_t widened_p_bytes(const GramPlan& p, int64_t n, mvf_dtype dtype) {
+    return dtype == MVF_F32 ? align_up(sizeof(double) * (size_t)phase_cells(p, n), 256) : 0;
+}
+
 extern "C" size_t mvf_gram_workspace_bytes(int64_t n, int64_t m, mvf_dtype dtype) {
     if (n <= 0 || m <= 0) return 0;
     const GramPlan p = make_plan(n, m, dtype);
-    return align_up(p.gram_bytes, 256) + align_up(p.rhs_bytes, 256);
+    return align_up(p.gram_bytes, 256) + align_up(p.rhs_bytes, 256) + widened_p_bytes(p, n, dtype);
 }
 
 extern "C" int mvf_gram_stages(int stages, const void* x4, const void* P, const void* y4, int64_t n,
@@ -770,9 +833,6 @@ extern "C" int mvf_gram_stages(int stages, const void* x4, const void* P, const 
     return 0;
 }
 
-static inline int64_t ublk_npad(int64_t n) { return cdiv(n, GCHUNK) * GCHUNK; }
-static inline int64_t ublk_mpad(int64_t m) { return cdiv(m, GT) * GT; }
-
 extern "C" size_t mvf_ublk_bytes(int64_t n, int64_t m, mvf_dtype dtype) {
     if (n <= 0 || m <= 0) return 0;
     return (size_t)ublk_npad(n) * (size_t)ublk_mpad(m) * (dtype == MVF_F64 ? sizeof(double) : sizeof(float));
@@ -814,21 +874,36 @@ extern "C" int mvf_gram_cached(int stages, const void* ublk, const void* x4, con
     hipStream_t st = (hipStream_t)stream;
     if (stages & MVF_GRAM_STAGE_TILES) {
         const GramPlan p = make_plan(n, m, dtype);
-        const size_t need = align_up(p.gram_bytes, 256) + align_up(p.rhs_bytes, 256);
+        const size_t pd_off = align_up(p.gram_bytes, 256) + align_up(p.rhs_bytes, 256);
+        const size_t need = pd_off + widened_p_bytes(p, n, dtype);
         MVF_REQUIRE(workspace && workspace_bytes >= need, "mvf_gram_cached: workspace too small (%zu < %zu)",
                     workspace_bytes, need);
+        const int64_t n_pad = ublk_npad(n);
+        double* const pd = (double*)((char*)workspace + pd_off);
         MVF_REQUIRE((int64_t)p.phase_slices * p.npairs < (1LL << 31), "mvf_gram_cached: too many jobs");
+        // (the float32 kernel addresses a slice of a panel through a buffer resource with 32-bit byte offsets)
+        MVF_REQUIRE(dtype != MVF_F32 || p.slice_len * UB * (int64_t)sizeof(float) < (1LL << 31),
+                    "mvf_gram_cached: slice too long");
         MVF_REQUIRE(p.nphases == 1 || G, "mvf_gram_cached: null G (the tile stage reduces all but its last phase)");
         for (int64_t ph = 0; ph < p.nphases; ++ph) {
             const int64_t s0 = ph * p.phase_slices, ns = std::min(p.phase_slices, p.nslices - s0);
             const unsigned njobs = (unsigned)(ns * p.npairs);
-            if (dtype == MVF_F32)
+            if (dtype == MVF_F32) {
+                // this phase's cells [c0, c1) of P, widened; the tile kernel indexes P by absolute cell
+                const int64_t c0 = s0 * p.slice_len, c1 = std::min(n_pad, c0 + ns * p.slice_len);
+                hipLaunchKernelGGL(widen_p_kernel, dim3((unsigned)((c1 - c0) / 256)), dim3(256), 0, st, (const float*)P, n,
+                                   c0, c1, pd);
+                // The kernel indexes P by ABSOLUTE cell, so it gets the buffer's address biased by - c0: for every phase but
+                // the first that address lies BELOW the workspace.  Valid only because the kernel never indexes it outside
+                // [c0, c1): a job's cells are [n0, n1) with c0 <= n0 and n1 <= c1, and the remainder loop's clamp reads cell
+                // n - 1 at the lowest, which is >= c0 (a phase starts at a slice that holds live cells: c0 < n).
+                const double* Pd = (const double*)((uintptr_t)pd - (uintptr_t)c0 * sizeof(double));
                 hipLaunchKernelGGL(gram_cached_kernel<float>, dim3(njobs), dim3(256), 0, st, (const float*)ublk,
-                                   (const float*)P, n, ublk_npad(n), m, p.nt, p.npairs, p.slice_len, s0,
+                                   Pd, n, n_pad, m, p.nt, p.npairs, p.slice_len, s0,
                                    (double*)workspace, p.npairs, 0);
-            else
+            } else
                 hipLaunchKernelGGL(gram_cached_kernel<double>, dim3((unsigned)(ns * p.njobs)), dim3(256), 0, st,
-                                   (const double*)ublk, (const double*)P, n, ublk_npad(n), m, p.nt, p.npairs, p.slice_len, s0,
+                                   (const double*)ublk, (const double*)P, n, n_pad, m, p.nt, p.npairs, p.slice_len, s0,
                                    (double*)workspace, p.njobs, p.edge2);
             if (ph + 1 < p.nphases)
                 hipLaunchKernelGGL(gram_reduce_kernel, dim3(GT * GT / 256, (unsigned)p.npairs), dim3(256), 0, st,
