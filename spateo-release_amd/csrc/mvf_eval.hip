@@ -365,6 +365,8 @@ extern "C" int mvf_integrate(const void* x4, int64_t n, const void* ctrl4, int64
     hipStream_t st = (hipStream_t)stream;
     const double s = std::sqrt(beta * LOG2E);
     const size_t per = (dtype == MVF_F32 ? 16 : 32) + 32;  // bytes of LDS per staged control point
+    // cap = 3072 (float32) / 2304 (float64) control points: above it the kernel re-stages chunk by chunk inside every field
+    // evaluation.  tests/_cell_cases.py RK4_CAP states the same expression and the RK4 edge tests pin m = cap - 1, cap, cap + 1.
     const int cap = (int)((144 * 1024) / per);               // leave headroom below the 160 KiB of a CU
     const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(m, cap));
     const size_t lds = (size_t)chunk * per;

@@ -271,7 +271,8 @@ class CpuKernels:
         X, ctrl, Cn = _np(x4)[:, :3].astype(np.float64), _np(ctrl4)[:, :3], _np(C)
 
         def f(q):
-            v = svo.con_K(q, ctrl, beta).reshape(len(q), len(ctrl)) @ Cn
+            # (no control points: the field is its affine part alone, as the device kernel's empty sum gives it)
+            v = svo.con_K(q, ctrl, beta).reshape(len(q), len(ctrl)) @ Cn if len(ctrl) else np.zeros((len(q), 3))
             if affine is not None:
                 alpha, _, A, b = affine
                 v = alpha * v + q @ np.asarray(A).T + np.asarray(b)[None, :]
@@ -293,8 +294,17 @@ class CpuKernels:
         vfd = {"X_ctrl": ctrl, "C": Cn, "beta": beta}
         n = len(X)
         out = {}
-        v = svo.con_K(X, ctrl, beta).reshape(n, len(ctrl)) @ Cn
-        J = dgo.Jacobian_rkhs_gaussian(X, vfd, vectorize=True)
+        if len(ctrl) >= 2 and n >= 2:
+            v = svo.con_K(X, ctrl, beta).reshape(n, len(ctrl)) @ Cn
+            J = dgo.Jacobian_rkhs_gaussian(X, vfd, vectorize=True)
+        else:
+            # one query, one control point or none: the oracle squeezes such shapes away (and cdist refuses an empty list);
+            # the same sums written out, an empty one being 0
+            ctrl, Cn = ctrl.reshape(-1, 3), Cn.reshape(-1, 3)
+            D = X[:, None, :] - ctrl[None, :, :]
+            K = np.exp(-beta * np.sum(D * D, axis=2))
+            v = K @ Cn
+            J = -2 * beta * np.einsum("nm,mf,nmi->fin", K, Cn, D)
         if affine is not None:
             alpha, jmul, A, b = affine
             v = np.asarray(alpha, dtype=float).reshape(1, -1) * v + X @ np.asarray(A).T + np.asarray(b)[None, :]  # alpha: scalar or (3,)
