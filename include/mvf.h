@@ -455,6 +455,60 @@ int mvf_integrate_rk45(const void* x4, int64_t n, const void* ctrl4, int64_t m, 
                        double max_step, int max_steps, int sampling, int n_out, double* t, double* traj, int* stats,
                        mvf_dtype dtype, void* stream);
 
+/* ---- alignment: the assignment step, fused (no NA x NB matrix) ----------------------------------------------------------
+ * Replaces: `Morpho_pairwise._update_assignment_P` (spateo/alignment/methods/morpho_class.py:1071-1200), i.e. `calc_distance`
+ * (spateo/alignment/methods/utils.py:647-788, 866-941), `calc_probability` (:944-985) and `get_P_core` (:993-1096) on the
+ * dense path, for the metrics and probability types below.  Every metric is d_ij = a_i + b_j - s <X'_i, Y'_j>, optionally
+ * clamped at 0 / square-rooted; mvf_assign_prepare builds the operands of one side of one layer, mvf_assign runs the two
+ * tile passes (layer products as f64 MFMA, exponent arithmetic in float64 whatever the dtype; `dtype` is the storage of
+ * the coordinates and of X' / Y').  Partial sums go through the workspace and are added in a fixed order: two calls give
+ * bit-identical results. */
+typedef enum {
+    MVF_ASSIGN_EUC = 0,       /* "euc" / "euclidean": the SQUARED distance, clamped at 0 (the reference's naming) */
+    MVF_ASSIGN_SQRT_EUC = 1,  /* "square_euc" / "square_euclidean": its square root                               */
+    MVF_ASSIGN_KL = 2,        /* "kl": rows + 0.01, normalised, log(. + 1e-8)                                     */
+    MVF_ASSIGN_SYM_KL = 3,    /* "sym_kl": (kl(x, y) + kl(y, x)) / 2 as one product over 2 g features             */
+    MVF_ASSIGN_COS = 4        /* "cos" / "cosine": 1/2 - 1/2 cosine similarity, norms floored at 1e-8             */
+} mvf_assign_metric;
+typedef enum { MVF_ASSIGN_GAUSS = 0, MVF_ASSIGN_COS_PROB = 1, MVF_ASSIGN_PROB = 2 } mvf_assign_prob;
+#define MVF_ASSIGN_MAX_LAYERS 4
+/* one expression / representation layer (a HOST struct of DEVICE pointers): Xp (na x ld) and Yp (nb x ld) in `dtype`, a (na)
+ * and b (nb) float64, all from mvf_assign_prepare; prob: exp(-d / (2 param)) | 1 - d | d  (calc_probability, :974-983) */
+typedef struct {
+    const void* Xp;
+    const void* Yp;
+    const double* a;
+    const double* b;
+    int64_t ld;
+    int metric;
+    int prob;
+    double param;
+} mvf_assign_layer;
+/* features per prepared row: g (2 g for sym_kl) rounded up to a multiple of 16; 0 for g <= 0 or an unknown metric */
+int64_t mvf_assign_padded_features(int64_t g, int metric);
+/* Replaces the per-cell part of `_kl_distance_backend` / `_cosine_distance_backend` / `_euc_distance_backend`
+ * (utils.py:683-695, 736-739, 780).  layer: n x g float64 (device); side 0 = the A cells (rows of P), 1 = the B cells.
+ * Out: Lp (n x ld, dtype; ld = mvf_assign_padded_features(g, metric), the tail of each row zero) and ab (n float64): the
+ * row constant a_i (side 0) or b_j (side 1), formed from the operands as stored.  n == 0 launches nothing. */
+int mvf_assign_prepare(const double* layer, int64_t n, int64_t g, int metric, int side, void* Lp, int64_t ld, double* ab,
+                       mvf_dtype dtype, void* stream);
+size_t mvf_assign_workspace_bytes(int64_t na, int64_t nb);
+/* xa4 (na x 4) = XAHat, xb4 (nb x 4) = coordsB in the x4 layout (dtype); layers: 1 .. MVF_ASSIGN_MAX_LAYERS host structs;
+ * model_mul (na float64) = alpha exp(-SigmaDiag / sigma2) (morpho_class.py:1087); spatial_outlier as get_P_core forms it
+ * (:1051-1053).  Outputs (device float64): K_NA, K_NA_spatial, K_NA_sigma2 (na), K_NB (nb), PXB = P @ coordsB (na x 3, the
+ * unused columns 0), scalars[0] = sum_ij P_sigma2 d_ij (`sigma2_related` before its division, :1075).  Sp = sum K_NB.
+ * na == 0 or nb == 0 returns 0 without touching the device. */
+int mvf_assign(const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers, int nlayers,
+               const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier, double* K_NA,
+               double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars, void* workspace,
+               size_t workspace_bytes, mvf_dtype dtype, void* stream);
+/* The same, and the dense P (na x nb float64, row-major) as well: `self.P` of the reference (:1167), for label transfer and
+ * debugging - the one variant that writes na nb values. */
+int mvf_assign_dense(const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers, int nlayers,
+                     const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier, double* K_NA,
+                     double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars, double* P,
+                     void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

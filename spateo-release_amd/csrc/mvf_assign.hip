@@ -1,0 +1,525 @@
+// The assignment step of Spateo's alignment, fused: every weight the other updates consume (K_NA, K_NB, K_NA_spatial,
+// K_NA_sigma2, sum P_sigma2 d, P @ coordsB) without the NA x NB matrix P.
+//
+// Reference: `Morpho_pairwise._update_assignment_P` (spateo/alignment/methods/morpho_class.py:1071-1200) = `calc_distance`
+// (methods/utils.py:647-788, 866-941) + `get_P_core` (:993-1096), which materialise P and three more NA x NB matrices.
+//
+// Every supported layer metric is d_ij = a_i + b_j - s <X'_i, Y'_j> (optionally clamped at 0 / square-rooted):
+//   euc     X' = x, Y' = y, a = |x|^2, b = |y|^2, s = 2, clamped (the reference's "euc" IS the squared distance)
+//   kl      X' = p, Y' = log(q + 1e-8), a = sum p log(p + 1e-8), b = 0, s = 1        (p, q: x + 0.01, row-normalised)
+//   sym_kl  X' = [p, log p'], Y' = [log q', q], a = sum p log p' / 2, b = sum q log q' / 2, s = 1/2   (2 G features)
+//   cos     X' = x / max(|x|, 1e-8), Y' likewise, a = 1/2, b = 0, s = 1/2
+// mvf_assign_prepare builds X' / Y' (cell dtype, rows zero-padded to a multiple of 16 features) and a / b (float64) in O(N G);
+// the pairwise part is one tile routine: the layer dot products as v_mfma_f64_16x16x4_f64 (operands widened from the cell
+// dtype, float64 accumulation), the spatial distance from the coordinates and all exponent arithmetic in float64 on VALU.
+//
+// Two passes over the tiles, flash-attention style (the column normalisers must be known before a row sum can be formed):
+//   pass 1  per B column j, over the A rows i:  S0 = sum e1, S1 = sum e1 m_i, S2 = sum e2 m_i, S3 = sum e2 m_i q_ij
+//           (e1 = exp(-d sigma2_variance / 2 sigma2), e2 = exp(-d / 2 sigma2), q = product of the layer probabilities)
+//   factors in_j = 1 - o / (o + S0), c1 = 1 / (o + S1), c2 = in_j / (S2 + 1e-8), c3 = in_j / (S3 + 1e-8), K_NB_j = c3 S3
+//   pass 2  per A row i, over the B columns j:  K_NA_spatial = m_i sum e1 c1, K_NA_sigma2 = m_i sum e2 c2,
+//           K_NA = m_i sum e2 q c3, PXB = m_i sum e2 q c3 y_j, and sum_ij m_i e2 c2 d
+// No max-subtraction before exp, as in the reference: a column whose terms all underflow has S = 0, in_j = 0 and gives
+// exactly 0 everywhere.  A workgroup is 4 waves on a 64 x 64 tile (each wave 32 x 32: 2 x 2 MFMA blocks); the rows (pass 1) /
+// columns (pass 2) are split over workgroups, every split writes its partial sums to the workspace and a small kernel adds
+// them in split order: no floating-point atomics, two calls give the same bits.
+#include "mvf_common.h"
+
+namespace mvf {
+namespace {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int AT = 64;            // tile edge (rows of A and columns of B per workgroup step)
+constexpr int AKS = 16;           // features per k-step: 4 lane groups x 4 consecutive features (one 16 / 32-byte load)
+constexpr int MAX_LAYERS = 4;
+constexpr int MAX_SPLITS = 64;
+constexpr int TARGET_WGS = 1024;  // workgroups a pass aims for (4 per CU)
+constexpr double ASSIGN_EPS = 1e-8;
+
+struct DevLayer {
+    const void* X;
+    const void* Y;
+    const double* a;
+    const double* b;
+    int64_t ld;
+    double s;       // d = a_i + b_j - s dot
+    double nparam;  // gauss: -1 / (2 p)
+    int post;       // 0 none, 1 clamp at 0, 2 clamp at 0 and square root
+    int prob;       // mvf_assign_prob
+};
+
+struct DevLayers {
+    DevLayer l[MAX_LAYERS];
+    int n;
+};
+
+struct Plan {
+    int64_t rtiles, ctiles, na_pad, nb_pad, rsplit, csplit;
+    size_t off_part1, off_fac, off_part2, off_rows, total;  // in bytes
+};
+
+Plan make_plan(int64_t na, int64_t nb) {
+    Plan p;
+    p.rtiles = cdiv(na, AT), p.ctiles = cdiv(nb, AT);
+    p.na_pad = p.rtiles * AT, p.nb_pad = p.ctiles * AT;
+    p.rsplit = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(p.rtiles, MAX_SPLITS), cdiv(TARGET_WGS, p.ctiles)));
+    p.csplit = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(p.ctiles, MAX_SPLITS), cdiv(TARGET_WGS, p.rtiles)));
+    size_t o = 0;
+    p.off_part1 = o, o += align_up((size_t)p.rsplit * 4 * p.nb_pad * sizeof(double), 256);
+    p.off_fac = o, o += align_up((size_t)p.nb_pad * 4 * sizeof(double), 256);
+    p.off_part2 = o, o += align_up((size_t)p.csplit * p.na_pad * 8 * sizeof(double), 256);
+    p.off_rows = o, o += align_up((size_t)p.na_pad * sizeof(double), 256);
+    p.total = o;
+    return p;
+}
+
+template <typename T>
+__device__ __forceinline__ void load4(const T* p, double (&v)[4]) {
+    const typename Vec4<T>::type u = *reinterpret_cast<const typename Vec4<T>::type*>(p);
+    v[0] = (double)u.x, v[1] = (double)u.y, v[2] = (double)u.z, v[3] = (double)u.w;
+}
+
+// q[a][b][r] = product over the layers of the probability of d(row i0 + 16 a + lk + 4 r, column j0 + 16 b + li), for the
+// wave's 32 x 32 block at (i0, j0).  Rows / columns beyond the arrays are clamped to the last one (finite values, masked by
+// the callers).
+template <typename T>
+__device__ __forceinline__ void layer_product(const DevLayers& L, int64_t i0, int64_t j0, int64_t na, int64_t nb, int li, int lk,
+                                              f64x4 (&q)[2][2]) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) q[a][b] = f64x4{1.0, 1.0, 1.0, 1.0};
+    for (int l = 0; l < L.n; ++l) {
+        const DevLayer& ly = L.l[l];
+        const int64_t ld = ly.ld;
+        // A operand of the MFMA: row li of block a, features 4 lk .. 4 lk + 3 of the k-step; B operand: column li of block b
+        const T* pa[2];
+        const T* pb[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            pa[h] = (const T*)ly.X + std::min<int64_t>(i0 + 16 * h + li, na - 1) * ld + 4 * lk;
+            pb[h] = (const T*)ly.Y + std::min<int64_t>(j0 + 16 * h + li, nb - 1) * ld + 4 * lk;
+        }
+        f64x4 acc[2][2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
+        double na_[2][4], nb_[2][4];  // the next k-step's operands fly during this step's MFMAs
+#pragma unroll
+        for (int h = 0; h < 2; ++h) load4(pa[h], na_[h]), load4(pb[h], nb_[h]);
+        for (int64_t k0 = 0; k0 < ld; k0 += AKS) {
+            double fa[2][4], fb[2][4];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) fa[h][t] = na_[h][t], fb[h][t] = nb_[h][t];
+            if (k0 + AKS < ld) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) load4(pa[h] + k0 + AKS, na_[h]), load4(pb[h] + k0 + AKS, nb_[h]);
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+                        acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a][t], fb[b][t], acc[a][b], 0, 0, 0);
+        }
+        // D[row lk + 4 r of block a][column li of block b] sits in acc[a][b][r] of lane (li, lk)
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double ai = ly.a[std::min<int64_t>(i0 + 16 * a + lk + 4 * r, na - 1)];
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const double bj = ly.b[std::min<int64_t>(j0 + 16 * b + li, nb - 1)];
+                    double d = (ai + bj) - ly.s * acc[a][b][r];
+                    if (ly.post >= 1) d = fmax(d, 0.0);
+                    if (ly.post == 2) d = sqrt(d);
+                    double p;
+                    if (ly.prob == MVF_ASSIGN_GAUSS) p = exp(d * ly.nparam);
+                    else if (ly.prob == MVF_ASSIGN_COS_PROB) p = 1.0 - d;
+                    else p = d;
+                    q[a][b][r] *= p;
+                }
+            }
+    }
+}
+
+struct Point {
+    double x, y, z, n2;
+};
+
+template <typename T>
+__device__ __forceinline__ Point load_point(const T* x4, int64_t i) {
+    double v[4];
+    load4(x4 + 4 * i, v);
+    Point p;
+    p.x = v[0], p.y = v[1], p.z = v[2];
+    p.n2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+    return p;
+}
+
+// the reference's squared distance: |x|^2 + |y|^2 - 2 x.y, clamped at 0 (methods/utils.py:780-783)
+__device__ __forceinline__ double sq_dist(const Point& p, const Point& c) {
+    const double dot = (p.x * c.x + p.y * c.y) + p.z * c.z;
+    return fmax((p.n2 + c.n2) - 2.0 * dot, 0.0);
+}
+
+// ---- pass 1: column sums.  grid (column tiles, row splits); part1[split][S0..S3][nb_pad]
+template <typename T>
+__global__ __launch_bounds__(256) void assign_pass1_kernel(const T* __restrict__ xa4, int64_t na, const T* __restrict__ xb4,
+                                                           int64_t nb, DevLayers L, const double* __restrict__ mm, double h1,
+                                                           double h2, int64_t rtiles, int64_t nb_pad,
+                                                           double* __restrict__ part1) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, lk = lane >> 4, wi = wave >> 1, wj = wave & 1;
+    const int64_t j0 = (int64_t)blockIdx.x * AT + 32 * wj;
+    const int64_t t_lo = rtiles * blockIdx.y / gridDim.y, t_hi = rtiles * (blockIdx.y + 1) / gridDim.y;
+    Point cb[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) cb[b] = load_point(xb4, std::min<int64_t>(j0 + 16 * b + li, nb - 1));
+    double s[4][2] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+    for (int64_t t = t_lo; t < t_hi; ++t) {
+        const int64_t i0 = t * AT + 32 * wi;
+        f64x4 q[2][2];
+        layer_product<T>(L, i0, j0, na, nb, li, lk, q);
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t i = i0 + 16 * a + lk + 4 * r;
+                const bool live = i < na;
+                const Point pa = load_point(xa4, live ? i : na - 1);
+                const double m = live ? mm[i] : 0.0, one = live ? 1.0 : 0.0;
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const double d = sq_dist(pa, cb[b]);
+                    const double e1 = exp(d * h1), e2m = exp(d * h2) * m;
+                    s[0][b] += e1 * one;
+                    s[1][b] += e1 * m;
+                    s[2][b] += e2m;
+                    s[3][b] += e2m * q[a][b][r];
+                }
+            }
+    }
+    // the 8 (row half, lane group) partials of every column, added in a fixed order
+    __shared__ double red[4][8][AT];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) red[k][wi * 4 + lk][32 * wj + 16 * b + li] = s[k][b];
+    __syncthreads();
+    const int k = threadIdx.x >> 6, c = threadIdx.x & 63;
+    double tot = 0.0;
+#pragma unroll
+    for (int g = 0; g < 8; ++g) tot += red[k][g][c];
+    part1[((int64_t)blockIdx.y * 4 + k) * nb_pad + (int64_t)blockIdx.x * AT + c] = tot;
+}
+
+// ---- column factors: fac[j] = {c1, c2, c3, 0}, K_NB[j] = c3 S3 (the splits added in order)
+__global__ __launch_bounds__(256) void assign_factors_kernel(const double* __restrict__ part1, int64_t rsplit, int64_t nb,
+                                                             int64_t nb_pad, double outlier, double* __restrict__ fac,
+                                                             double* __restrict__ K_NB) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= nb_pad) return;
+    double S[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t sp = 0; sp < rsplit; ++sp)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) S[k] += part1[(sp * 4 + k) * nb_pad + j];
+    double c1 = 0.0, c2 = 0.0, c3 = 0.0;
+    if (j < nb) {
+        const double inl = 1.0 - outlier / (outlier + S[0]);
+        c1 = 1.0 / (outlier + S[1]);
+        c2 = inl / (S[2] + ASSIGN_EPS);
+        c3 = inl / (S[3] + ASSIGN_EPS);
+        K_NB[j] = c3 * S[3];
+    }
+    fac[4 * j + 0] = c1, fac[4 * j + 1] = c2, fac[4 * j + 2] = c3, fac[4 * j + 3] = 0.0;  // columns >= nb: zero weight
+}
+
+// ---- pass 2: row sums.  grid (row tiles, column splits); part2[split][na_pad][8] = {sum e1 c1, sum e2 c2, sum e2 q c3,
+// PXB x, y, z, sum e2 c2 d, 0} (the row factor m_i is applied by the reduction)
+template <typename T, bool DENSE>
+__global__ __launch_bounds__(256) void assign_pass2_kernel(const T* __restrict__ xa4, int64_t na, const T* __restrict__ xb4,
+                                                           int64_t nb, DevLayers L, const double* __restrict__ mm, double h1,
+                                                           double h2, const double* __restrict__ fac, int64_t ctiles,
+                                                           int64_t na_pad, double* __restrict__ part2,
+                                                           double* __restrict__ P) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, lk = lane >> 4, wi = wave >> 1, wj = wave & 1;
+    const int64_t i0 = (int64_t)blockIdx.x * AT + 32 * wi;
+    const int64_t t_lo = ctiles * blockIdx.y / gridDim.y, t_hi = ctiles * (blockIdx.y + 1) / gridDim.y;
+    Point pa[2][4];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pa[a][r] = load_point(xa4, std::min<int64_t>(i0 + 16 * a + lk + 4 * r, na - 1));
+    double acc[2][4][7];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int k = 0; k < 7; ++k) acc[a][r][k] = 0.0;
+    for (int64_t t = t_lo; t < t_hi; ++t) {
+        const int64_t j0 = t * AT + 32 * wj;
+        f64x4 q[2][2];
+        layer_product<T>(L, i0, j0, na, nb, li, lk, q);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int64_t j = j0 + 16 * b + li;  // < nb_pad: fac is zero for nb <= j
+            const Point cb = load_point(xb4, std::min<int64_t>(j, nb - 1));
+            double f[4];
+            load4(fac + 4 * j, f);
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double d = sq_dist(pa[a][r], cb);
+                    const double e1 = exp(d * h1), e2 = exp(d * h2);
+                    const double t2 = e2 * f[1], t3 = (e2 * q[a][b][r]) * f[2];
+                    acc[a][r][0] += e1 * f[0];
+                    acc[a][r][1] += t2;
+                    acc[a][r][2] += t3;
+                    acc[a][r][3] += t3 * cb.x;
+                    acc[a][r][4] += t3 * cb.y;
+                    acc[a][r][5] += t3 * cb.z;
+                    acc[a][r][6] += t2 * d;
+                    if (DENSE) {
+                        const int64_t i = i0 + 16 * a + lk + 4 * r;
+                        if (i < na && j < nb) P[i * nb + j] = mm[i] * t3;
+                    }
+                }
+        }
+    }
+    // sum over the 16 column lanes (a butterfly inside each group of 16 lanes: the same order on every lane), then over the
+    // two column halves of the tile through LDS
+    __shared__ double red[2][AT][8];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int k = 0; k < 7; ++k) {
+                double v = acc[a][r][k];
+#pragma unroll
+                for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+                if (li == 0) red[wj][32 * wi + 16 * a + lk + 4 * r][k] = v;
+            }
+    __syncthreads();
+    for (int e = threadIdx.x; e < AT * 8; e += 256) {
+        const int row = e >> 3, k = e & 7;
+        const double v = k < 7 ? red[0][row][k] + red[1][row][k] : 0.0;
+        part2[((int64_t)blockIdx.y * na_pad + (int64_t)blockIdx.x * AT + row) * 8 + k] = v;
+    }
+}
+
+// ---- rows: the column splits added in order, times m_i
+__global__ __launch_bounds__(256) void assign_rows_kernel(const double* __restrict__ part2, int64_t csplit, int64_t na,
+                                                          int64_t na_pad, const double* __restrict__ mm,
+                                                          double* __restrict__ K_NA, double* __restrict__ K_NA_spatial,
+                                                          double* __restrict__ K_NA_sigma2, double* __restrict__ PXB,
+                                                          double* __restrict__ rows) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= na) return;
+    double v[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t sp = 0; sp < csplit; ++sp)
+#pragma unroll
+        for (int k = 0; k < 7; ++k) v[k] += part2[(sp * na_pad + i) * 8 + k];
+    const double m = mm[i];
+    K_NA_spatial[i] = m * v[0];
+    K_NA_sigma2[i] = m * v[1];
+    K_NA[i] = m * v[2];
+    PXB[3 * i + 0] = m * v[3], PXB[3 * i + 1] = m * v[4], PXB[3 * i + 2] = m * v[5];
+    rows[i] = m * v[6];
+}
+
+// one workgroup: out[0] = sum of v[0 .. n) in a fixed order
+__global__ __launch_bounds__(256) void assign_sum_kernel(const double* __restrict__ v, int64_t n, double* __restrict__ out) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) s += v[i];
+    const double t = block_sum<256>(s, red);
+    if (threadIdx.x == 0) out[0] = t;
+}
+
+// ---- operand preparation: one wave per cell
+__device__ __forceinline__ double wave_all_sum(double v) { return __shfl(wave_sum(v), 0, 64); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void assign_prepare_kernel(const double* __restrict__ Lraw, int64_t n, int64_t g, int metric,
+                                                             int side, T* __restrict__ Lp, int64_t ld, double* __restrict__ ab) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const double* x = Lraw + i * g;
+    T* o = Lp + i * ld;
+    double cst = 0.0;
+    if (metric == MVF_ASSIGN_EUC || metric == MVF_ASSIGN_SQRT_EUC) {
+        double s = 0.0;
+        for (int64_t k = lane; k < g; k += 64) {
+            const T v = (T)x[k];
+            o[k] = v;
+            s += (double)v * (double)v;
+        }
+        cst = wave_all_sum(s);
+    } else if (metric == MVF_ASSIGN_COS) {
+        double s = 0.0;
+        for (int64_t k = lane; k < g; k += 64) s += x[k] * x[k];
+        const double nrm = fmax(sqrt(wave_all_sum(s)), ASSIGN_EPS);
+        for (int64_t k = lane; k < g; k += 64) o[k] = (T)(x[k] / nrm);
+        cst = side == 0 ? 0.5 : 0.0;
+    } else {  // kl / sym_kl
+        double s = 0.0;
+        for (int64_t k = lane; k < g; k += 64) s += x[k] + 0.01;
+        const double tot = wave_all_sum(s);
+        const bool sym = metric == MVF_ASSIGN_SYM_KL;
+        double e = 0.0;
+        for (int64_t k = lane; k < g; k += 64) {
+            const T p = (T)((x[k] + 0.01) / tot);
+            const double lp = log((double)p + ASSIGN_EPS);
+            e += (double)p * lp;
+            // A side: [p, log p] ; B side: [log q, q]  (kl keeps the first half only)
+            if (side == 0) {
+                o[k] = p;
+                if (sym) o[g + k] = (T)lp;
+            } else {
+                o[k] = (T)lp;
+                if (sym) o[g + k] = p;
+            }
+        }
+        e = wave_all_sum(e);
+        cst = sym ? 0.5 * e : (side == 0 ? e : 0.0);
+    }
+    const int64_t gp = metric == MVF_ASSIGN_SYM_KL ? 2 * g : g;
+    for (int64_t k = gp + lane; k < ld; k += 64) o[k] = (T)0;
+    if (lane == 0) ab[i] = cst;
+}
+
+int64_t padded_features(int64_t g, int metric) { return cdiv(metric == MVF_ASSIGN_SYM_KL ? 2 * g : g, AKS) * AKS; }
+
+template <typename T>
+int run_assign(hipStream_t st, const Plan& p, const void* xa4, int64_t na, const void* xb4, int64_t nb, const DevLayers& L,
+               const double* mm, double h1, double h2, double outlier, double* K_NA, double* K_NB, double* K_NA_spatial,
+               double* K_NA_sigma2, double* PXB, double* scalars, double* P, char* ws) {
+    double* part1 = (double*)(ws + p.off_part1);
+    double* fac = (double*)(ws + p.off_fac);
+    double* part2 = (double*)(ws + p.off_part2);
+    double* rows = (double*)(ws + p.off_rows);
+    hipLaunchKernelGGL((assign_pass1_kernel<T>), dim3((unsigned)p.ctiles, (unsigned)p.rsplit), dim3(256), 0, st, (const T*)xa4, na,
+                       (const T*)xb4, nb, L, mm, h1, h2, p.rtiles, p.nb_pad, part1);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(assign_factors_kernel, dim3((unsigned)cdiv(p.nb_pad, 256)), dim3(256), 0, st, part1, p.rsplit, nb, p.nb_pad,
+                       outlier, fac, K_NB);
+    MVF_LAUNCH_CHECK();
+    if (P)
+        hipLaunchKernelGGL((assign_pass2_kernel<T, true>), dim3((unsigned)p.rtiles, (unsigned)p.csplit), dim3(256), 0, st,
+                           (const T*)xa4, na, (const T*)xb4, nb, L, mm, h1, h2, fac, p.ctiles, p.na_pad, part2, P);
+    else
+        hipLaunchKernelGGL((assign_pass2_kernel<T, false>), dim3((unsigned)p.rtiles, (unsigned)p.csplit), dim3(256), 0, st,
+                           (const T*)xa4, na, (const T*)xb4, nb, L, mm, h1, h2, fac, p.ctiles, p.na_pad, part2, P);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(assign_rows_kernel, dim3((unsigned)cdiv(na, 256)), dim3(256), 0, st, part2, p.csplit, na, p.na_pad, mm, K_NA,
+                       K_NA_spatial, K_NA_sigma2, PXB, rows);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(assign_sum_kernel, dim3(1), dim3(256), 0, st, rows, na, scalars);
+    MVF_LAUNCH_CHECK();
+    return 0;
+}
+
+int assign_entry(const char* who, const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers,
+                 int nlayers, const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier,
+                 double* K_NA, double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars, double* P,
+                 bool dense, void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream) {
+    if (na == 0 || nb == 0) return 0;
+    MVF_REQUIRE(na > 0 && nb > 0, "%s: negative size", who);
+    MVF_REQUIRE(na < ((int64_t)1 << 31) && nb < ((int64_t)1 << 31), "%s: too many cells", who);
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "%s: bad dtype %d", who, (int)dtype);
+    MVF_REQUIRE(nlayers >= 1 && nlayers <= MAX_LAYERS, "%s: need 1 .. %d layers, got %d", who, MAX_LAYERS, nlayers);
+    MVF_REQUIRE(xa4 && xb4 && layers && model_mul && K_NA && K_NB && K_NA_spatial && K_NA_sigma2 && PXB && scalars && workspace &&
+                    (P || !dense),
+                "%s: null pointer", who);
+    MVF_REQUIRE(sigma2 > 0.0 && sigma2_variance > 0.0 && spatial_outlier >= 0.0, "%s: need sigma2 > 0, sigma2_variance > 0, outlier >= 0", who);
+    const Plan p = make_plan(na, nb);
+    MVF_REQUIRE(workspace_bytes >= p.total, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, p.total);
+    DevLayers L;
+    L.n = nlayers;
+    for (int l = 0; l < nlayers; ++l) {
+        const mvf_assign_layer& s = layers[l];
+        MVF_REQUIRE(s.Xp && s.Yp && s.a && s.b, "%s: null pointer in layer %d", who, l);
+        MVF_REQUIRE(s.ld >= AKS && s.ld % AKS == 0, "%s: layer %d: ld must be a positive multiple of %d", who, l, AKS);
+        MVF_REQUIRE(s.metric >= MVF_ASSIGN_EUC && s.metric <= MVF_ASSIGN_COS, "%s: layer %d: bad metric %d", who, l, s.metric);
+        MVF_REQUIRE(s.prob >= MVF_ASSIGN_GAUSS && s.prob <= MVF_ASSIGN_PROB, "%s: layer %d: bad probability type %d", who, l, s.prob);
+        MVF_REQUIRE(s.prob != MVF_ASSIGN_GAUSS || s.param > 0.0, "%s: layer %d: a gauss layer needs a parameter > 0", who, l);
+        DevLayer& d = L.l[l];
+        d.X = s.Xp, d.Y = s.Yp, d.a = s.a, d.b = s.b, d.ld = s.ld, d.prob = s.prob;
+        d.nparam = s.prob == MVF_ASSIGN_GAUSS ? -1.0 / (2.0 * s.param) : 0.0;
+        d.s = s.metric <= MVF_ASSIGN_SQRT_EUC ? 2.0 : (s.metric == MVF_ASSIGN_KL ? 1.0 : 0.5);
+        d.post = s.metric == MVF_ASSIGN_EUC ? 1 : (s.metric == MVF_ASSIGN_SQRT_EUC ? 2 : 0);
+    }
+    for (int l = nlayers; l < MAX_LAYERS; ++l) L.l[l] = L.l[0];
+    const double h1 = -1.0 / (2.0 * (sigma2 / sigma2_variance)), h2 = -1.0 / (2.0 * sigma2);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MVF_F32)
+        return run_assign<float>(st, p, xa4, na, xb4, nb, L, model_mul, h1, h2, spatial_outlier, K_NA, K_NB, K_NA_spatial,
+                                 K_NA_sigma2, PXB, scalars, P, (char*)workspace);
+    return run_assign<double>(st, p, xa4, na, xb4, nb, L, model_mul, h1, h2, spatial_outlier, K_NA, K_NB, K_NA_spatial,
+                              K_NA_sigma2, PXB, scalars, P, (char*)workspace);
+}
+
+}  // namespace
+}  // namespace mvf
+
+using namespace mvf;
+
+extern "C" int64_t mvf_assign_padded_features(int64_t g, int metric) {
+    if (g <= 0 || metric < MVF_ASSIGN_EUC || metric > MVF_ASSIGN_COS) return 0;
+    return padded_features(g, metric);
+}
+
+extern "C" int mvf_assign_prepare(const double* layer, int64_t n, int64_t g, int metric, int side, void* Lp, int64_t ld,
+                                  double* ab, mvf_dtype dtype, void* stream) {
+    if (n == 0) return 0;
+    MVF_REQUIRE(n > 0 && g > 0, "mvf_assign_prepare: need n >= 0 and g > 0");
+    MVF_REQUIRE(metric >= MVF_ASSIGN_EUC && metric <= MVF_ASSIGN_COS, "mvf_assign_prepare: bad metric %d", metric);
+    MVF_REQUIRE(side == 0 || side == 1, "mvf_assign_prepare: side must be 0 (A) or 1 (B)");
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "mvf_assign_prepare: bad dtype %d", (int)dtype);
+    MVF_REQUIRE(ld == padded_features(g, metric), "mvf_assign_prepare: ld must be mvf_assign_padded_features(g, metric)");
+    MVF_REQUIRE(layer && Lp && ab, "mvf_assign_prepare: null pointer");
+    MVF_REQUIRE(cdiv(n, 4) < ((int64_t)1 << 31), "mvf_assign_prepare: too many cells");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MVF_F32)
+        hipLaunchKernelGGL(assign_prepare_kernel<float>, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, layer, n, g, metric, side,
+                           (float*)Lp, ld, ab);
+    else
+        hipLaunchKernelGGL(assign_prepare_kernel<double>, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, layer, n, g, metric, side,
+                           (double*)Lp, ld, ab);
+    MVF_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t mvf_assign_workspace_bytes(int64_t na, int64_t nb) {
+    if (na <= 0 || nb <= 0) return 0;
+    return make_plan(na, nb).total;
+}
+
+extern "C" int mvf_assign(const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers, int nlayers,
+                          const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier, double* K_NA,
+                          double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars, void* workspace,
+                          size_t workspace_bytes, mvf_dtype dtype, void* stream) {
+    return assign_entry("mvf_assign", xa4, na, xb4, nb, layers, nlayers, model_mul, sigma2, sigma2_variance, spatial_outlier, K_NA,
+                        K_NB, K_NA_spatial, K_NA_sigma2, PXB, scalars, nullptr, false, workspace, workspace_bytes, dtype, stream);
+}
+
+extern "C" int mvf_assign_dense(const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers,
+                                int nlayers, const double* model_mul, double sigma2, double sigma2_variance,
+                                double spatial_outlier, double* K_NA, double* K_NB, double* K_NA_spatial, double* K_NA_sigma2,
+                                double* PXB, double* scalars, double* P, void* workspace, size_t workspace_bytes, mvf_dtype dtype,
+                                void* stream) {
+    return assign_entry("mvf_assign_dense", xa4, na, xb4, nb, layers, nlayers, model_mul, sigma2, sigma2_variance, spatial_outlier,
+                        K_NA, K_NB, K_NA_spatial, K_NA_sigma2, PXB, scalars, P, true, workspace, workspace_bytes, dtype, stream);
+}

@@ -590,6 +590,45 @@ class HipKernels:
     def sym_unpack(self, tri, G):
         _lib.check(self.lib.mvf_sym_unpack(_ptr(tri), G.shape[0], _ptr(G), self._stream()), "mvf_sym_unpack")
 
+    @_on_device
+    def assign_prepare(self, layer, metric, side):
+        """One side (0 = A cells, 1 = B cells) of one layer of the assignment step: host (n, g) float64 -> device
+        (X' or Y' (n, ld) in the cell dtype, a or b (n,) float64, ld)  (mvf_assign_prepare)."""
+        L = np.ascontiguousarray(layer, dtype=np.float64)
+        n, g = L.shape
+        ld = int(self.lib.mvf_assign_padded_features(g, int(metric)))
+        Lp = self.empty(n, ld)
+        ab = self.empty(n, dtype=torch.float64)
+        _lib.check(self.lib.mvf_assign_prepare(_ptr(self.h2d(L)), n, g, int(metric), int(side), _ptr(Lp), ld, _ptr(ab),
+                                               self.cdtype, self._stream()), "mvf_assign_prepare")
+        return Lp, ab, ld
+
+    @_on_device
+    def assign(self, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, spatial_outlier, dense=False):
+        """The fused assignment step (mvf_assign / mvf_assign_dense).  layers: [(Xp, Yp, a, b, ld, metric, prob, param)]
+        of device tensors from assign_prepare.  Returns device float64 tensors {K_NA, K_NB, K_NA_spatial, K_NA_sigma2,
+        PXB (na, 3), scalars (1,) = sum P_sigma2 d [, P (na, nb)]}."""
+        na, nb = xa4.shape[0], xb4.shape[0]
+        f64 = torch.float64
+        arr = (_lib.AssignLayer * len(layers))()
+        for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, layers):
+            s.Xp, s.Yp, s.a, s.b, s.ld = _ptr(Xp), _ptr(Yp), _ptr(a), _ptr(b), int(ld)
+            s.metric, s.prob, s.param = int(metric), int(prob), float(param)
+        out = {"K_NA": self.empty(na, dtype=f64), "K_NB": self.empty(nb, dtype=f64), "K_NA_spatial": self.empty(na, dtype=f64),
+               "K_NA_sigma2": self.empty(na, dtype=f64), "PXB": self.empty(na, 3, dtype=f64), "scalars": self.empty(1, dtype=f64)}
+        need = int(self.lib.mvf_assign_workspace_bytes(na, nb))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        head = (_ptr(xa4), na, _ptr(xb4), nb, arr, len(layers), _ptr(model_mul), float(sigma2), float(sigma2_variance),
+                float(spatial_outlier), _ptr(out["K_NA"]), _ptr(out["K_NB"]), _ptr(out["K_NA_spatial"]),
+                _ptr(out["K_NA_sigma2"]), _ptr(out["PXB"]), _ptr(out["scalars"]))
+        tail = (_ptr(ws), need, self.cdtype, self._stream())
+        if dense:
+            out["P"] = self.empty(na, nb, dtype=f64)
+            _lib.check(self.lib.mvf_assign_dense(*head, _ptr(out["P"]), *tail), "mvf_assign_dense")
+        else:
+            _lib.check(self.lib.mvf_assign(*head, *tail), "mvf_assign")
+        return out
+
     @staticmethod
     def _affine_buf(affine):
         if affine is None:

@@ -30,9 +30,20 @@ MVF_COMM_ID_BYTES = 128
 RED_SUM, RED_MIN = 0, 1
 GRAM_TILES, GRAM_RHS, GRAM_REDUCE, GRAM_REDUCE_RHS = 1, 2, 4, 8
 RK45_UNIFORM_TIME, RK45_ARC_LENGTH = 0, 1
+ASSIGN_METRICS = {"euc": 0, "euclidean": 0, "square_euc": 1, "square_euclidean": 1, "kl": 2, "sym_kl": 3, "cos": 4, "cosine": 4}
+ASSIGN_PROBS = {"gauss": 0, "gaussian": 0, "cos": 1, "cosine": 1, "prob": 2}
+ASSIGN_MAX_LAYERS = 4
 EVAL_V, EVAL_JAC, EVAL_DIV, EVAL_CURL, EVAL_ACC, EVAL_CURV, EVAL_TORS, EVAL_JDET = 1, 2, 4, 8, 16, 32, 64, 128
 
 _p, _i64, _i, _d, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_size_t
+
+
+
+class AssignLayer(C.Structure):
+    """mvf_assign_layer of include/mvf.h: one prepared expression / representation layer (device pointers)."""
+    _fields_ = [("Xp", C.c_void_p), ("Yp", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("ld", C.c_int64),
+                ("metric", C.c_int), ("prob", C.c_int), ("param", C.c_double)]
+
 
 # name -> (restype, argtypes); mirrors include/mvf.h one to one
 SIGNATURES = {
@@ -92,6 +103,13 @@ SIGNATURES = {
     "mvf_integrate": (_i, [_p, _i64, _p, _i64, _d, _p, C.POINTER(C.c_double), _d, _i, _i, _p, _i, _p]),
     "mvf_integrate_rk45": (_i, [_p, _i64, _p, _i64, _d, _p, C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _d, _d,
                                 _d, _d, _i, _i, _i, _p, _p, _p, _i, _p]),
+    "mvf_assign_padded_features": (_i64, [_i64, _i]),
+    "mvf_assign_prepare": (_i, [_p, _i64, _i64, _i, _i, _p, _i64, _p, _i, _p]),
+    "mvf_assign_workspace_bytes": (_sz, [_i64, _i64]),
+    "mvf_assign": (_i, [_p, _i64, _p, _i64, C.POINTER(AssignLayer), _i, _p, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _sz, _i,
+                        _p]),
+    "mvf_assign_dense": (_i, [_p, _i64, _p, _i64, C.POINTER(AssignLayer), _i, _p, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p,
+                              _sz, _i, _p]),
 }
 
 _lib = None

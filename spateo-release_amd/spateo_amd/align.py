@@ -1,5 +1,6 @@
-"""Alignment-side callers of the same Gaussian kernel and M-step: ``BA_transform`` and
-``update_nonrigid`` (the non-rigid update of ``Morpho_pairwise``: the SparseVFC M-step with Gamma <-> K, K_NA <-> P).
+"""Alignment-side callers of the same Gaussian kernel and M-step: ``BA_transform``,
+``update_nonrigid`` (the non-rigid update of ``Morpho_pairwise``: the SparseVFC M-step with Gamma <-> K, K_NA <-> P) and
+``update_assignment`` (its assignment step, fused: every weight the other updates consume, without the NA x NB matrix).
 
 Mirror of ``spateo/alignment/transform.py:61-116``: the learned non-rigid alignment ``vecfld`` (output of
 ``st.align.morpho_align``) applied to query points.  The N x M kernel contraction ``con_K(x, ctrl, beta) @ Coff`` runs
@@ -18,7 +19,120 @@ from . import _runtime as _rt
 from .engine import SparseVFCEngine, _consistent_K
 from .vectorfield import vector_field_function
 
-__all__ = ["BA_transform", "update_nonrigid"]
+__all__ = ["BA_transform", "update_nonrigid", "update_assignment"]
+
+RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
+
+
+def _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
+                          probability_parameters, sparse_calculation_mode, return_P):
+    """Validation of update_assignment (no device needed): the arrays as float64 and the per-layer (metric, probability
+    type, parameter) codes of include/mvf.h."""
+    XA, XB = np.asarray(XAHat, dtype=np.float64), np.asarray(coordsB, dtype=np.float64)
+    if sparse_calculation_mode:
+        raise NotImplementedError("update_assignment: sparse_calculation_mode (top-k sparsification of P) needs the dense P "
+                                  "and is not supported")
+    if XA.ndim != 2 or XB.ndim != 2 or XA.shape[1] != XB.shape[1]:
+        raise AssertionError("X and Y do not have the same number of features.")  # _euc_distance_backend (utils.py:775)
+    if XA.shape[1] not in (2, 3):
+        raise NotImplementedError(f"update_assignment: spatial coordinates must be 2-D or 3-D, got D = {XA.shape[1]}")
+    LA = [np.asarray(a, dtype=np.float64) for a in (exp_layers_A if isinstance(exp_layers_A, (list, tuple)) else [exp_layers_A])]
+    LB = [np.asarray(b, dtype=np.float64) for b in (exp_layers_B if isinstance(exp_layers_B, (list, tuple)) else [exp_layers_B])]
+    n_layers = len(LA)
+    as_list = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n_layers  # noqa: E731
+    metrics, kinds = as_list(dissimilarity), as_list(probability_type)
+    params = [None] * n_layers if probability_parameters is None else as_list(probability_parameters)
+    if n_layers < 1 or not (len(LB) == len(metrics) == len(kinds) == len(params) == n_layers):
+        raise ValueError("exp_layers_A, exp_layers_B, dissimilarity, probability_type and probability_parameters must list "
+                         "the same (non-zero) number of layers")
+    if n_layers > _lib.ASSIGN_MAX_LAYERS:
+        raise NotImplementedError(f"update_assignment: at most {_lib.ASSIGN_MAX_LAYERS} layers are supported, got {n_layers}")
+    codes = []
+    for A, B, met, kind, par in zip(LA, LB, metrics, kinds, params):
+        if met == "label":
+            raise NotImplementedError("update_assignment: the 'label' metric (a label-transfer table lookup, not a product "
+                                      "of features) is not supported")
+        if met not in _lib.ASSIGN_METRICS:
+            raise ValueError(f"Unsupported dissimilarity metric: {met}")
+        if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1]:
+            raise AssertionError("X and Y do not have the same number of features.")
+        if len(A) != len(XA) or len(B) != len(XB):
+            raise ValueError("every layer must have one row per cell of its slice")
+        if str(kind).lower() not in _lib.ASSIGN_PROBS:
+            raise ValueError(f"Unsupported probability type: {kind}")  # calc_probability (utils.py:983)
+        prob = _lib.ASSIGN_PROBS[str(kind).lower()]
+        if prob == 0 and par is None:
+            raise ValueError("probability_parameter must be provided for 'Gauss' probability type.")  # (utils.py:976)
+        codes.append((_lib.ASSIGN_METRICS[met], prob, 0.0 if par is None else float(par)))
+    if return_P and len(XA) * len(XB) > RETURN_P_MAX_ENTRIES:
+        raise ValueError(f"return_P=True materialises NA x NB = {len(XA) * len(XB)} entries; the cap is "
+                         f"{RETURN_P_MAX_ENTRIES} (align.RETURN_P_MAX_ENTRIES)")
+    return XA, XB, LA, LB, codes
+
+
+def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity, probability_type,
+                      probability_parameters, sigma2, alpha, SigmaDiag, gamma, samples_s, sigma2_variance=1.0,
+                      dtype: str = "float64", device=None, return_P=False, sparse_calculation_mode=False):
+    """The assignment step of Spateo's alignment, ``Morpho_pairwise._update_assignment_P``
+    (``spateo/alignment/methods/morpho_class.py:1071-1200``) followed by ``get_P_core`` on the dense path
+    (``spateo/alignment/methods/utils.py:993-1096``; ``use_chunk`` changes nothing mathematically), on the MI355X as one
+    fused two-pass kernel (``mvf_assign``): the NA x NB matrix ``P`` is never written.  For SVI the caller passes the
+    batch's rows of ``coordsB`` and of the B layers and blends the three ``Sp*`` scalars itself.
+
+    ``XAHat`` (NA, D) and ``coordsB`` (NB, D) with D in {2, 3}; 1 to 4 layers ``exp_layers_A[l]`` (NA, G_l) /
+    ``exp_layers_B[l]`` (NB, G_l) with ``dissimilarity[l]`` in ``"kl"``, ``"sym_kl"``, ``"euc"`` / ``"euclidean"`` (the
+    SQUARED distance clamped at 0, as the reference has it), ``"square_euc"`` / ``"square_euclidean"`` (its square root),
+    ``"cos"`` / ``"cosine"``; ``probability_type[l]`` in ``"gauss"`` (``exp(-d / (2 probability_parameters[l]))``),
+    ``"cos"`` (``1 - d``), ``"prob"`` (``d``); ``alpha`` and ``SigmaDiag`` (NA,); the rest scalars.  ``dtype`` is the
+    storage of the coordinates and of the prepared layer operands; distances, exponents and every sum are float64 in
+    both modes.  Not supported (``NotImplementedError``): the ``"label"`` metric, ``sparse_calculation_mode``, more than
+    4 layers, D outside {2, 3}.
+
+    Returns host float64: ``K_NA``, ``K_NA_spatial``, ``K_NA_sigma2`` (NA,), ``K_NB`` (NB,), ``Sp``, ``Sp_spatial``,
+    ``Sp_sigma2``, ``sigma2_related`` (already divided by ``Dim * Sp_sigma2``, ``:1200``), ``PXB = P @ coordsB`` (NA, D)
+    and, with ``return_P=True``, the dense ``P`` (NA, NB) - label transfer and debugging only; ``ValueError`` above
+    ``RETURN_P_MAX_ENTRIES`` entries.  Two calls give bit-identical results.
+
+    What the other updates take from it:
+
+    * ``update_nonrigid``'s ``PXB_term`` is ``PXB - RnA * K_NA[:, None]``;
+    * ``_update_rigid``'s ``XA_hat^T P XB_hat`` (``:1300-1408``) is ``XA_hat^T PXB - (XA_hat^T K_NA) mu_XB``, from
+      ``PXB`` and ``K_NA``."""
+    if dtype not in ("float32", "float64"):
+        raise ValueError("dtype must be 'float32' or 'float64'")
+    XA, XB, LA, LB, codes = _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
+                                                  probability_parameters, sparse_calculation_mode, return_P)
+    NA, D = XA.shape
+    al, sd = np.asarray(alpha, dtype=np.float64).reshape(-1), np.asarray(SigmaDiag, dtype=np.float64).reshape(-1)
+    if len(al) != NA or len(sd) != NA:
+        raise ValueError("alpha and SigmaDiag must be (NA,)")
+    sigma2, gamma, samples_s, sigma2_variance = float(sigma2), float(gamma), float(samples_s), float(sigma2_variance)
+    names = ("K_NA", "K_NB", "K_NA_spatial", "K_NA_sigma2")
+    if NA == 0 or len(XB) == 0:
+        out = {q: np.zeros(len(XB) if q == "K_NB" else NA) for q in names}
+        out.update(Sp=0.0, Sp_spatial=0.0, Sp_sigma2=0.0, sigma2_related=float("nan"), PXB=np.zeros((NA, D)))
+        if return_P:
+            out["P"] = np.zeros((NA, len(XB)))
+        return out
+    model_mul = al * np.exp(-sd / sigma2)                                                   # morpho_class.py:1087
+    outlier = np.power(2 * np.pi * sigma2, D / 2) * (1 - gamma) / (gamma * (samples_s * NA))  # utils.py:1051-1053
+    k = _rt._make_kernels(device, dtype)
+    layers = []
+    for A, B, (metric, prob, param) in zip(LA, LB, codes):
+        Xp, a, ld = k.assign_prepare(A, metric, 0)
+        Yp, b, _ = k.assign_prepare(B, metric, 1)
+        layers.append((Xp, Yp, a, b, ld, metric, prob, param))
+    dev = k.assign(k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, float(outlier),
+                   dense=bool(return_P))
+    keys = list(names) + ["PXB", "scalars"] + (["P"] if return_P else [])
+    host = dict(zip(keys, _rt._to_host(k, [dev[q] for q in keys])))
+    out = {q: np.array(host[q], dtype=np.float64) for q in names}
+    out["Sp"], out["Sp_spatial"], out["Sp_sigma2"] = (float(out[q].sum()) for q in ("K_NB", "K_NA_spatial", "K_NA_sigma2"))
+    out["sigma2_related"] = float(host["scalars"][0]) / (D * out["Sp_sigma2"])
+    out["PXB"] = np.array(host["PXB"][:, :D], dtype=np.float64)
+    if return_P:
+        out["P"] = np.array(host["P"], dtype=np.float64)
+    return out
 
 
 def update_nonrigid(coordsA, inducing_variables, beta, K_NA, PXB_term, sigma2, lambdaVF, dtype: str = "float64",
