@@ -38,7 +38,7 @@ def test_goldens_cover_the_cases_the_step_is_used_on(g):
     assert any(float(g[f"{t}_sigma2_variance"]) != 1.0 for t in ac.case_tags(g))
     for t in ac.case_tags(g):
         NA, NB = len(g[f"{t}_XAHat"]), len(g[f"{t}_coordsB"])
-        assert NA % 16 and NB % 16
+        assert NA % 16 and NB % 16   # exact tile multiples, 1-cell sides and the split plans: tests/_assign_edge_cases.py
         far = g[f"{t}_far"]
         assert len(far) >= 0.05 * NB and np.all(g[f"{t}_K_NB"][far] == 0.0)  # columns whose terms all underflow: exactly 0
         assert all(np.isfinite(g[f"{t}_{q}"]).all() for q in ac.QUANTITIES)

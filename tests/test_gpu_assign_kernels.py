@@ -1,0 +1,373 @@
+"""Kernel-level edge tests of the fused assignment step (``csrc/mvf_assign.hip``) through the raw C ABI - ``mvf_assign_prepare``,
+``mvf_assign``, ``mvf_assign_dense`` - on ``cuda:0`` in both cell dtypes, at the tile / wave / MFMA-block / k-step / split edges
+where such kernels go wrong.  tests/_assign_edge_cases.py holds the inputs, the case lists and the NumPy references;
+tests/test_assign_kernel_refs.py proves without a GPU that the references are right to 1e-12, that every case is well
+conditioned and that each targeted off-by-one would move a compared quantity by >= 1e-7.
+
+A  ``mvf_assign_prepare`` alone against ``prepare_reference``: euc operands bit for bit, pad features exactly 0, float64
+   operands within 1e-13 max(1, |v|), float32 operands within one float32 ulp in at most 1e-3 of the elements, a / b within
+   1e-12 of the value recomputed from the read-back operands.
+B  The pair stage on the device's OWN operands: the prepared operands and coordinates are read back and fed to
+   ``pair_reference``; every output within 1e-10 (``_assign_case.F64_TOL``) of the quantity's maximum in BOTH dtype modes (with
+   the stored operands as input, float32 mode does the same float64 arithmetic).  Every call has a guard behind every
+   output and behind the workspace, runs on a workspace filled with NaN bit patterns, and is made twice (same bits).
+C  The dense variant at shapes whose tile edges cut P.
+D  Workspace: NaN-filled against zero-filled, stale partials of a larger call, a larger workspace than needed; a non-default
+   stream.
+E  One representative per family through ``spateo_amd.align.update_assignment`` against the formula restatement, at the bounds
+   of tests/test_gpu_assign.py.
+
+No bound is fitted to what the device returned.  Run with ``-s`` for the largest deviation of every family
+(profiles/assign_kernel_edges.md records them)."""
+import numpy as np
+import pytest
+import torch
+
+import _assign_case as ac
+import _assign_edge_cases as ec
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+DTYPES = ["float64", "float32"]
+SENTINEL = {torch.float64: -1.2345e300, torch.float32: -1.2345e30}
+GUARD = 4096  # elements behind every buffer
+_KERNELS = {}
+_WORST = {}
+
+
+def _k(dtype):
+    if dtype not in _KERNELS:
+        from spateo_amd._kernels import HipKernels
+
+        assert torch.cuda.is_available(), "GPU tests need a HIP device"
+        _KERNELS[dtype] = HipKernels(DEV, dtype)
+    return _KERNELS[dtype]
+
+
+def _note(family, dtype, value):
+    key = (family, dtype)
+    _WORST[key] = max(_WORST.get(key, 0.0), float(value))
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _deviation_table():
+    yield
+    print("\n| case family | dtype | largest deviation |\n|---|---|---|")
+    for (fam, dtype), v in sorted(_WORST.items()):
+        print(f"| {fam} | {dtype} | {v:.3g} |")
+
+
+def _dev(a, dtype=torch.float64):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(DEV)
+
+
+def _guarded(n, tdtype=torch.float64):
+    """n live elements and GUARD more, all holding the sentinel."""
+    return torch.full((n + GUARD,), SENTINEL[tdtype], dtype=tdtype, device=DEV)
+
+
+def _intact(buf, n):
+    return bool((buf[n:] == SENTINEL[buf.dtype]).all())
+
+
+def _written(buf, n):
+    return bool((buf[:n] != SENTINEL[buf.dtype]).all())
+
+
+def _same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
+
+
+# ------------------------------------------------------------------------------------------------------ raw calls
+def _prepare(k, layer, metric, side):
+    """mvf_assign_prepare into guarded buffers: (X' / Y' (n, ld) device view, a / b (n,) device view, ld)."""
+    from spateo_amd import _lib
+
+    L = _dev(np.asarray(layer, dtype=np.float64))
+    n, g = L.shape
+    ld = int(k.lib.mvf_assign_padded_features(g, ec.METRICS[metric]))
+    assert ld == ec.padded_features(g, metric)
+    Lp, ab = _guarded(n * ld, k.tdtype), _guarded(n)
+    _lib.check(k.lib.mvf_assign_prepare(L.data_ptr(), n, g, ec.METRICS[metric], side, Lp.data_ptr(), ld, ab.data_ptr(), k.cdtype,
+                                        k._stream()), "mvf_assign_prepare")
+    torch.cuda.synchronize()
+    assert _intact(Lp, n * ld) and _intact(ab, n), "mvf_assign_prepare wrote behind a buffer"
+    assert _written(Lp, n * ld) and _written(ab, n), "mvf_assign_prepare left an element unwritten"
+    return Lp[: n * ld].view(n, ld), ab[:n], ld
+
+
+class _DeviceCase:
+    """A case on the device: coordinates and model_mul uploaded, every layer prepared BY THE DEVICE, and all of it read back."""
+
+    def __init__(self, name, dtype):
+        c, k = ec.case(name), _k(dtype)
+        self.name, self.dtype, self.case, self.k = name, dtype, c, k
+        self.na, self.nb = len(c["XA"]), len(c["XB"])
+        self.xa4, self.xb4 = k.to_x4(c["XA"]), k.to_x4(c["XB"])
+        mm, self.outlier = ec.raw_scalars(c)
+        self.mm = _dev(mm)
+        self.layers, self.host_layers = [], []
+        for A, B, met, kind, par in zip(c["layers_A"], c["layers_B"], c["dissimilarity"], c["probability_type"],
+                                        c["probability_parameters"]):
+            Xp, a, ld = _prepare(k, A, met, 0)
+            Yp, b, _ = _prepare(k, B, met, 1)
+            self.layers.append((Xp, Yp, a, b, ld, ec.METRICS[met], ec.PROBS[kind], 0.0 if par is None else float(par)))
+            self.host_layers.append((Xp.double().cpu().numpy(), Yp.double().cpu().numpy(), a.cpu().numpy(), b.cpu().numpy(),
+                                     met, kind, par))
+        self.xa, self.xb = self.xa4.double().cpu().numpy(), self.xb4.double().cpu().numpy()
+        assert not self.xa[:, 3].any() and not self.xb[:, 3].any() and not self.xa[:, c["XA"].shape[1]:].any()
+        self.mm_host = mm
+        self._ref = None
+
+    def reference(self):
+        """pair_reference on exactly what the device holds."""
+        if self._ref is None:
+            c = self.case
+            self._ref = ec.pair_reference(self.xa, self.xb, self.host_layers, self.mm_host, c["sigma2"], c["sigma2_variance"],
+                                          self.outlier)
+        return self._ref
+
+
+_CASES = {}
+
+
+def _device_case(name, dtype):
+    if (name, dtype) not in _CASES:
+        if len(_CASES) >= 4:
+            _CASES.pop(next(iter(_CASES)))
+        _CASES[(name, dtype)] = _DeviceCase(name, dtype)
+    return _CASES[(name, dtype)]
+
+
+def _nan_workspace(nbytes):
+    """A guarded workspace whose live bytes are NaN bit patterns: a kernel that reads workspace it did not write returns NaN."""
+    assert nbytes % 8 == 0
+    ws = _guarded(nbytes // 8)
+    ws[: nbytes // 8] = float("nan")
+    return ws
+
+
+def _assign(dc, dense=False, ws=None, ws_bytes=None):
+    """mvf_assign / mvf_assign_dense through the raw ABI on the current stream.  Every output sits in front of a guard; the
+    workspace (default: exactly mvf_assign_workspace_bytes, NaN-filled, guarded) likewise.  Returns host arrays."""
+    from spateo_amd import _lib
+
+    k, na, nb = dc.k, dc.na, dc.nb
+    sizes = {"K_NA": na, "K_NB": nb, "K_NA_spatial": na, "K_NA_sigma2": na, "PXB": 3 * na, "scalar": 1}
+    if dense:
+        sizes["P"] = na * nb
+    bufs = {q: _guarded(n) for q, n in sizes.items()}
+    need = int(k.lib.mvf_assign_workspace_bytes(na, nb))
+    assert need == ec.workspace_bytes(na, nb)
+    if ws is None:
+        ws, ws_bytes = _nan_workspace(need), need
+    arr = (_lib.AssignLayer * len(dc.layers))()
+    for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, dc.layers):
+        s.Xp, s.Yp, s.a, s.b, s.ld = Xp.data_ptr(), Yp.data_ptr(), a.data_ptr(), b.data_ptr(), int(ld)
+        s.metric, s.prob, s.param = int(metric), int(prob), float(param)
+    c = dc.case
+    head = (dc.xa4.data_ptr(), na, dc.xb4.data_ptr(), nb, arr, len(dc.layers), dc.mm.data_ptr(), float(c["sigma2"]),
+            float(c["sigma2_variance"]), float(dc.outlier)) + tuple(bufs[q].data_ptr() for q in
+                                                                   ("K_NA", "K_NB", "K_NA_spatial", "K_NA_sigma2", "PXB", "scalar"))
+    tail = (ws.data_ptr(), int(ws_bytes), k.cdtype, k._stream())
+    if dense:
+        _lib.check(k.lib.mvf_assign_dense(*head, bufs["P"].data_ptr(), *tail), "mvf_assign_dense")
+    else:
+        _lib.check(k.lib.mvf_assign(*head, *tail), "mvf_assign")
+    torch.cuda.synchronize()
+    for q, n in sizes.items():
+        assert _intact(bufs[q], n), f"{dc.name}: wrote behind {q}[{n}]"
+        assert _written(bufs[q], n), f"{dc.name}: left an element of {q} unwritten"
+    assert _intact(ws, ws_bytes // 8), f"{dc.name}: wrote behind the workspace"
+    out = {q: bufs[q][:n].cpu().numpy() for q, n in sizes.items()}
+    out["PXB"] = out["PXB"].reshape(na, 3)
+    out["scalar"] = out["scalar"].reshape(())
+    if dense:
+        out["P"] = out["P"].reshape(na, nb)
+    for q, v in out.items():
+        assert np.isfinite(v).all(), f"{dc.name}: {q} is not finite"
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------ A: prepare
+def _ulps32(got, ref):
+    return np.abs(got.astype(np.float64) - ref.astype(np.float64)) / np.spacing(np.abs(ref)).astype(np.float64)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("metric", sorted(ec.METRICS))
+def test_prepare_feature_sweep_both_sides(dtype, metric):
+    k = _k(dtype)
+    T = np.dtype(dtype).type
+    rng = np.random.default_rng(11)
+    worst, off, total, worst_ab = 0.0, 0, 0, 0.0
+    for g in ec.PREPARE_GS:
+        gp = 2 * g if metric == "sym_kl" else g
+        for n in ec.PREPARE_NS:
+            labels = rng.integers(0, 5, n)
+            layer = (ec.counts_layer if metric in ("kl", "sym_kl") else ec.grid_layer)(rng, g, labels, 11)
+            zero = 1 if n >= 3 else None   # one all-zero row among live ones
+            if zero is not None:
+                layer[zero] = 0.0
+            for side in (0, 1):
+                Lp, ab, ld = _prepare(k, layer, metric, side)
+                got, gab = Lp.cpu().numpy(), ab.cpu().numpy()
+                ref, rab = ec.prepare_reference(layer, metric, side, T)
+                assert got.shape == ref.shape == (n, ld) and got.dtype == ref.dtype
+                assert not got[:, gp:].any(), (g, n, side, "pad features")
+                if metric in ("euc", "square_euc"):
+                    assert np.array_equal(got, ref), (g, n, side)
+                elif dtype == "float64":
+                    err = np.abs(got - ref) / np.maximum(1.0, np.abs(ref))
+                    worst = max(worst, float(err.max()))
+                    assert err.max() <= ec.PREP_F64_TOL, (g, n, side, float(err.max()))
+                else:
+                    ulps = _ulps32(got[:, :gp], ref[:, :gp])
+                    assert ulps.max() <= 1.0, (g, n, side, float(ulps.max()))
+                    off, total = off + int((ulps > 0).sum()), total + ulps.size
+                # a / b from the operands the device stored
+                w = got.astype(np.float64)
+                if metric in ("euc", "square_euc"):
+                    want = (w * w).sum(1)
+                elif metric == "cos":
+                    want = np.full(n, 0.5 if side == 0 else 0.0)
+                    assert np.array_equal(gab, want)
+                else:
+                    p = w[:, :g] if (side == 0) else (w[:, g:2 * g] if metric == "sym_kl" else None)
+                    e = np.zeros(n) if p is None else (p * np.log(p + ec.EPS)).sum(1)
+                    want = 0.5 * e if metric == "sym_kl" else e
+                top = max(float(np.abs(want).max()), float(np.abs(rab).max()))
+                if top > 0:
+                    worst_ab = max(worst_ab, float(np.abs(gab - want).max() / top), float(np.abs(gab - rab).max() / top))
+                    assert np.abs(gab - want).max() <= ec.REF_TOL * top and np.abs(gab - rab).max() <= ec.REF_TOL * top, (g, n, side)
+                else:
+                    assert not gab.any()
+                if zero is not None:   # all-zero rows: cos a zero operand row and a = 1/2, kl / sym_kl the uniform profile
+                    if metric == "cos":
+                        assert not got[zero].any() and gab[zero] == (0.5 if side == 0 else 0.0)
+                    elif metric in ("kl", "sym_kl"):
+                        for part in ([got[zero, :g]] + ([got[zero, g:2 * g]] if metric == "sym_kl" else [])):
+                            assert (part == part[0]).all(), (g, n, side)
+                        p0 = got[zero, 0] if side == 0 else (got[zero, g] if metric == "sym_kl" else None)
+                        if p0 is not None and dtype == "float64":
+                            assert abs(p0 - 1.0 / g) <= ec.PREP_F64_TOL
+                        elif p0 is not None:
+                            assert _ulps32(np.array([p0]), np.array([T(1.0 / g)]))[0] <= 1.0
+    print(f"prepare {metric} {dtype}: operands {worst:.2e} (float64, rel), {off} of {total} float32 elements one ulp off; "
+          f"a / b {worst_ab:.2e}")
+    if dtype == "float64":
+        _note(f"prepare {metric}: operands", dtype, worst)
+    else:
+        _note(f"prepare {metric}: fraction of elements one ulp off", dtype, off / max(total, 1))
+        assert off <= ec.PREP_F32_FRACTION * total, (off, total)
+    _note(f"prepare {metric}: a / b", dtype, worst_ab)
+
+
+# ------------------------------------------------------------------------------------------------------ B: pair stage
+def _check_against_reference(dc, got, dense=False):
+    ref = dc.reference()
+    dev = ec.raw_deviations(got, ref, with_P=dense)
+    print(f"  {dc.name} {dc.dtype} plan {ec.plan(dc.na, dc.nb)}: " + ", ".join(f"{q} {v:.1e}" for q, v in dev.items()))
+    for q, v in dev.items():
+        _note(f"{ec.family(dc.name)}: {q}", dc.dtype, v)
+    for q, v in dev.items():
+        assert v <= ac.F64_TOL, (dc.name, dc.dtype, q, v)
+    far = dc.case["far"]
+    assert not got["K_NB"][far].any() and (not dense or not got["P"][:, far].any())   # out of reach: exact zeros
+    near = np.setdiff1d(np.arange(dc.nb), far)
+    assert np.all(got["K_NB"][near] > 0.0)
+    return dev
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", ec.PAIR_CASES)
+def test_pair_stage_on_the_devices_own_operands(dtype, name):
+    dc = _device_case(name, dtype)
+    got = _assign(dc)
+    _check_against_reference(dc, got)
+    again = _assign(dc)
+    for q in ec.RAW:
+        assert _same_bits(got[q], again[q]), (name, q)   # two calls, same bits: every case, every split plan
+    if ec.SPECS[name][1].get("far") == "all":
+        assert all(not got[q].any() for q in ec.RAW)
+
+
+# ------------------------------------------------------------------------------------------------------ C: dense
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", ec.DENSE_CASES)
+def test_dense_variant_where_tile_edges_cut_P(dtype, name):
+    dc = _device_case(name, dtype)
+    got = _assign(dc, dense=True)   # (the guard behind P[na nb] is checked in _assign)
+    _check_against_reference(dc, got, dense=True)
+    plain = _assign(dc)
+    for q in ec.RAW:
+        assert _same_bits(plain[q], got[q]), (name, q)
+    P = got["P"]
+    for a, b, q in ((P.sum(1), got["K_NA"], "K_NA"), (P.sum(0), got["K_NB"], "K_NB"), (P @ dc.xb[:, :3], got["PXB"], "PXB")):
+        err = float(np.abs(a - b).max() / np.abs(b).max())
+        _note(f"dense: P against {q}", dtype, err)
+        assert err <= ec.REF_TOL, (name, q, err)
+
+
+# ------------------------------------------------------------------------------------------------------ D: workspace, stream
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("small,large", [("cells-65x33", "feat-kl-g17"), ("feat-kl-g17", "split-2500x2500"),
+                                         ("split-50x4417", "split-4417x50")])
+def test_workspace_contents_and_size_do_not_matter(dtype, small, large):
+    """A workspace larger than needed, (1) zero-filled, (2) NaN-filled, (3) holding the partials of a larger call: same bits,
+    nothing written behind it."""
+    ds, dl = _device_case(small, dtype), _device_case(large, dtype)
+    need_s, need_l = ec.workspace_bytes(ds.na, ds.nb), ec.workspace_bytes(dl.na, dl.nb)
+    size = max(need_s, need_l) + 4096
+    assert need_s < size
+    ws = _guarded(size // 8)
+    ws[: size // 8] = 0.0
+    zero = _assign(ds, ws=ws, ws_bytes=size)
+    ws[: size // 8] = float("nan")
+    nan = _assign(ds, ws=ws, ws_bytes=size)
+    big = _assign(dl, ws=ws, ws_bytes=size)
+    stale = _assign(ds, ws=ws, ws_bytes=size)
+    ws2 = _nan_workspace(size)
+    ws2[: need_s // 8] = 0.0   # NaN everywhere behind what the call needs
+    tight = _assign(ds, ws=ws2, ws_bytes=size)
+    _check_against_reference(dl, big)
+    for q in ec.RAW:
+        assert _same_bits(zero[q], nan[q]) and _same_bits(zero[q], stale[q]) and _same_bits(zero[q], tight[q]), (small, q)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", ["feat-kl-g17", "split-4417x50", "layers-4"])
+def test_a_call_on_another_stream_gives_the_same_bits(dtype, name):
+    dc = _device_case(name, dtype)
+    first = _assign(dc)
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream(device=DEV)
+    with torch.cuda.stream(stream):
+        assert dc.k._stream() == stream.cuda_stream != torch.cuda.default_stream(DEV).cuda_stream
+        other = _assign(dc, dense=False)
+    torch.cuda.synchronize()
+    for q in ec.RAW:
+        assert _same_bits(first[q], other[q]), (name, q)
+
+
+# ------------------------------------------------------------------------------------------------------ E: the wrapper
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("name", sorted(ec.WRAPPER_CASES))
+def test_update_assignment_on_one_representative_per_family(dtype, name):
+    """Padding to x4, model_mul, the outlier constant, the PXB[:, :D] slice and the scalars on the new shapes, against the
+    formula restatement on the UNROUNDED inputs: float64 1e-10, float32 max(1.25 x the float32 floor of the nearest golden,
+    1e-5) - the bounds of test_a_size_no_golden_holds_against_the_chunked_restatement."""
+    import spateo_amd
+
+    c = ec.case(name)
+    args, kw = ec.call_arguments(c)
+    got = spateo_amd.align.update_assignment(*args, dtype=dtype, device=DEV, **kw)
+    ref = ac.restatement(*args, chunk=512, **kw)
+    tols = ac.tolerances(ac.load(), ec.WRAPPER_CASES[name], dtype)
+    assert all(t >= ac.F32_BASE for t in tols.values()) or dtype == "float64"
+    ac.check(got, ref, tols, f"update_assignment {name} {dtype}")
+    dev = ac.deviations(got, ref)
+    _note("update_assignment: all quantities", dtype, max(dev.values()))
+    assert got["PXB"].shape == c["XA"].shape and not got["K_NB"][c["far"]].any()
