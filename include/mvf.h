@@ -509,6 +509,48 @@ int mvf_assign_dense(const void* xa4, int64_t na, const void* xb4, int64_t nb, c
                      double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars, double* P,
                      void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream);
 
+/* ---- alignment: the O(N) glue of one iteration between the assignment and the non-rigid update (mvf_align.hip) ----------
+ * With mvf_assign, mvf_gram, mvf_solve_minnorm*, mvf_apply and mvf_pinv_diag these three make the loop of
+ * `Morpho_pairwise.run` (spateo/alignment/methods/morpho_class.py:280-294) device resident: per iteration the host reads
+ * ONE block of MVF_ALIGN_MOMENT_DOUBLES float64 and does the 3 x 3 SVDs and the scalar updates.  Float64 arithmetic
+ * whatever `dtype` (the storage of the x4 arrays), no floating-point atomics, partial sums added in a fixed order: two
+ * calls give bit-identical results.  coordsA / coordsB / PXB / RnA / XAHat / PXB_term are n x 3 float64 (2-D data: third
+ * column 0, R and t embedded in 3 x 3 / 3).  ABI version rule: entry points that only ADD to the table leave mvf_version
+ * unchanged (as mvf_assign* did at 7); the version moves when an existing signature or layout changes. */
+#define MVF_ALIGN_MOMENT_DOUBLES 64
+/* Replaces: `_update_alpha` (morpho_class.py:1250-1252) and the `model_mul` of the next `_update_assignment_P` (:1087).
+ * alpha_i = exp(psi(kappa_i + K_NA_spatial_i) - psi(kappa_i na + Sp_spatial)), model_mul_i = alpha_i exp(-SigmaDiag_i /
+ * sigma2); psi = digamma for positive arguments (recurrence up to 10, then the asymptotic series through x^-14).
+ * na == 0 launches nothing. */
+int mvf_align_alpha(const double* kappa, const double* K_NA_spatial, const double* SigmaDiag, int64_t na, double Sp_spatial,
+                    double sigma2, double* alpha, double* model_mul, void* stream);
+size_t mvf_align_workspace_bytes(int64_t na, int64_t nb);
+/* Replaces the reductions of `_update_rigid` (:1312-1318, 1343-1358), `_update_sigma2` (:1427) and `_get_optimal_R`
+ * (:1451-1461), without P.  VnA4: x4 in `dtype` (mvf_apply's output; zeros before the non-rigid update has run); PXB = P
+ * (coordsB - origin) as mvf_assign returns it for xb4 = coordsB - origin (origin: HOST double[3], NULL = 0); extra: optional
+ * device scalar copied to out[50] (mvf_assign's `scalars`).  out (device, all 64 written):
+ *   [0..2] K_NA.coordsA  [3..5] K_NA.VnA  [6..8] K_NB.coordsB  [9] Sp = sum K_NB  [10] sum K_NA  [11] Sp_spatial
+ *   [12] Sp_sigma2  [13] sum K_NA_sigma2 SigmaDiag  [14..16] mu_XA  [17..19] mu_Vn  [20..22] mu_XB  (= [0..8] / Sp; 0 if Sp == 0)
+ *   with xc = coordsA - mu_XA, vc = VnA - mu_Vn, pc = PXB - K_NA (mu_XB - origin) per row:
+ *   [23..31] sum K_NA xc vc^T   [32..40] sum xc pc^T  (= XA_hat^T P XB_hat of :1357; its transpose is `A` of :1461)
+ *   [41..43] sum K_NA xc   [44..46] sum K_NA vc   [47..49] sum pc   [50] extra   [51..63] 0
+ * The second-order sums are taken on rows centred by the device's means; the host moves them to other means (the inlier
+ * terms of :1328-1337) with the first-order centred sums [41..49], which is exact algebra on small numbers.
+ * na == 0 or nb == 0 launches nothing. */
+int mvf_align_moments(const double* coordsA, const void* VnA4, const double* K_NA, const double* K_NA_spatial,
+                      const double* K_NA_sigma2, const double* SigmaDiag, const double* PXB, int64_t na, const double* coordsB,
+                      const double* K_NB, int64_t nb, const double* origin, const double* extra, double* out, void* workspace,
+                      size_t workspace_bytes, mvf_dtype dtype, void* stream);
+/* Replaces: `RnA = coordsA R^T + t` (:1404), `XAHat = VnA + RnA` (:293), `PXB_term` (:1276) and the division that turns it
+ * into the Gram stage's right-hand side.  Rt: HOST double[12] = R row-major, t.  Per cell, in this operation order:
+ *   RnA_d = ((x_0 R[d][0] + x_1 R[d][1]) + x_2 R[d][2]) + t_d;  XAHat_d = VnA_d + RnA_d;  xa4_d = (dtype)(XAHat_d - origin_d);
+ *   PXB_term_d = PXB_d - (RnA_d - origin_d) K_NA;  Y_d = K_NA != 0 ? PXB_term_d / K_NA : 0;  Y4 = (dtype)Y;  Pw = (dtype)K_NA.
+ * Outputs may be NULL (skipped): RnA, XAHat, PXB_term (n x 3 float64), xa4, Y4 (n x 4, dtype), Pw (n, dtype).  VnA4 NULL = 0.
+ * na == 0 launches nothing. */
+int mvf_align_transform(const double* coordsA, const void* VnA4, const double* PXB, const double* K_NA, int64_t na,
+                        const double* Rt, const double* origin, double* RnA, double* XAHat, void* xa4, double* PXB_term,
+                        void* Y4, void* Pw, mvf_dtype dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -629,6 +629,40 @@ class HipKernels:
             _lib.check(self.lib.mvf_assign(*head, *tail), "mvf_assign")
         return out
 
+    # ---- the O(N) glue of the alignment loop (mvf_align.hip): device tensors in, device tensors out ----
+    @_on_device
+    def align_alpha(self, kappa, K_NA_spatial, SigmaDiag, Sp_spatial, sigma2, alpha, model_mul):
+        """alpha and the next assignment's model_mul (float64 (na,) device tensors, overwritten) - mvf_align_alpha."""
+        _lib.check(self.lib.mvf_align_alpha(_ptr(kappa), _ptr(K_NA_spatial), _ptr(SigmaDiag), kappa.shape[0], float(Sp_spatial),
+                                            float(sigma2), _ptr(alpha), _ptr(model_mul), self._stream()), "mvf_align_alpha")
+
+    @staticmethod
+    def _host3(v, n):
+        import ctypes
+
+        return None if v is None else (ctypes.c_double * n)(*[float(x) for x in np.asarray(v, dtype=np.float64).reshape(n)])
+
+    @_on_device
+    def align_moments(self, A, V4, K_NA, K_NA_spatial, K_NA_sigma2, SigmaDiag, PXB, B, K_NB, out, origin=None, extra=None):
+        """The iteration's one block of reductions (mvf_align_moments) into `out` (float64, ALIGN_MOMENT_DOUBLES)."""
+        na, nb = A.shape[0], B.shape[0]
+        need = int(self.lib.mvf_align_workspace_bytes(na, nb))
+        if getattr(self, "_align_ws", None) is None or self._align_ws.numel() < need:
+            self._align_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.mvf_align_moments(_ptr(A), _ptr(V4), _ptr(K_NA), _ptr(K_NA_spatial), _ptr(K_NA_sigma2), _ptr(SigmaDiag),
+                                              _ptr(PXB), na, _ptr(B), _ptr(K_NB), nb, self._host3(origin, 3), _ptr(extra), _ptr(out),
+                                              _ptr(self._align_ws), self._align_ws.numel(), self.cdtype, self._stream()),
+                   "mvf_align_moments")
+
+    @_on_device
+    def align_transform(self, A, V4, PXB, K_NA, R, t, origin=None, RnA=None, XAHat=None, xa4=None, PXB_term=None, Y4=None,
+                        Pw=None):
+        """mvf_align_transform: R (3 x 3), t (3) host; every output is an optional preallocated device tensor."""
+        Rt = self._host3(np.concatenate([np.asarray(R, dtype=np.float64).reshape(9), np.asarray(t, dtype=np.float64).reshape(3)]), 12)
+        _lib.check(self.lib.mvf_align_transform(_ptr(A), _ptr(V4), _ptr(PXB), _ptr(K_NA), A.shape[0], Rt, self._host3(origin, 3),
+                                                _ptr(RnA), _ptr(XAHat), _ptr(xa4), _ptr(PXB_term), _ptr(Y4), _ptr(Pw), self.cdtype,
+                                                self._stream()), "mvf_align_transform")
+
     @staticmethod
     def _affine_buf(affine):
         if affine is None:

@@ -19,7 +19,7 @@ from . import _runtime as _rt
 from .engine import SparseVFCEngine, _consistent_K
 from .vectorfield import vector_field_function
 
-__all__ = ["BA_transform", "update_nonrigid", "update_assignment"]
+__all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate"]
 
 RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
 
@@ -70,6 +70,26 @@ def _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilar
     return XA, XB, LA, LB, codes
 
 
+def _spatial_outlier(sigma2, gamma, samples_s, NA, D):
+    return float(np.power(2 * np.pi * sigma2, D / 2) * (1 - gamma) / (gamma * (samples_s * NA)))  # utils.py:1051-1053
+
+
+def _prepare_layers(k, LA, LB, codes):
+    """Upload and prepare both sides of every layer (mvf_assign_prepare): the operands no iteration changes."""
+    layers = []
+    for A, B, (metric, prob, param) in zip(LA, LB, codes):
+        Xp, a, ld = k.assign_prepare(A, metric, 0)
+        Yp, b, _ = k.assign_prepare(B, metric, 1)
+        layers.append((Xp, Yp, a, b, ld, metric, prob, param))
+    return layers
+
+
+def _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, dense=False):
+    """The device-resident body of update_assignment (and of every iteration of morpho_iterate): device tensors in, the
+    dict of device tensors of HipKernels.assign out."""
+    return k.assign(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier), dense=dense)
+
+
 def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity, probability_type,
                       probability_parameters, sigma2, alpha, SigmaDiag, gamma, samples_s, sigma2_variance=1.0,
                       dtype: str = "float64", device=None, return_P=False, sparse_calculation_mode=False):
@@ -115,15 +135,11 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
             out["P"] = np.zeros((NA, len(XB)))
         return out
     model_mul = al * np.exp(-sd / sigma2)                                                   # morpho_class.py:1087
-    outlier = np.power(2 * np.pi * sigma2, D / 2) * (1 - gamma) / (gamma * (samples_s * NA))  # utils.py:1051-1053
+    outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
     k = _rt._make_kernels(device, dtype)
-    layers = []
-    for A, B, (metric, prob, param) in zip(LA, LB, codes):
-        Xp, a, ld = k.assign_prepare(A, metric, 0)
-        Yp, b, _ = k.assign_prepare(B, metric, 1)
-        layers.append((Xp, Yp, a, b, ld, metric, prob, param))
-    dev = k.assign(k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, float(outlier),
-                   dense=bool(return_P))
+    layers = _prepare_layers(k, LA, LB, codes)
+    dev = _assign_device(k, k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, outlier,
+                         dense=bool(return_P))
     keys = list(names) + ["PXB", "scalars"] + (["P"] if return_P else [])
     host = dict(zip(keys, _rt._to_host(k, [dev[q] for q in keys])))
     out = {q: np.array(host[q], dtype=np.float64) for q in names}
@@ -133,6 +149,33 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
     if return_P:
         out["P"] = np.array(host["P"], dtype=np.float64)
     return out
+
+
+def _nonrigid_solve(k, G, Gamma, reg, R):
+    """The device-resident solve of update_nonrigid (and of morpho_iterate): C = pinv(G + reg Gamma) R with scipy.linalg.pinv's
+    cut-off.  Returns (C (m x 3 float64 device), rcond, lowrank); the decomposition stays in k's workspace for pinv_diag."""
+    m = G.shape[0]
+    f64 = torch.float64
+    C, info, einfo = k.zeros(m, 3, dtype=f64), k.zeros(1, dtype=torch.int32), k.zeros(12, dtype=f64)
+    rcond = m * float(np.finfo(np.float64).eps)
+    lowrank = m >= 1024 and hasattr(k, "solve_minnorm_lr")
+    if lowrank:
+        # rank-revealing factor + Jacobi on its columns (the faster path once the factor drops most columns)
+        k.solve_minnorm_lr(G, Gamma, reg, R, C, info, einfo, rcond=rcond)
+        if int(info.cpu()[0]) != 0:
+            raise _lib.MVFError("update_nonrigid: SigmaInv has non-finite entries")
+        SparseVFCEngine._check_converged(float(einfo.cpu()[0]))
+    else:
+        shift = 2.0 ** -36
+        while True:
+            k.solve_minnorm(G, Gamma, reg, shift, R, C, info, einfo, rcond=rcond)
+            if int(info.cpu()[0]) == 0:
+                SparseVFCEngine._check_converged(float(einfo.cpu()[0]))
+                break
+            shift *= 16.0
+            if shift > 2.0 ** -12:
+                raise _lib.MVFError("update_nonrigid: SigmaInv is not numerically positive semi-definite")
+    return C, rcond, lowrank
 
 
 def update_nonrigid(coordsA, inducing_variables, beta, K_NA, PXB_term, sigma2, lambdaVF, dtype: str = "float64",
@@ -213,25 +256,7 @@ def update_nonrigid(coordsA, inducing_variables, beta, K_NA, PXB_term, sigma2, l
         k.gram(x4_I, torch.ones(n_i, dtype=Pw.dtype, device=k.device), k.to_x4(dXI), c4, float(beta), G_I, R_I)
         k.lincomb3(G, 1.0, G, wg, G_I)
         k.lincomb3(R, 1.0, R, wg, R_I)
-    C, info, einfo = k.zeros(m, 3, dtype=f64), k.zeros(1, dtype=torch.int32), k.zeros(12, dtype=f64)
-    rcond = m * float(np.finfo(np.float64).eps)
-    lowrank = m >= 1024 and hasattr(k, "solve_minnorm_lr")
-    if lowrank:
-        # rank-revealing factor + Jacobi on its columns (the faster path once the factor drops most columns)
-        k.solve_minnorm_lr(G, Gamma, step * ls2, R, C, info, einfo, rcond=rcond)
-        if int(info.cpu()[0]) != 0:
-            raise _lib.MVFError("update_nonrigid: SigmaInv has non-finite entries")
-        SparseVFCEngine._check_converged(float(einfo.cpu()[0]))
-    else:
-        shift = 2.0 ** -36
-        while True:
-            k.solve_minnorm(G, Gamma, step * ls2, shift, R, C, info, einfo, rcond=rcond)
-            if int(info.cpu()[0]) == 0:
-                SparseVFCEngine._check_converged(float(einfo.cpu()[0]))
-                break
-            shift *= 16.0
-            if shift > 2.0 ** -12:
-                raise _lib.MVFError("update_nonrigid: SigmaInv is not numerically positive semi-definite")
+    C, rcond, lowrank = _nonrigid_solve(k, G, Gamma, step * ls2, R)
     V4, _ = k.apply(x4, c4, float(beta), C)
     SigmaInv = _rt._d2h(k, G) + step * ls2 * _rt._d2h(k, Gamma)
     # SigmaDiag = sigma2 diag(U pinv(SigmaInv) U^T) (morpho_class.py:1295-1297) from the decomposition the solve left
@@ -271,3 +296,282 @@ def BA_transform(vecfld, quary_points, deformation_scale: int = 1, dtype: str = 
         vel = vel * scale
         opt = opt * scale + mean_ref
     return hat, vel, opt
+
+
+def _digamma(x):
+    """Digamma for a positive float, the formula of mvf_align_alpha's device function (recurrence up to 10, then the
+    asymptotic series through x^-14) in Python float64: what gamma's update needs once per iteration."""
+    import math
+
+    x = float(x)
+    if not x > 0.0:
+        raise ValueError("digamma is implemented for positive arguments only")
+    s = 0.0
+    while x < 10.0:
+        s += 1.0 / x
+        x += 1.0
+    r = 1.0 / x
+    r2 = r * r
+    p = 1.0 / 12.0
+    for c in (-691.0 / 32760.0, 1.0 / 132.0, -1.0 / 240.0, 1.0 / 252.0, -1.0 / 120.0, 1.0 / 12.0):
+        p = p * r2 + c
+    return ((math.log(x) - 0.5 * r) - p * r2) - s
+
+
+def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type, probability_parameters,
+                       inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, kappa, gamma_a, gamma_b,
+                       partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype, record, SVI_mode, guidance,
+                       sparse_calculation_mode, kernel_type, origin):
+    """Validation of morpho_iterate (no device needed).  Returns the arguments as float64 arrays / floats."""
+    if dtype not in ("float32", "float64"):
+        raise ValueError("dtype must be 'float32' or 'float64'")
+    if SVI_mode:
+        raise NotImplementedError("morpho_iterate: SVI_mode (stochastic batches of B with blended running averages) is not "
+                                  "supported; update_assignment / update_nonrigid(svi=) are the per-batch stages")
+    if guidance is not None and guidance is not False:
+        raise NotImplementedError("morpho_iterate: guidance pairs are not supported (update_nonrigid(guidance=) is the stage)")
+    if kernel_type != "euc":
+        raise NotImplementedError(f"morpho_iterate: kernel_type={kernel_type!r} is not supported (only the Euclidean 'euc' "
+                                  f"kernel; 'geodist' needs the graph distances of the inducing variables)")
+    XA, XB, LA, LB, codes = _assignment_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
+                                                  probability_parameters, sparse_calculation_mode, False)
+    NA, D = XA.shape
+    if NA == 0 or len(XB) == 0:
+        raise ValueError("morpho_iterate: both slices need at least one cell")
+    ctrl = np.asarray(inducing_variables, dtype=np.float64)
+    if ctrl.ndim != 2 or ctrl.shape[1] != D or len(ctrl) == 0:
+        raise AssertionError("X and Y do not have the same number of features.")  # con_K's assertion (utils.py:1150)
+    if int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError("max_iter must be a positive integer")
+    if record not in (False, True, "arrays"):
+        raise ValueError("record must be False, True or 'arrays'")
+    if not (float(sigma2) > 0.0 and float(beta) > 0.0 and float(lambdaVF) >= 0.0):
+        raise ValueError("sigma2 and beta must be positive and lambdaVF non-negative")
+    if not (float(gamma_a) > 0.0 and float(gamma_b) > 0.0 and float(partial_robust_level) > 0.0):
+        raise ValueError("gamma_a, gamma_b and partial_robust_level must be positive")
+    if isinstance(kappa, (float, int)):
+        kap = np.full(NA, float(kappa))
+    elif isinstance(kappa, np.ndarray):
+        kap = np.asarray(kappa, dtype=np.float64).reshape(-1)
+    else:
+        raise ValueError("kappa should be a float or a numpy array.")  # morpho_class.py:722
+    if len(kap) != NA or not np.all(kap > 0.0):
+        raise ValueError("kappa must be positive, a float or one value per A cell")
+    inl = None
+    if inliers is not None:
+        iA, iB, iP = (np.asarray(a, dtype=np.float64) for a in inliers)
+        iP = iP.reshape(-1, 1)
+        if iA.ndim != 2 or iA.shape != iB.shape or iA.shape[1] != D or len(iP) != len(iA) or len(iA) == 0 or not iP.sum() > 0:
+            raise ValueError("inliers must be (inlier_A (k, D), inlier_B (k, D), inlier_P (k,) or (k, 1)) with a positive sum")
+        inl = (iA, iB, iP)
+    if samples_s is None:  # morpho_class.py:738-741
+        samples_s = max(np.prod(XA.max(0) - XA.min(0)), np.prod(XB.max(0) - XB.min(0)))
+    if not float(samples_s) > 0.0:
+        raise ValueError("samples_s must be positive")
+    org = np.zeros(3)
+    if origin is not None:
+        org[:D] = np.asarray(origin, dtype=np.float64).reshape(D)
+    return dict(XA=XA, XB=XB, LA=LA, LB=LB, codes=codes, ctrl=ctrl, kappa=kap, inliers=inl, samples_s=float(samples_s),
+                origin=org, sigma2_end=None if sigma2_end is None else float(sigma2_end))
+
+
+def _rigid_from_block(blk, D, sigma2, inliers, nn_init_weight, R_prev, update_R):
+    """`_update_rigid` (morpho_class.py:1300-1408) from the block of mvf_align_moments, in host float64: the means, the
+    D x D matrix ``A``, its SVD, R and t.  The block's second-order sums are centred on the device's means (K_NA . coordsA /
+    Sp, ...); with inliers the reference's means move by the O(pairs) inlier terms, and the sums are moved with them through
+    the first-order centred sums (exact algebra, include/mvf.h).  The reference's ``mu_XB += ...`` acts in place on the
+    arrays its translation reads afterwards (``mu_XB`` IS ``PXB`` there): the translation's numerator is formed from the
+    augmented sums, as there."""
+    Sp, sumK = blk[9], blk[10]
+    PXA, PVA, PXB = blk[0:D].copy(), blk[3:3 + D].copy(), blk[6:6 + D].copy()
+    deno = Sp
+    w = 0.0
+    if inliers is not None:
+        iA, iB, iP = inliers
+        w = sigma2 * nn_init_weight * Sp / iP.sum()
+        PXB = PXB + w * (iP.T @ iB)[0]
+        PXA = PXA + w * (iP.T @ iA)[0]
+        deno = Sp + w * iP.sum()
+    mu_XB, mu_XA = PXB / deno, PXA / deno
+    dA, dB = np.zeros(3), np.zeros(3)
+    if inliers is not None:  # (without inliers the device's means ARE the reference's: the same sums and the same division)
+        dA[:D], dB[:D] = mu_XA - blk[14:14 + D], mu_XB - blk[20:20 + D]
+    c1, c2, c3 = blk[41:44], blk[44:47], blk[47:50]
+    M1 = blk[23:32].reshape(3, 3) - np.outer(dA, c2)
+    M2 = blk[32:41].reshape(3, 3) - np.outer(dA, c3) - np.outer(c1, dB) + np.outer(dA, dB) * sumK
+    A = -((M1 - M2)[:D, :D]).T
+    if inliers is not None:
+        A = A - w * ((iA - mu_XA) * iP).T.dot(-(iB - mu_XB)).T
+    svdU, _, svdV = np.linalg.svd(A)
+    C = np.eye(D)
+    C[-1, -1] = np.linalg.det(svdU @ svdV)
+    R = (svdU @ C @ svdV) if update_R else R_prev
+    t_num = PXB - PVA - PXA @ R.T
+    if inliers is not None:
+        t_num = t_num + w * (iP.T @ (iB - iA @ R.T))[0]
+    return R, t_num / deno
+
+
+def _embed(R, t):
+    """D x D rotation and D translation as the 3 x 3 / 3 the kernels take (2-D data: the third axis untouched)."""
+    R3, t3 = np.eye(3), np.zeros(3)
+    D = len(t)
+    R3[:D, :D], t3[:D] = R, t
+    return R3, t3
+
+
+def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity, probability_type, probability_parameters,
+                   inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter=0, kappa=1.0, gamma_a=1.0,
+                   gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
+                   update_R=True, dtype: str = "float64", device=None, record=True, origin=None, SVI_mode=False, guidance=None,
+                   sparse_calculation_mode=False, kernel_type="euc"):
+    """The iteration loop of Spateo's pairwise alignment on the MI355X: the non-SVI, dense-path body of
+    ``Morpho_pairwise.run`` (``spateo/alignment/methods/morpho_class.py:280-294``: assignment -> gamma -> alpha -> non-rigid
+    -> rigid -> ``XAHat`` -> sigma2) for ``max_iter`` iterations from the state ``_initialize_variational_variables`` sets
+    (``:700-747``: alpha = 1, gamma = 0.5, ``VnA = 0``, ``XAHat = RnA = coordsA``, ``SigmaDiag = 0``, R = I, ``sigma2_variance``
+    from 1 towards ``partial_robust_level`` by ``_get_anneling_factor`` over 100 iterations), followed by ``_get_optimal_R``
+    (``:1437-1469``) and the ``vecfld`` of ``_wrap_output`` (``:1507-1528``, ``normalize_c=False``).
+
+    Both slices' layers are uploaded and prepared once; between the first upload and the result nothing of size NA or NB
+    crosses the link.  Per iteration the device runs ``mvf_assign``, ``mvf_align_transform``, the non-rigid update's
+    ``mvf_gram`` / ``mvf_solve_minnorm`` / ``mvf_apply`` / ``mvf_pinv_diag`` (from iteration ``nonrigid_start_iter + 1`` on, as
+    ``:289``), ``mvf_align_moments`` and ``mvf_align_alpha``; the host reads one block of 64 float64 (page-locked) next to
+    the solve's status words and does, in float64, the 3 x 3 SVD, gamma with its clamp to [0.01, 0.99] (``:1220-1224``),
+    sigma2 with its floors 1e-3 and, below iteration 100, 1e-2 (``:1426-1435``), and ``sigma2_variance``.
+
+    ``coordsA`` (NA, D) / ``coordsB`` (NB, D), D in {2, 3}, as the caller has normalised them; layers, ``dissimilarity``,
+    ``probability_type``, ``probability_parameters`` as ``update_assignment`` takes them; ``inducing_variables`` (M, D) and
+    ``beta`` as ``update_nonrigid``; ``sigma2`` the initial value (``_init_guess_sigma2`` in the reference).  Defaults are the
+    reference constructor's (``morpho_class.py:133-152``: ``nn_init_weight=1.0``, ``gamma_a = gamma_b = 1.0``, ``kappa=1.0``,
+    ``partial_robust_level=10``); ``kappa`` is a float or an (NA,) array; ``samples_s`` defaults to the larger bounding-box
+    volume (``:738-741``).  ``inliers = (inlier_A, inlier_B, inlier_P)``: the pairs of the coarse alignment (``nn_init``);
+    their terms of ``_update_rigid`` (``:1328-1337, 1352-1368, 1390-1396``) are O(pairs) host float64 work.
+    ``sigma2_end`` replaces sigma2 after the loop (``:296-297``).  ``origin`` (D,), optional and not in the reference: a point
+    near the data that the coordinates handed to the assignment kernel are taken relative to - distances are formed as
+    |x|^2 + |y|^2 - 2 x.y, which loses digits when both slices sit far from the origin; None leaves the operands as
+    ``update_assignment`` has them.  ``record``: True keeps per-iteration ``sigma2``, ``gamma``, ``R``, ``t``, ``Sp`` in
+    ``history``; ``"arrays"`` (debugging: it crosses the link every iteration) also ``alpha``, ``XAHat``, ``VnA``, ``K_NA``,
+    ``Coff``.
+
+    Not supported (``NotImplementedError``): ``SVI_mode``, ``guidance``, ``sparse_calculation_mode``, the ``"label"`` metric,
+    ``kernel_type="geodist"`` (anything but ``"euc"``), and what ``update_assignment`` / ``update_nonrigid`` refuse (more than
+    4 layers, D outside {2, 3}).
+
+    Returns a dict of host float64: ``R``, ``t``, ``Coff``, ``VnA``, ``RnA``, ``XAHat``, ``optimal_R``, ``optimal_t``,
+    ``optimal_RnA``, ``sigma2``, ``gamma``, ``alpha``, ``SigmaDiag``, ``sigma2_variance``, the last assignment's ``K_NA``,
+    ``K_NB``, ``K_NA_spatial``, ``K_NA_sigma2``, ``Sp``, ``Sp_spatial``, ``Sp_sigma2``, ``history`` (if recorded) and
+    ``vecfld``: ``BA_transform(vecfld, coordsA)`` reproduces ``XAHat`` and ``optimal_RnA``.  Two calls give equal bits."""
+    a = _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
+                           probability_parameters, inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter,
+                           kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
+                           record, SVI_mode, guidance, sparse_calculation_mode, kernel_type, origin)
+    XA, XB, ctrl, org = a["XA"], a["XB"], a["ctrl"], a["origin"]
+    NA, D = XA.shape
+    NB, m = len(XB), len(ctrl)
+    beta, lambdaVF, sigma2, samples_s = float(beta), float(lambdaVF), float(sigma2), a["samples_s"]
+    k = _rt._make_kernels(device, dtype)
+    f64 = torch.float64
+    ph = _rt._Phases(k.device)   # {setup, assign, nonrigid, glue, result: seconds} in last_fit_profile() under PROFILE_FITS
+    # ---- uploaded / built once ----
+    layers = _prepare_layers(k, a["LA"], a["LB"], a["codes"])
+    has_origin = bool(np.any(org != 0.0))
+    xa4 = k.to_x4(XA, org[:D] if has_origin else None)       # XAHat of iteration 0 = coordsA, as update_assignment uploads it
+    xb4 = k.to_x4(XB, org[:D] if has_origin else None)
+    A64, B64 = k.h2d_padded(XA, 3, f64), k.h2d_padded(XB, 3, f64)
+    center = ctrl.mean(0)
+    x4c, c4 = k.to_x4(XA, center), k.to_x4(ctrl, center)     # what the Gram / apply / pinv_diag kernels read (update_nonrigid)
+    Gamma = _consistent_K(k, ctrl, center, beta)
+    kap = k.h2d(a["kappa"])
+    # ---- the state that stays on the device ----
+    alpha, model_mul = (torch.ones(NA, dtype=f64, device=k.device) for _ in range(2))   # alpha = 1, SigmaDiag = 0 (:723, :734)
+    SigmaDiag = k.zeros(NA, dtype=f64)
+    V4 = k.zeros(NA, 4)
+    RnA, XAHat, PXB_term = k.empty(NA, 3, dtype=f64), k.empty(NA, 3, dtype=f64), k.empty(NA, 3, dtype=f64)
+    Y4, Pw = k.empty(NA, 4), k.empty(NA)
+    G, Rhs = k.zeros(m, m, dtype=f64), k.zeros(m, 3, dtype=f64)
+    Coff = k.zeros(m, 3, dtype=f64)
+    block = k.empty(_lib.ALIGN_MOMENT_DOUBLES, dtype=f64)
+    R, t = np.eye(D), np.zeros(D)
+    gamma, sigma2_variance = 0.5, 1.0
+    variance_step = float(np.power(float(partial_robust_level) / 1.0, 1.0 / 100))  # _get_anneling_factor (utils.py:1357-1365)
+    nonrigid = False
+    history = {q: [] for q in ("sigma2", "gamma", "R", "t", "Sp")}
+    if record == "arrays":
+        history.update({q: [] for q in ("alpha", "XAHat", "VnA", "K_NA", "Coff")})
+    R3, t3 = _embed(R, t)
+    k.align_transform(A64, V4, None, None, R3, t3, RnA=RnA, XAHat=XAHat)
+    dev = blk = None
+    ph.mark("setup")
+    for it in range(int(max_iter)):
+        outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
+        dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier)
+        ph.mark("assign")
+        if it > nonrigid_start_iter or nonrigid:               # morpho_class.py:289
+            nonrigid = True
+            # PXB_term = P coordsB - RnA K_NA with the RnA of the previous iteration's R, t; Y = PXB_term / K_NA; Pw = K_NA
+            k.align_transform(A64, V4, dev["PXB"], dev["K_NA"], R3, t3, origin=org, PXB_term=PXB_term, Y4=Y4, Pw=Pw)
+            k.gram(x4c, Pw, Y4, c4, beta, G, Rhs)
+            Coff, rcond, lowrank = _nonrigid_solve(k, G, Gamma, sigma2 * lambdaVF, Rhs)
+            V4, _ = k.apply(x4c, c4, beta, Coff)
+            diag = k.pinv_diag(x4c, c4, beta, rcond=rcond, lowrank=lowrank)
+            k.lincomb3(SigmaDiag, sigma2, diag)                # SigmaDiag = sigma2 diag(U pinv(SigmaInv) U^T)  (:1296)
+            ph.mark("nonrigid")
+        k.align_moments(A64, V4, dev["K_NA"], dev["K_NA_spatial"], dev["K_NA_sigma2"], SigmaDiag, dev["PXB"], B64, dev["K_NB"],
+                        block, origin=org, extra=dev["scalars"])
+        (blk,) = k.to_host([block])                            # the iteration's one read: 64 float64, page-locked
+        blk = np.array(blk, dtype=np.float64)
+        Sp, Sp_spatial, Sp_sigma2 = float(blk[9]), float(blk[11]), float(blk[12])
+        if not (Sp > 0.0 and Sp_sigma2 > 0.0 and np.isfinite(blk).all()):
+            raise _lib.MVFError(f"morpho_iterate: iteration {it}: the assignment is empty or not finite (Sp = {Sp}, Sp_sigma2 = "
+                                f"{Sp_sigma2}): no B cell lies within reach of the A slice at sigma2 = {sigma2}")
+        gamma = float(np.exp(_digamma(gamma_a + Sp_spatial) - _digamma(gamma_a + gamma_b + NB)))   # :1220-1222
+        gamma = max(min(gamma, 0.99), 0.01)
+        R, t = _rigid_from_block(blk, D, sigma2, a["inliers"], float(nn_init_weight), R, update_R)
+        R3, t3 = _embed(R, t)
+        k.align_transform(A64, V4, None, None, R3, t3, origin=org, RnA=RnA, XAHat=XAHat, xa4=xa4)
+        sigma2_related = float(blk[50]) / (D * Sp_sigma2)     # :1200
+        sigma2 = max(sigma2_related + float(blk[13]) / Sp_sigma2, 1e-3)                            # :1426-1429
+        sigma2_variance = min(sigma2_variance * variance_step, float(partial_robust_level))        # :1431-1433
+        if it < 100:
+            sigma2 = max(sigma2, 1e-2)
+        # alpha of this iteration (:1250-1252) and the NEXT assignment's model_mul, which needs this iteration's sigma2
+        k.align_alpha(kap, dev["K_NA_spatial"], SigmaDiag, Sp_spatial, sigma2, alpha, model_mul)
+        ph.mark("glue")
+        if record:
+            for q, v in (("sigma2", sigma2), ("gamma", gamma), ("R", R.copy()), ("t", t.copy()), ("Sp", Sp)):
+                history[q].append(v)
+        if record == "arrays":
+            h = k.to_host([alpha, XAHat, V4, dev["K_NA"], Coff], own_pinned=False)
+            for q, v in zip(("alpha", "XAHat", "VnA", "K_NA", "Coff"), h):
+                history[q].append(np.array(v[:, :D] if v.ndim == 2 else v, dtype=np.float64))
+    if a["sigma2_end"] is not None:
+        sigma2 = a["sigma2_end"]
+    # ---- _get_optimal_R (:1437-1469) from the last iteration's block: its means are the device's, A = (sum xc pc^T)^T ----
+    mu_XnA, mu_XnB = blk[14:14 + D], blk[20:20 + D]
+    svdU, _, svdV = np.linalg.svd(blk[32:41].reshape(3, 3)[:D, :D].T)
+    C = np.eye(D)
+    C[-1, -1] = np.linalg.det(svdU @ svdV)
+    optimal_R = svdU @ C @ svdV
+    optimal_t = mu_XnB - mu_XnA @ optimal_R.T
+    oRnA = k.empty(NA, 3, dtype=f64)
+    k.align_transform(A64, None, None, None, *_embed(optimal_R, optimal_t), RnA=oRnA)
+    names = ("K_NA", "K_NB", "K_NA_spatial", "K_NA_sigma2")
+    host = k.to_host([RnA, XAHat, V4, oRnA, Coff, alpha, SigmaDiag] + [dev[q] for q in names], own_pinned=False)
+    out = {q: np.array(v[:, :D], dtype=np.float64) for q, v in zip(("RnA", "XAHat", "VnA", "optimal_RnA", "Coff"), host)}
+    out.update({q: np.array(v, dtype=np.float64) for q, v in zip(("alpha", "SigmaDiag") + names, host[5:])})
+    out.update(R=R, t=t, optimal_R=optimal_R, optimal_t=optimal_t, sigma2=sigma2, gamma=gamma, sigma2_variance=sigma2_variance,
+               Sp=float(blk[9]), Sp_spatial=float(blk[11]), Sp_sigma2=float(blk[12]))
+    if record:
+        out["history"] = {q: np.array(v) for q, v in history.items()}
+    ph.mark("result")
+    ph.done()
+    out["vecfld"] = {
+        "R": R, "t": t, "optimal_R": optimal_R, "optimal_t": optimal_t, "init_R": np.eye(D), "init_t": np.zeros(D), "beta": beta,
+        "Coff": out["Coff"], "inducing_variables": ctrl, "normalize_scales": None, "normalize_means": None, "normalize_c": False,
+        "dissimilarity": list(dissimilarity) if isinstance(dissimilarity, (list, tuple)) else dissimilarity, "sigma2": sigma2,
+        "gamma": gamma, "NA": NA, "sigma2_variance": sigma2_variance, "method": "Spateo",
+        "norm_dict": {"mean_transformed": np.zeros(D), "mean_fixed": np.zeros(D), "scale": 1.0, "scale_transformed": 1.0,
+                      "scale_fixed": 1.0},
+        "kernel_type": "euc",
+    }
+    return out

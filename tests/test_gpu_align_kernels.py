@@ -1,0 +1,240 @@
+"""Kernel-level edge tests of the alignment loop's glue (``csrc/mvf_align.hip``) through the raw C ABI - ``mvf_align_alpha``,
+``mvf_align_moments``, ``mvf_align_transform`` - on ``cuda:0`` in both cell dtypes, at n = 1, the wave and workgroup edges
+(63 / 64 / 65, 255 / 256 / 257), one reduction block +- 1 (1023 / 1024 / 1025 cells) and 70 001 cells (several partial blocks
+and a tail).  tests/_align_loop_case.py holds the NumPy references.
+
+Every call has guard words behind every output and behind the workspace, runs on a workspace filled with NaN bit patterns,
+and is made twice (same bits).  Bounds, none fitted to what the device returned:
+
+* moments: 1e-12 of sum |terms| against the same sums in ``math.fsum``, the second-order sums on rows centred by the means
+  the device formed (read back), the means themselves against the fsum'd sums; for denormal weights an absolute slack of
+  n denormal spacings (each product of a denormal weight is rounded to the denormal grid);
+* transform: the float64 outputs bit for bit against the NumPy evaluation in the operation order the kernel's header
+  states, the cell-dtype stores equal to NumPy's rounding of the float64 value;
+* alpha / model_mul: 1e-12 relative against ``scipy.special.psi``.
+
+Run with ``-s`` for the largest deviation of every family."""
+import numpy as np
+import pytest
+import torch
+
+import _align_loop_case as lc
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+DTYPES = ["float64", "float32"]
+SIZES = [1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 70001]
+VARIANTS = ["zero_K", "one_K", "denormal_K", "kappa_small", "kappa_large", "zero_Ks", "offset", "reflection"]
+SENTINEL = {torch.float64: -1.2345e300, torch.float32: -1.2345e30, torch.uint8: 0xA5}
+GUARD = 1024
+_KERNELS, _WORST = {}, {}
+
+
+def _k(dtype):
+    if dtype not in _KERNELS:
+        from spateo_amd._kernels import HipKernels
+
+        assert torch.cuda.is_available(), "GPU tests need a HIP device"
+        _KERNELS[dtype] = HipKernels(DEV, dtype)
+    return _KERNELS[dtype]
+
+
+def _note(family, dtype, value):
+    _WORST[(family, dtype)] = max(_WORST.get((family, dtype), 0.0), float(value))
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _deviation_table():
+    yield
+    print("\n| family | dtype | largest deviation / bound |\n|---|---|---|")
+    for (fam, dtype), v in sorted(_WORST.items()):
+        print(f"| {fam} | {dtype} | {v:.3g} |")
+
+
+def _dev(a, tdtype=torch.float64):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(tdtype).to(DEV)
+
+
+def _guarded(n, tdtype=torch.float64):
+    return torch.full((n + GUARD,), SENTINEL[tdtype], dtype=tdtype, device=DEV)
+
+
+def _intact(buf, n):
+    return bool((buf[n:] == SENTINEL[buf.dtype]).all())
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({8: np.int64, 4: np.int32, 1: np.uint8}[a.dtype.itemsize])
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
+
+
+def make_inputs(n, variant, seed=0):
+    """One A slice of n cells and a B slice of max(1, 3 n // 4) cells; every array float64 on the host."""
+    rng = np.random.default_rng(1000 * seed + n)
+    nb = max(1, (3 * n) // 4)
+    off = 1e4 if variant == "offset" else 0.0
+    A, B = rng.standard_normal((n, 3)) + off, rng.standard_normal((nb, 3)) + off
+    V = 0.1 * rng.standard_normal((n, 3))
+    K = rng.uniform(0.1, 1.5, n) * (rng.random(n) < 0.9)          # some cells without a partner
+    KB = rng.uniform(0.1, 1.5, nb)
+    if variant == "zero_K":
+        K[:] = 0.0
+    elif variant == "one_K":
+        K[:] = 0.0
+        K[n // 2] = 0.7
+    elif variant == "denormal_K":
+        K = K * 1e-310
+    Ks = np.zeros(n) if variant == "zero_Ks" else rng.uniform(0.0, 2.0, n)
+    K2 = rng.uniform(0.0, 1.0, n)
+    sd = rng.uniform(0.0, 0.1, n)
+    origin = np.full(3, off)
+    PXB = K[:, None] * (B[rng.integers(0, nb, n)] - origin + 0.05 * rng.standard_normal((n, 3)))
+    kappa = np.full(n, {"kappa_small": 1e-3, "kappa_large": 1e3}.get(variant, 1.0)) * rng.uniform(1.0, 1.5, n)
+    th = 0.4
+    R = np.array([[np.cos(th), -np.sin(th), 0], [np.sin(th), np.cos(th), 0], [0, 0, 1.0]]) @ \
+        np.array([[1, 0, 0], [0, np.cos(0.2), -np.sin(0.2)], [0, np.sin(0.2), np.cos(0.2)]])
+    if variant == "reflection":
+        R = R @ np.diag([1.0, 1.0, -1.0])
+    t = rng.standard_normal(3) + off * (1.0 - R.sum(1))
+    return dict(n=n, nb=nb, A=A, B=B, V=V, K=K, KB=KB, Ks=Ks, K2=K2, sd=sd, PXB=PXB, kappa=kappa, R=R, t=t, origin=origin,
+                sigma2=0.3, Sp_spatial=float(Ks.sum()))
+
+
+CASES = [(n, "base") for n in SIZES] + [(n, v) for v in VARIANTS for n in (257, 1025)]
+
+
+def _v4(inp, dtype):
+    """VnA as the x4 tensor of the cell dtype, and widened back to float64 (what the kernels see)."""
+    tdt = torch.float32 if dtype == "float32" else torch.float64
+    V4 = torch.zeros(inp["n"], 4, dtype=tdt, device=DEV)
+    V4[:, :3] = _dev(inp["V"]).to(tdt)
+    return V4, V4[:, :3].to(torch.float64).cpu().numpy()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n, variant", CASES)
+def test_moments(n, variant, dtype):
+    k, lib = _k(dtype), _k(dtype).lib
+    inp = make_inputs(n, variant)
+    nb = inp["nb"]
+    V4, Vw = _v4(inp, dtype)
+    d = {q: _dev(inp[q]) for q in ("A", "B", "K", "KB", "Ks", "K2", "sd", "PXB")}
+    extra = _dev(np.array([3.25]))
+    need = int(lib.mvf_align_workspace_bytes(n, nb))
+    assert need > 0 and need % 8 == 0
+    import ctypes
+
+    org = (ctypes.c_double * 3)(*inp["origin"])
+    outs = []
+    for rep in range(2):
+        ws = torch.full((need // 8 + GUARD,), float("nan"), dtype=torch.float64, device=DEV)
+        ws[need // 8:] = SENTINEL[torch.float64]
+        out = _guarded(64)
+        rc = lib.mvf_align_moments(d["A"].data_ptr(), V4.data_ptr(), d["K"].data_ptr(), d["Ks"].data_ptr(), d["K2"].data_ptr(),
+                                   d["sd"].data_ptr(), d["PXB"].data_ptr(), n, d["B"].data_ptr(), d["KB"].data_ptr(), nb, org,
+                                   extra.data_ptr(), out.data_ptr(), ws.data_ptr(), need, k.cdtype, k._stream())
+        assert rc == 0, lib.mvf_last_error()
+        torch.cuda.synchronize()
+        assert _intact(out, 64) and _intact(ws, need // 8)
+        outs.append(out[:64].cpu().numpy())
+    assert _same_bits(outs[0], outs[1])
+    got = outs[0]
+    assert np.isfinite(got).all() and got[50] == 3.25 and np.all(got[51:] == 0.0)
+    val, mag = lc.moments_reference(inp["A"], Vw, inp["K"], inp["Ks"], inp["K2"], inp["sd"], inp["PXB"], inp["B"], inp["KB"],
+                                    inp["origin"], mu=got[14:23])
+    slack = n * 5e-324 * 64 if variant == "denormal_K" else 0.0   # products of denormal weights land on the denormal grid
+    worst = 0.0
+    for i in list(range(14)) + list(range(23, 50)):
+        bound = 1e-12 * mag[i] + slack
+        assert abs(got[i] - val[i]) <= bound, (i, got[i], val[i], mag[i])
+        worst = max(worst, abs(got[i] - val[i]) / bound if bound > 0 else 0.0)
+    Sp = val[9]
+    for i in range(9):   # the means against the fsum'd first-order sums
+        bound = 2e-12 * mag[i] / Sp + slack / Sp
+        assert abs(got[14 + i] - val[i] / Sp) <= bound, (i, got[14 + i], val[i] / Sp)
+    _note(f"moments {variant}", dtype, worst)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n, variant", CASES)
+def test_transform(n, variant, dtype):
+    import ctypes
+
+    k, lib = _k(dtype), _k(dtype).lib
+    inp = make_inputs(n, variant)
+    tdt, npdt = (torch.float32, np.float32) if dtype == "float32" else (torch.float64, np.float64)
+    V4, Vw = _v4(inp, dtype)
+    d = {q: _dev(inp[q]) for q in ("A", "K", "PXB")}
+    Rt = (ctypes.c_double * 12)(*inp["R"].reshape(9), *inp["t"])
+    org = (ctypes.c_double * 3)(*inp["origin"])
+    runs = []
+    for rep in range(2):
+        bufs = {"RnA": _guarded(3 * n), "XAHat": _guarded(3 * n), "xa4": _guarded(4 * n, tdt), "PXB_term": _guarded(3 * n),
+                "Y4": _guarded(4 * n, tdt), "Pw": _guarded(n, tdt)}
+        rc = lib.mvf_align_transform(d["A"].data_ptr(), V4.data_ptr(), d["PXB"].data_ptr(), d["K"].data_ptr(), n, Rt, org,
+                                     *(bufs[q].data_ptr() for q in ("RnA", "XAHat", "xa4", "PXB_term", "Y4", "Pw")), k.cdtype,
+                                     k._stream())
+        assert rc == 0, lib.mvf_last_error()
+        torch.cuda.synchronize()
+        sizes = {"RnA": 3 * n, "XAHat": 3 * n, "xa4": 4 * n, "PXB_term": 3 * n, "Y4": 4 * n, "Pw": n}
+        assert all(_intact(bufs[q], sizes[q]) for q in bufs)
+        runs.append({q: bufs[q][: sizes[q]].cpu().numpy() for q in bufs})
+    assert all(_same_bits(runs[0][q], runs[1][q]) for q in runs[0])
+    ref = dict(zip(("RnA", "XAHat", "xa4", "PXB_term", "Y4", "Pw"),
+                   lc.transform_reference(inp["A"], Vw, inp["PXB"], inp["K"], inp["R"], inp["t"], inp["origin"], npdt)))
+    for q, r in ref.items():
+        assert _same_bits(runs[0][q], np.ascontiguousarray(r).reshape(-1)), (q, np.abs(runs[0][q] - r.reshape(-1)).max())
+    if variant in ("zero_K", "one_K"):
+        Y = runs[0]["Y4"].reshape(n, 4)
+        assert np.all(Y[inp["K"] == 0] == 0.0)          # update_nonrigid's rule: rows with K_NA == 0 give 0
+    # a subset of the outputs: the others are not touched
+    only = _guarded(3 * n)
+    rc = lib.mvf_align_transform(d["A"].data_ptr(), None, None, None, n, Rt, None, only.data_ptr(), None, None, None, None, None,
+                                 k.cdtype, k._stream())
+    assert rc == 0, lib.mvf_last_error()
+    torch.cuda.synchronize()
+    r0 = lc.transform_reference(inp["A"], np.zeros((n, 3)), inp["PXB"], inp["K"], inp["R"], inp["t"], np.zeros(3), npdt)[0]
+    assert _intact(only, 3 * n) and _same_bits(only[: 3 * n].cpu().numpy(), r0.reshape(-1))
+    _note(f"transform {variant}", dtype, 0.0)
+
+
+@pytest.mark.parametrize("n, variant", CASES)
+def test_alpha(n, variant):
+    k, lib = _k("float64"), _k("float64").lib
+    inp = make_inputs(n, variant)
+    d = {q: _dev(inp[q]) for q in ("kappa", "Ks", "sd")}
+    runs = []
+    for rep in range(2):
+        al, mm = _guarded(n), _guarded(n)
+        rc = lib.mvf_align_alpha(d["kappa"].data_ptr(), d["Ks"].data_ptr(), d["sd"].data_ptr(), n, inp["Sp_spatial"],
+                                 inp["sigma2"], al.data_ptr(), mm.data_ptr(), k._stream())
+        assert rc == 0, lib.mvf_last_error()
+        torch.cuda.synchronize()
+        assert _intact(al, n) and _intact(mm, n)
+        runs.append((al[:n].cpu().numpy(), mm[:n].cpu().numpy()))
+    assert _same_bits(runs[0][0], runs[1][0]) and _same_bits(runs[0][1], runs[1][1])
+    ra, rm = lc.alpha_reference(inp["kappa"], inp["Ks"], inp["sd"], inp["Sp_spatial"], inp["sigma2"])
+    assert np.all(np.abs(runs[0][0] - ra) <= 1e-12 * np.abs(ra)) and np.all(np.abs(runs[0][1] - rm) <= 1e-12 * np.abs(rm))
+    pos = ra > 0
+    if pos.any():
+        _note(f"alpha {variant}", "float64", float((np.abs(runs[0][0] - ra)[pos] / ra[pos]).max() / 1e-12))
+
+
+def test_empty_and_refusals():
+    lib = _k("float64").lib
+    p = torch.zeros(64, dtype=torch.float64, device=DEV).data_ptr()
+    assert lib.mvf_align_workspace_bytes(0, 5) == 0 and lib.mvf_align_workspace_bytes(5, 0) == 0
+    assert lib.mvf_align_alpha(None, None, None, 0, 0.0, 1.0, None, None, None) == 0
+    assert lib.mvf_align_transform(None, None, None, None, 0, None, None, None, None, None, None, None, None, 1, None) == 0
+    assert lib.mvf_align_moments(None, None, None, None, None, None, None, 0, None, None, 3, None, None, None, None, 0, 1, None) == 0
+    assert lib.mvf_align_alpha(p, p, p, 5, 1.0, 0.0, p, p, None) != 0 and b"sigma2" in lib.mvf_last_error()
+    assert lib.mvf_align_moments(p, p, p, p, p, p, p, 5, p, p, 5, None, None, p, p, 8, 1, None) != 0
+    assert b"workspace too small" in lib.mvf_last_error()
+    assert lib.mvf_align_transform(p, None, None, None, 5, None, None, p, None, None, None, None, None, 1, None) != 0
+    assert lib.mvf_align_transform(p, None, None, None, 5, (__import__("ctypes").c_double * 12)(), None, None, None, None, p, None,
+                                   None, 1, None) != 0 and b"need PXB and K_NA" in lib.mvf_last_error()
