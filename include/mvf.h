@@ -551,6 +551,37 @@ int mvf_align_transform(const double* coordsA, const void* VnA4, const double* P
                         const double* Rt, const double* origin, double* RnA, double* XAHat, void* xa4, double* PXB_term,
                         void* Y4, void* Pw, mvf_dtype dtype, void* stream);
 
+/* ---- alignment, SVI mode: one batch of the B slice per iteration, running averages with step_size (:749-760, 894-896) ----
+ * Three additions to the table (mvf_version stays 7 by the rule above).  Float64 arithmetic whatever `dtype`, no atomics,
+ * every output element written by one lane: two calls give bit-identical results. */
+/* Replaces: `self.coordsB[self.batch_idx, :]` and `layer[self.batch_idx]` (:1105-1107, 1149, 1161, 1270, 1315, 1345) for
+ * batch_idx[j] = perm[(start + j) mod nb], j < bs - with start = (-iter bs) mod nb the batch `_update_batch` (:894-896) draws
+ * at iteration `iter` from the initial `batch_perm`.  One launch copies, bit for bit, into contiguous batch buffers: the rows
+ * of xb4 (nb x 4, dtype) -> xb4_out (bs x 4), of coordsB (nb x 3 float64) -> coordsB_out (bs x 3) and, per layer l < nlayers
+ * (0 .. MVF_ASSIGN_MAX_LAYERS host structs; only Yp, b and ld are read), of layers[l].Yp (nb x ld, dtype) -> Yp_out[l]
+ * (bs x ld) and layers[l].b -> b_out[l] (bs float64).  Yp_out / b_out: HOST arrays of nlayers DEVICE pointers.  The prepared
+ * rows move as 16-byte chunks, consecutive lanes on consecutive chunks of a row; xb4, xb4_out, Yp and Yp_out must be 16-byte
+ * aligned and ld a multiple of 16.  perm: DEVICE int32, a permutation of 0 .. nb - 1 - the CALLER guarantees it (the kernel
+ * reads row perm[.] unchecked); 0 <= start < nb, bs <= nb < 2^31.  bs == 0 launches nothing. */
+int mvf_align_gather(const int32_t* perm, int64_t nb, int64_t start, int64_t bs, const void* xb4, void* xb4_out,
+                     const double* coordsB, double* coordsB_out, const mvf_assign_layer* layers, int nlayers,
+                     void* const* Yp_out, double* const* b_out, mvf_dtype dtype, void* stream);
+/* Replaces: `_update_alpha` in SVI mode (:1240-1247) and the `model_mul` of the next `_update_assignment_P` (:1087).
+ *   a_i = exp(psi(kappa_i + K_NA_spatial_i) - psi(kappa_i na + Sp_spatial))        (mvf_align_alpha's expression and psi)
+ *   alpha_i = step < 1 ? (step a_i) + ((1 - step) alpha_i) : a_i;   model_mul_i = alpha_i exp(-SigmaDiag_i / sigma2)
+ * alpha is read and overwritten; Sp_spatial is the BLENDED sum; 0 < step <= 1.  step == 1 gives mvf_align_alpha's bits. */
+int mvf_align_alpha_svi(const double* kappa, const double* K_NA_spatial, const double* SigmaDiag, int64_t na, double Sp_spatial,
+                        double sigma2, double step, double* alpha, double* model_mul, void* stream);
+/* Replaces: the blended `PXB_term` of `_update_nonrigid` in SVI mode (:1270-1274).  Per cell, d = 0, 1, 2, in this order:
+ *   now_d = PXB_d - (RnA_d - origin_d) K_NA;   PXB_term_d = (step now_d) + ((1 - step) PXB_term_d)        (in place, float64)
+ *   Y4_d = (dtype)PXB_term_d, Y4_3 = 0;   Pw = (dtype)K_NA
+ * RnA (na x 3 float64) as mvf_align_transform wrote it; PXB = P (coordsB[batch] - origin); origin: HOST double[3], NULL = 0.
+ * Rows with K_NA == 0 keep the earlier batches' share, so Y4 is the right-hand side for UNIT weights (mvf_gram_stages with
+ * MVF_GRAM_STAGE_RHS | MVF_GRAM_STAGE_REDUCE_RHS, P = 1) and Pw the weights of the Gram matrix.  PXB_term must hold finite values (zeros before the first
+ * non-rigid update, :760); 0 < step <= 1.  na == 0 launches nothing. */
+int mvf_align_transform_svi(const double* RnA, const double* PXB, const double* K_NA, int64_t na, const double* origin,
+                            double step, double* PXB_term, void* Y4, void* Pw, mvf_dtype dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

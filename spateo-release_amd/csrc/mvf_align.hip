@@ -9,6 +9,12 @@
 //   mvf_align_transform  RnA = coordsA R^T + t, XAHat = VnA + RnA (:1404, :293), PXB_term = P coordsB - RnA K_NA (:1276) and
 //                        Y = PXB_term / K_NA, written in the layouts mvf_assign and mvf_gram read
 //
+// and for the SVI mode of that loop (:283-284, 894-896: one batch of B per iteration, running averages with step_size):
+//
+//   mvf_align_gather         the batch's rows of xb4, coordsB and every prepared B layer into contiguous batch buffers
+//   mvf_align_alpha_svi      mvf_align_alpha with the blend of :1240-1247
+//   mvf_align_transform_svi  the blended PXB_term of :1270-1274 and the Gram stage's operands for unit weights
+//
 // All arithmetic is float64 whatever the cell dtype (the library is built with -ffp-contract=off: a * b + c is a rounded
 // product and a rounded sum, never an fma).  No floating-point atomics: every workgroup writes its partial sums to the
 // workspace and ONE workgroup adds them in workgroup order, so two calls give the same bits.
@@ -66,9 +72,94 @@ __global__ __launch_bounds__(256) void align_alpha_kernel(const double* __restri
     model_mul[i] = a * exp(-sd[i] / sigma2);
 }
 
+// the SVI blend of :1240-1247: step * (the value above) + (1 - step) * alpha; step == 1 takes the value itself, so that the
+// bits are mvf_align_alpha's whatever `alpha` held
+__global__ __launch_bounds__(256) void align_alpha_svi_kernel(const double* __restrict__ kappa, const double* __restrict__ Ks,
+                                                              const double* __restrict__ sd, int64_t n, double Sp_spatial,
+                                                              double sigma2, double step, double* __restrict__ alpha,
+                                                              double* __restrict__ model_mul) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double kp = kappa[i];
+    double a = exp(digamma_pos(kp + Ks[i]) - digamma_pos(kp * (double)n + Sp_spatial));
+    if (step < 1.0) a = step * a + (1.0 - step) * alpha[i];
+    alpha[i] = a;
+    model_mul[i] = a * exp(-sd[i] / sigma2);
+}
+
 struct Rt {
     double R[9], t[3], o[3];
 };
+
+struct Org {
+    double o[3];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void align_transform_svi_kernel(const double* __restrict__ RnA, const double* __restrict__ PXB,
+                                                                  const double* __restrict__ K, int64_t n, Org org, double step,
+                                                                  double* __restrict__ PXB_term, T* __restrict__ Y4,
+                                                                  T* __restrict__ Pw) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double k = K[i], rest = 1.0 - step;
+    double pt[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const double now = PXB[3 * i + d] - (RnA[3 * i + d] - org.o[d]) * k;
+        pt[d] = step * now + rest * PXB_term[3 * i + d];
+        PXB_term[3 * i + d] = pt[d];
+    }
+    typename Vec4<T>::type u;
+    u.x = (T)pt[0], u.y = (T)pt[1], u.z = (T)pt[2], u.w = (T)0;
+    *reinterpret_cast<typename Vec4<T>::type*>(Y4 + 4 * i) = u;
+    Pw[i] = (T)k;
+}
+
+// ---- the batch gather --------------------------------------------------------------------------------------------------
+// Segment y of the grid: 0 = the per-row small parts (one lane per batch row: its xb4 vector, its three coordsB values and
+// every layer's row constant b), 1 + l = the prepared rows of layer l, moved as 16-byte chunks with consecutive lanes on
+// consecutive chunks of a row (rows are ld * sizeof(T) bytes, a multiple of 64, and start 16-byte aligned).
+struct GatherArgs {
+    const uint4* ysrc[MVF_ASSIGN_MAX_LAYERS];
+    uint4* ydst[MVF_ASSIGN_MAX_LAYERS];
+    int64_t chunks[MVF_ASSIGN_MAX_LAYERS];   // 16-byte chunks per row
+    const double* bsrc[MVF_ASSIGN_MAX_LAYERS];
+    double* bdst[MVF_ASSIGN_MAX_LAYERS];
+    int nlayers;
+    int x4_chunks;                           // 16-byte chunks per xb4 row: 1 (float32) or 2 (float64)
+};
+
+__device__ __forceinline__ int64_t batch_row(const int32_t* __restrict__ perm, int64_t nb, int64_t start, int64_t j) {
+    int64_t p = start + j;                   // start < nb and j < bs <= nb: one wrap at the most
+    if (p >= nb) p -= nb;
+    return (int64_t)perm[p];
+}
+
+__global__ __launch_bounds__(256) void align_gather_kernel(const int32_t* __restrict__ perm, int64_t nb, int64_t start, int64_t bs,
+                                                           const uint4* __restrict__ xb4, uint4* __restrict__ xb4_out,
+                                                           const double* __restrict__ B, double* __restrict__ B_out,
+                                                           GatherArgs ga) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t first = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.y == 0) {
+        for (int64_t j = first; j < bs; j += stride) {
+            const int64_t r = batch_row(perm, nb, start, j);
+            for (int c = 0; c < ga.x4_chunks; ++c) xb4_out[j * ga.x4_chunks + c] = xb4[r * ga.x4_chunks + c];
+            B_out[3 * j] = B[3 * r], B_out[3 * j + 1] = B[3 * r + 1], B_out[3 * j + 2] = B[3 * r + 2];
+            for (int l = 0; l < ga.nlayers; ++l) ga.bdst[l][j] = ga.bsrc[l][r];
+        }
+        return;
+    }
+    const int l = (int)blockIdx.y - 1;
+    const int64_t cpr = ga.chunks[l], total = bs * cpr;
+    const uint4* __restrict__ src = ga.ysrc[l];
+    uint4* __restrict__ dst = ga.ydst[l];
+    for (int64_t c = first; c < total; c += stride) {
+        const int64_t j = c / cpr, off = c - j * cpr;
+        dst[c] = src[batch_row(perm, nb, start, j) * cpr + off];
+    }
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void align_transform_kernel(const double* __restrict__ A, const T* __restrict__ V4,
@@ -303,6 +394,75 @@ extern "C" int mvf_align_transform(const double* coordsA, const void* VnA4, cons
     else
         hipLaunchKernelGGL(align_transform_kernel<double>, grid, dim3(256), 0, st, coordsA, (const double*)VnA4, PXB, K_NA, na, rt,
                            RnA, XAHat, (double*)xa4, PXB_term, (double*)Y4, (double*)Pw);
+    MVF_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mvf_align_gather(const int32_t* perm, int64_t nb, int64_t start, int64_t bs, const void* xb4, void* xb4_out,
+                                const double* coordsB, double* coordsB_out, const mvf_assign_layer* layers, int nlayers,
+                                void* const* Yp_out, double* const* b_out, mvf_dtype dtype, void* stream) {
+    if (bs == 0) return 0;
+    MVF_REQUIRE(nb > 0 && nb < ((int64_t)1 << 31), "mvf_align_gather: bad cell count");
+    MVF_REQUIRE(bs > 0 && bs <= nb && start >= 0 && start < nb, "mvf_align_gather: need 0 <= start < nb and 0 <= bs <= nb");
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "mvf_align_gather: bad dtype %d", (int)dtype);
+    MVF_REQUIRE(nlayers >= 0 && nlayers <= MVF_ASSIGN_MAX_LAYERS, "mvf_align_gather: 0 .. %d layers, got %d",
+                MVF_ASSIGN_MAX_LAYERS, nlayers);
+    MVF_REQUIRE(perm && xb4 && xb4_out && coordsB && coordsB_out && (nlayers == 0 || (layers && Yp_out && b_out)),
+                "mvf_align_gather: null pointer");
+    const int64_t dsize = dtype == MVF_F32 ? 4 : 8;
+    GatherArgs ga;
+    ga.nlayers = nlayers, ga.x4_chunks = (int)(4 * dsize / 16);
+    int64_t most = bs;
+    for (int l = 0; l < MVF_ASSIGN_MAX_LAYERS; ++l) {
+        ga.ysrc[l] = nullptr, ga.ydst[l] = nullptr, ga.bsrc[l] = nullptr, ga.bdst[l] = nullptr, ga.chunks[l] = 0;
+        if (l >= nlayers) continue;
+        MVF_REQUIRE(layers[l].Yp && layers[l].b && Yp_out[l] && b_out[l], "mvf_align_gather: layer %d: null pointer", l);
+        MVF_REQUIRE(layers[l].ld > 0 && layers[l].ld % 16 == 0, "mvf_align_gather: layer %d: ld = %lld is not a positive multiple of 16",
+                    l, (long long)layers[l].ld);
+        MVF_REQUIRE((((uintptr_t)layers[l].Yp | (uintptr_t)Yp_out[l]) & 15) == 0, "mvf_align_gather: layer %d: rows not 16-byte aligned", l);
+        ga.ysrc[l] = (const uint4*)layers[l].Yp, ga.ydst[l] = (uint4*)Yp_out[l];
+        ga.bsrc[l] = layers[l].b, ga.bdst[l] = b_out[l];
+        ga.chunks[l] = layers[l].ld * dsize / 16;
+        most = std::max(most, bs * ga.chunks[l]);
+    }
+    MVF_REQUIRE((((uintptr_t)xb4 | (uintptr_t)xb4_out) & 15) == 0, "mvf_align_gather: xb4 not 16-byte aligned");
+    const unsigned gx = (unsigned)std::min<int64_t>(4096, cdiv(most, 256));
+    hipLaunchKernelGGL(align_gather_kernel, dim3(gx, (unsigned)(1 + nlayers)), dim3(256), 0, (hipStream_t)stream, perm, nb, start, bs,
+                       (const uint4*)xb4, (uint4*)xb4_out, coordsB, coordsB_out, ga);
+    MVF_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mvf_align_alpha_svi(const double* kappa, const double* K_NA_spatial, const double* SigmaDiag, int64_t na,
+                                   double Sp_spatial, double sigma2, double step, double* alpha, double* model_mul, void* stream) {
+    if (na == 0) return 0;
+    MVF_REQUIRE(na > 0 && cdiv(na, 256) < ((int64_t)1 << 31), "mvf_align_alpha_svi: bad cell count");
+    MVF_REQUIRE(sigma2 > 0.0 && Sp_spatial >= 0.0, "mvf_align_alpha_svi: need sigma2 > 0 and Sp_spatial >= 0");
+    MVF_REQUIRE(step > 0.0 && step <= 1.0, "mvf_align_alpha_svi: need 0 < step <= 1");
+    MVF_REQUIRE(kappa && K_NA_spatial && SigmaDiag && alpha && model_mul, "mvf_align_alpha_svi: null pointer");
+    hipLaunchKernelGGL(align_alpha_svi_kernel, dim3((unsigned)cdiv(na, 256)), dim3(256), 0, (hipStream_t)stream, kappa, K_NA_spatial,
+                       SigmaDiag, na, Sp_spatial, sigma2, step, alpha, model_mul);
+    MVF_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mvf_align_transform_svi(const double* RnA, const double* PXB, const double* K_NA, int64_t na, const double* origin,
+                                       double step, double* PXB_term, void* Y4, void* Pw, mvf_dtype dtype, void* stream) {
+    if (na == 0) return 0;
+    MVF_REQUIRE(na > 0 && cdiv(na, 256) < ((int64_t)1 << 31), "mvf_align_transform_svi: bad cell count");
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "mvf_align_transform_svi: bad dtype %d", (int)dtype);
+    MVF_REQUIRE(step > 0.0 && step <= 1.0, "mvf_align_transform_svi: need 0 < step <= 1");
+    MVF_REQUIRE(RnA && PXB && K_NA && PXB_term && Y4 && Pw, "mvf_align_transform_svi: null pointer");
+    Org org;
+    for (int i = 0; i < 3; ++i) org.o[i] = origin ? origin[i] : 0.0;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)cdiv(na, 256));
+    if (dtype == MVF_F32)
+        hipLaunchKernelGGL(align_transform_svi_kernel<float>, grid, dim3(256), 0, st, RnA, PXB, K_NA, na, org, step, PXB_term,
+                           (float*)Y4, (float*)Pw);
+    else
+        hipLaunchKernelGGL(align_transform_svi_kernel<double>, grid, dim3(256), 0, st, RnA, PXB, K_NA, na, org, step, PXB_term,
+                           (double*)Y4, (double*)Pw);
     MVF_LAUNCH_CHECK();
     return 0;
 }

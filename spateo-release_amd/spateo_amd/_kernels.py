@@ -663,6 +663,42 @@ class HipKernels:
                                                 _ptr(RnA), _ptr(XAHat), _ptr(xa4), _ptr(PXB_term), _ptr(Y4), _ptr(Pw), self.cdtype,
                                                 self._stream()), "mvf_align_transform")
 
+    # ---- the SVI mode of the loop ----
+    @_on_device
+    def align_gather(self, perm, start, bs, xb4, B, layers, xb4_out, B_out, Yp_out, b_out):
+        """mvf_align_gather: the rows perm[(start + j) mod nb], j < bs, of xb4, B (nb x 3 float64) and every layer's Yp / b
+        into the preallocated batch buffers.  perm: device int32, a permutation of range(nb) (the caller's guarantee)."""
+        nb = xb4.shape[0]
+        if perm.dtype != torch.int32 or perm.shape != (nb,) or B.shape != (nb, 3):
+            raise ValueError("align_gather: perm must be int32 (nb,) and B (nb, 3)")
+        if xb4_out.shape[0] < bs or B_out.shape[0] < bs or len(Yp_out) != len(layers) or len(b_out) != len(layers):
+            raise ValueError("align_gather: the batch buffers do not fit the batch")
+        arr = (_lib.AssignLayer * max(len(layers), 1))()
+        for s, (_, Yp, _, b, ld, *_) , Yo, bo in zip(arr, layers, Yp_out, b_out):
+            if Yp.shape != (nb, ld) or b.shape != (nb,) or Yo.shape[0] < bs or Yo.shape[1] != ld or bo.shape[0] < bs:
+                raise ValueError("align_gather: a layer's buffers do not fit")
+            s.Yp, s.b, s.ld = _ptr(Yp), _ptr(b), int(ld)
+        import ctypes
+
+        vp = ctypes.c_void_p * max(len(layers), 1)
+        _lib.check(self.lib.mvf_align_gather(_ptr(perm), nb, int(start), int(bs), _ptr(xb4), _ptr(xb4_out), _ptr(B), _ptr(B_out),
+                                             arr, len(layers), vp(*[_ptr(t) for t in Yp_out]), vp(*[_ptr(t) for t in b_out]),
+                                             self.cdtype, self._stream()), "mvf_align_gather")
+
+    @_on_device
+    def align_alpha_svi(self, kappa, K_NA_spatial, SigmaDiag, Sp_spatial, sigma2, step, alpha, model_mul):
+        """mvf_align_alpha_svi: alpha <- step exp(...) + (1 - step) alpha (in place) and the next model_mul."""
+        _lib.check(self.lib.mvf_align_alpha_svi(_ptr(kappa), _ptr(K_NA_spatial), _ptr(SigmaDiag), kappa.shape[0], float(Sp_spatial),
+                                                float(sigma2), float(step), _ptr(alpha), _ptr(model_mul), self._stream()),
+                   "mvf_align_alpha_svi")
+
+    @_on_device
+    def align_transform_svi(self, RnA, PXB, K_NA, step, PXB_term, Y4, Pw, origin=None):
+        """mvf_align_transform_svi: PXB_term <- step (PXB - (RnA - origin) K_NA) + (1 - step) PXB_term in place, Y4 / Pw."""
+        _lib.check(self.lib.mvf_align_transform_svi(_ptr(RnA), _ptr(PXB), _ptr(K_NA), RnA.shape[0], self._host3(origin, 3),
+                                                    float(step), _ptr(PXB_term), _ptr(Y4), _ptr(Pw), self.cdtype, self._stream()),
+                   "mvf_align_transform_svi")
+
     @staticmethod
     def _affine_buf(affine):
         if affine is None:

@@ -116,6 +116,10 @@ SIGNATURES = {
     "mvf_align_moments": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i64, C.POINTER(C.c_double), _p, _p, _p, _sz, _i, _p]),
     "mvf_align_transform": (_i, [_p, _p, _p, _p, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), _p, _p, _p, _p, _p, _p, _i,
                                  _p]),
+    "mvf_align_gather": (_i, [_p, _i64, _i64, _i64, _p, _p, _p, _p, C.POINTER(AssignLayer), _i, C.POINTER(_p), C.POINTER(_p), _i,
+                              _p]),
+    "mvf_align_alpha_svi": (_i, [_p, _p, _p, _i64, _d, _d, _d, _p, _p, _p]),
+    "mvf_align_transform_svi": (_i, [_p, _p, _p, _i64, C.POINTER(C.c_double), _d, _p, _p, _p, _i, _p]),
 }
 
 _lib = None

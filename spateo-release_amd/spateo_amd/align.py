@@ -19,7 +19,7 @@ from . import _runtime as _rt
 from .engine import SparseVFCEngine, _consistent_K
 from .vectorfield import vector_field_function
 
-__all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate"]
+__all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate", "morpho_iterate_svi"]
 
 RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
 
@@ -326,8 +326,8 @@ def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilari
     if dtype not in ("float32", "float64"):
         raise ValueError("dtype must be 'float32' or 'float64'")
     if SVI_mode:
-        raise NotImplementedError("morpho_iterate: SVI_mode (stochastic batches of B with blended running averages) is not "
-                                  "supported; update_assignment / update_nonrigid(svi=) are the per-batch stages")
+        raise NotImplementedError("morpho_iterate: SVI_mode (stochastic batches of B with blended running averages) is what "
+                                  "morpho_iterate_svi runs; this function is the SVI_mode=False loop")
     if guidance is not None and guidance is not False:
         raise NotImplementedError("morpho_iterate: guidance pairs are not supported (update_nonrigid(guidance=) is the stage)")
     if kernel_type != "euc":
@@ -375,14 +375,35 @@ def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilari
                 origin=org, sigma2_end=None if sigma2_end is None else float(sigma2_end))
 
 
-def _rigid_from_block(blk, D, sigma2, inliers, nn_init_weight, R_prev, update_R):
+def _moved_sums(blk, D, mu_XA, mu_Vn, mu_XB, move_Vn):
+    """The block's centred second-order sums moved from the device's means (blk[14:23]) to the means given, through the
+    first-order centred sums (exact algebra, include/mvf.h): (sum K_NA xc vc^T, sum xc pc^T) as 3 x 3."""
+    dA, dV, dB = np.zeros(3), np.zeros(3), np.zeros(3)
+    dA[:D], dB[:D] = mu_XA - blk[14:14 + D], mu_XB - blk[20:20 + D]
+    sumK = blk[10]
+    c1, c2, c3 = blk[41:44], blk[44:47], blk[47:50]
+    M1 = blk[23:32].reshape(3, 3) - np.outer(dA, c2)
+    if move_Vn:
+        dV[:D] = mu_Vn - blk[17:17 + D]
+        M1 = M1 - np.outer(c1, dV) + np.outer(dA, dV) * sumK
+    M2 = blk[32:41].reshape(3, 3) - np.outer(dA, c3) - np.outer(c1, dB) + np.outer(dA, dB) * sumK
+    return M1, M2
+
+
+def _rigid_from_block(blk, D, sigma2, inliers, nn_init_weight, R_prev, update_R, Sp_blend=None, step=1.0, t_prev=None):
     """`_update_rigid` (morpho_class.py:1300-1408) from the block of mvf_align_moments, in host float64: the means, the
     D x D matrix ``A``, its SVD, R and t.  The block's second-order sums are centred on the device's means (K_NA . coordsA /
     Sp, ...); with inliers the reference's means move by the O(pairs) inlier terms, and the sums are moved with them through
     the first-order centred sums (exact algebra, include/mvf.h).  The reference's ``mu_XB += ...`` acts in place on the
     arrays its translation reads afterwards (``mu_XB`` IS ``PXB`` there): the translation's numerator is formed from the
-    augmented sums, as there."""
-    Sp, sumK = blk[9], blk[10]
+    augmented sums, as there.
+
+    ``Sp_blend`` (SVI): the running ``Sp`` that the reference divides this batch's sums by (``:1321, 1339-1341, 1382``) and
+    weighs the inliers with - the means differ from the device's by ``Sp_now / Sp_blend``, the same move with another
+    ``mu`` (and ``mu_Vn`` moves too); ``step < 1`` blends R before the translation reads it and t afterwards
+    (``:1375-1376, 1399-1400``)."""
+    svi = Sp_blend is not None
+    Sp = Sp_blend if svi else blk[9]
     PXA, PVA, PXB = blk[0:D].copy(), blk[3:3 + D].copy(), blk[6:6 + D].copy()
     deno = Sp
     w = 0.0
@@ -393,12 +414,10 @@ def _rigid_from_block(blk, D, sigma2, inliers, nn_init_weight, R_prev, update_R)
         PXA = PXA + w * (iP.T @ iA)[0]
         deno = Sp + w * iP.sum()
     mu_XB, mu_XA = PXB / deno, PXA / deno
-    dA, dB = np.zeros(3), np.zeros(3)
-    if inliers is not None:  # (without inliers the device's means ARE the reference's: the same sums and the same division)
-        dA[:D], dB[:D] = mu_XA - blk[14:14 + D], mu_XB - blk[20:20 + D]
-    c1, c2, c3 = blk[41:44], blk[44:47], blk[47:50]
-    M1 = blk[23:32].reshape(3, 3) - np.outer(dA, c2)
-    M2 = blk[32:41].reshape(3, 3) - np.outer(dA, c3) - np.outer(c1, dB) + np.outer(dA, dB) * sumK
+    if svi or inliers is not None:
+        M1, M2 = _moved_sums(blk, D, mu_XA, PVA / Sp, mu_XB, svi)
+    else:  # (the device's means ARE the reference's: the same sums and the same division)
+        M1, M2 = blk[23:32].reshape(3, 3), blk[32:41].reshape(3, 3)
     A = -((M1 - M2)[:D, :D]).T
     if inliers is not None:
         A = A - w * ((iA - mu_XA) * iP).T.dot(-(iB - mu_XB)).T
@@ -406,10 +425,31 @@ def _rigid_from_block(blk, D, sigma2, inliers, nn_init_weight, R_prev, update_R)
     C = np.eye(D)
     C[-1, -1] = np.linalg.det(svdU @ svdV)
     R = (svdU @ C @ svdV) if update_R else R_prev
+    if svi and update_R and step < 1:
+        R = step * R + (1 - step) * R_prev
     t_num = PXB - PVA - PXA @ R.T
     if inliers is not None:
         t_num = t_num + w * (iP.T @ (iB - iA @ R.T))[0]
-    return R, t_num / deno
+    t = t_num / deno
+    if svi and step < 1:
+        t = step * t + (1 - step) * t_prev
+    return R, t
+
+
+def _optimal_from_block(blk, D, Sp_blend=None):
+    """`_get_optimal_R` (:1437-1469) from a block: A = (sum xc pc^T)^T on the means K_NA . coordsA / Sp, K_NB . coordsB / Sp -
+    the device's, or (SVI without the final full assignment) the last batch's sums over the running ``Sp``."""
+    if Sp_blend is None:
+        mu_XnA, mu_XnB = blk[14:14 + D], blk[20:20 + D]
+        M2 = blk[32:41].reshape(3, 3)
+    else:
+        mu_XnA, mu_XnB = blk[0:D] / Sp_blend, blk[6:6 + D] / Sp_blend
+        _, M2 = _moved_sums(blk, D, mu_XnA, None, mu_XnB, False)
+    svdU, _, svdV = np.linalg.svd(M2[:D, :D].T)
+    C = np.eye(D)
+    C[-1, -1] = np.linalg.det(svdU @ svdV)
+    optimal_R = svdU @ C @ svdV
+    return optimal_R, mu_XnB - mu_XnA @ optimal_R.T
 
 
 def _embed(R, t):
@@ -453,7 +493,7 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     ``history``; ``"arrays"`` (debugging: it crosses the link every iteration) also ``alpha``, ``XAHat``, ``VnA``, ``K_NA``,
     ``Coff``.
 
-    Not supported (``NotImplementedError``): ``SVI_mode``, ``guidance``, ``sparse_calculation_mode``, the ``"label"`` metric,
+    Not supported (``NotImplementedError``): ``SVI_mode`` (``morpho_iterate_svi`` runs it), ``guidance``, ``sparse_calculation_mode``, the ``"label"`` metric,
     ``kernel_type="geodist"`` (anything but ``"euc"``), and what ``update_assignment`` / ``update_nonrigid`` refuse (more than
     4 layers, D outside {2, 3}).
 
@@ -465,6 +505,14 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
                            probability_parameters, inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter,
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
                            record, SVI_mode, guidance, sparse_calculation_mode, kernel_type, origin)
+    return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
+                    partial_robust_level, nn_init_weight, update_R, dtype, device, record)
+
+
+def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b, partial_robust_level,
+             nn_init_weight, update_R, dtype, device, record, svi=None):
+    """The loop of morpho_iterate and, with ``svi = dict(batch_size=, batch_perm= (int32, validated), return_mapping=)``, of
+    morpho_iterate_svi, on validated arguments ``a`` (_iterate_arguments)."""
     XA, XB, ctrl, org = a["XA"], a["XB"], a["ctrl"], a["origin"]
     NA, D = XA.shape
     NB, m = len(XB), len(ctrl)
@@ -486,8 +534,24 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     alpha, model_mul = (torch.ones(NA, dtype=f64, device=k.device) for _ in range(2))   # alpha = 1, SigmaDiag = 0 (:723, :734)
     SigmaDiag = k.zeros(NA, dtype=f64)
     V4 = k.zeros(NA, 4)
-    RnA, XAHat, PXB_term = k.empty(NA, 3, dtype=f64), k.empty(NA, 3, dtype=f64), k.empty(NA, 3, dtype=f64)
     Y4, Pw = k.empty(NA, 4), k.empty(NA)
+    Pw_dtype = Pw.dtype
+    RnA, XAHat, PXB_term = k.empty(NA, 3, dtype=f64), k.empty(NA, 3, dtype=f64), k.empty(NA, 3, dtype=f64)
+    if svi is not None:
+        # the batch schedule (:894-896) follows from the initial permutation: batch_idx[j] = perm[(j - it bs) mod NB]; the
+        # permutation is uploaded once and every batch is gathered on the device into these buffers
+        bs, NB_eff = int(svi["batch_size"]), int(svi["batch_size"])
+        perm = k.h2d(svi["batch_perm"])
+        xb4_b, B64_b = k.empty(bs, 4), k.empty(bs, 3, dtype=f64)
+        Yp_b, b_b = [k.empty(bs, L[4]) for L in layers], [k.empty(bs, dtype=f64) for L in layers]
+        layers_b = [(L[0], Yb, L[2], bb) + tuple(L[4:]) for L, Yb, bb in zip(layers, Yp_b, b_b)]
+        PXB_term.zero_()                                       # the running PXB_term and SigmaInv start at 0 (:759-760)
+        S_run = k.zeros(m, m, dtype=f64)
+        ones = torch.ones(NA, dtype=Pw_dtype, device=k.device)
+        Sp_run = Sp_spatial_run = Sp_sigma2_run = 0.0
+        step = 1.0
+    else:
+        NB_eff = NB
     G, Rhs = k.zeros(m, m, dtype=f64), k.zeros(m, 3, dtype=f64)
     Coff = k.zeros(m, 3, dtype=f64)
     block = k.empty(_lib.ALIGN_MOMENT_DOUBLES, dtype=f64)
@@ -495,7 +559,7 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     gamma, sigma2_variance = 0.5, 1.0
     variance_step = float(np.power(float(partial_robust_level) / 1.0, 1.0 / 100))  # _get_anneling_factor (utils.py:1357-1365)
     nonrigid = False
-    history = {q: [] for q in ("sigma2", "gamma", "R", "t", "Sp")}
+    history = {q: [] for q in ("sigma2", "gamma", "R", "t", "Sp") + (("step_size",) if svi is not None else ())}
     if record == "arrays":
         history.update({q: [] for q in ("alpha", "XAHat", "VnA", "K_NA", "Coff")})
     R3, t3 = _embed(R, t)
@@ -504,9 +568,30 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     ph.mark("setup")
     for it in range(int(max_iter)):
         outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
-        dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier)
+        if svi is not None:
+            step = min(1.0, 10.0 / (it + 1.0))                 # :894, SVI_deacy = 10
+            k.align_gather(perm, (-it * bs) % NB, bs, xb4, B64, layers, xb4_b, B64_b, Yp_b, b_b)
+            dev = _assign_device(k, xa4, xb4_b, layers_b, model_mul, sigma2, sigma2_variance, outlier)
+        else:
+            dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier)
         ph.mark("assign")
-        if it > nonrigid_start_iter or nonrigid:               # morpho_class.py:289
+        if (it > nonrigid_start_iter or nonrigid) and svi is not None:
+            nonrigid = True
+            # PXB_term <- step (P coordsB[batch] - RnA K_NA) + (1 - step) PXB_term; rows without a partner in THIS batch keep the
+            # earlier batches' share, so the right-hand side is U^T PXB_term with unit weights (:1270-1279)
+            k.align_transform_svi(RnA, dev["PXB"], dev["K_NA"], step, PXB_term, Y4, Pw, origin=org)
+            k.gram(x4c, Pw, Y4, c4, beta, G, Rhs, tiles_only=True)
+            k.gram(x4c, ones, Y4, c4, beta, G, Rhs, rhs_only=True)
+            # SigmaInv <- step (sigma2 lambdaVF Gamma + U^T diag(K_NA) U) + (1 - step) SigmaInv (:1273): G takes the blend
+            # without the regulariser, which enters the solve as (step sigma2 lambdaVF) Gamma and the stored value after it
+            k.lincomb3(G, step, G, 1.0 - step, S_run)
+            Coff, rcond, lowrank = _nonrigid_solve(k, G, Gamma, step * sigma2 * lambdaVF, Rhs)
+            k.lincomb3(S_run, 1.0, G, step * sigma2 * lambdaVF, Gamma)
+            V4, _ = k.apply(x4c, c4, beta, Coff)
+            diag = k.pinv_diag(x4c, c4, beta, rcond=rcond, lowrank=lowrank)
+            k.lincomb3(SigmaDiag, sigma2, diag)
+            ph.mark("nonrigid")
+        elif it > nonrigid_start_iter or nonrigid:             # morpho_class.py:289
             nonrigid = True
             # PXB_term = P coordsB - RnA K_NA with the RnA of the previous iteration's R, t; Y = PXB_term / K_NA; Pw = K_NA
             k.align_transform(A64, V4, dev["PXB"], dev["K_NA"], R3, t3, origin=org, PXB_term=PXB_term, Y4=Y4, Pw=Pw)
@@ -516,17 +601,25 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
             diag = k.pinv_diag(x4c, c4, beta, rcond=rcond, lowrank=lowrank)
             k.lincomb3(SigmaDiag, sigma2, diag)                # SigmaDiag = sigma2 diag(U pinv(SigmaInv) U^T)  (:1296)
             ph.mark("nonrigid")
-        k.align_moments(A64, V4, dev["K_NA"], dev["K_NA_spatial"], dev["K_NA_sigma2"], SigmaDiag, dev["PXB"], B64, dev["K_NB"],
-                        block, origin=org, extra=dev["scalars"])
+        k.align_moments(A64, V4, dev["K_NA"], dev["K_NA_spatial"], dev["K_NA_sigma2"], SigmaDiag, dev["PXB"],
+                        B64 if svi is None else B64_b, dev["K_NB"], block, origin=org, extra=dev["scalars"])
         (blk,) = k.to_host([block])                            # the iteration's one read: 64 float64, page-locked
         blk = np.array(blk, dtype=np.float64)
         Sp, Sp_spatial, Sp_sigma2 = float(blk[9]), float(blk[11]), float(blk[12])
+        if svi is not None:                                    # :1178-1181
+            Sp_run = Sp = step * Sp + (1 - step) * Sp_run
+            Sp_spatial_run = Sp_spatial = step * Sp_spatial + (1 - step) * Sp_spatial_run
+            Sp_sigma2_run = Sp_sigma2 = step * Sp_sigma2 + (1 - step) * Sp_sigma2_run
         if not (Sp > 0.0 and Sp_sigma2 > 0.0 and np.isfinite(blk).all()):
             raise _lib.MVFError(f"morpho_iterate: iteration {it}: the assignment is empty or not finite (Sp = {Sp}, Sp_sigma2 = "
                                 f"{Sp_sigma2}): no B cell lies within reach of the A slice at sigma2 = {sigma2}")
-        gamma = float(np.exp(_digamma(gamma_a + Sp_spatial) - _digamma(gamma_a + gamma_b + NB)))   # :1220-1222
+        gamma = float(np.exp(_digamma(gamma_a + Sp_spatial) - _digamma(gamma_a + gamma_b + NB_eff)))   # :1214-1222
         gamma = max(min(gamma, 0.99), 0.01)
-        R, t = _rigid_from_block(blk, D, sigma2, a["inliers"], float(nn_init_weight), R, update_R)
+        if svi is None:
+            R, t = _rigid_from_block(blk, D, sigma2, a["inliers"], float(nn_init_weight), R, update_R)
+        else:
+            R, t = _rigid_from_block(blk, D, sigma2, a["inliers"], float(nn_init_weight), R, update_R, Sp_blend=Sp, step=step,
+                                     t_prev=t)
         R3, t3 = _embed(R, t)
         k.align_transform(A64, V4, None, None, R3, t3, origin=org, RnA=RnA, XAHat=XAHat, xa4=xa4)
         sigma2_related = float(blk[50]) / (D * Sp_sigma2)     # :1200
@@ -535,24 +628,38 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
         if it < 100:
             sigma2 = max(sigma2, 1e-2)
         # alpha of this iteration (:1250-1252) and the NEXT assignment's model_mul, which needs this iteration's sigma2
-        k.align_alpha(kap, dev["K_NA_spatial"], SigmaDiag, Sp_spatial, sigma2, alpha, model_mul)
+        if svi is None:
+            k.align_alpha(kap, dev["K_NA_spatial"], SigmaDiag, Sp_spatial, sigma2, alpha, model_mul)
+        else:                                                  # :1240-1247, with the blended Sp_spatial
+            k.align_alpha_svi(kap, dev["K_NA_spatial"], SigmaDiag, Sp_spatial, sigma2, step, alpha, model_mul)
         ph.mark("glue")
         if record:
             for q, v in (("sigma2", sigma2), ("gamma", gamma), ("R", R.copy()), ("t", t.copy()), ("Sp", Sp)):
                 history[q].append(v)
+            if svi is not None:
+                history["step_size"].append(step)
         if record == "arrays":
             h = k.to_host([alpha, XAHat, V4, dev["K_NA"], Coff], own_pinned=False)
             for q, v in zip(("alpha", "XAHat", "VnA", "K_NA", "Coff"), h):
                 history[q].append(np.array(v[:, :D] if v.ndim == 2 else v, dtype=np.float64))
     if a["sigma2_end"] is not None:
         sigma2 = a["sigma2_end"]
-    # ---- _get_optimal_R (:1437-1469) from the last iteration's block: its means are the device's, A = (sum xc pc^T)^T ----
-    mu_XnA, mu_XnB = blk[14:14 + D], blk[20:20 + D]
-    svdU, _, svdV = np.linalg.svd(blk[32:41].reshape(3, 3)[:D, :D].T)
-    C = np.eye(D)
-    C[-1, -1] = np.linalg.det(svdU @ svdV)
-    optimal_R = svdU @ C @ svdV
-    optimal_t = mu_XnB - mu_XnA @ optimal_R.T
+    if svi is not None and svi["return_mapping"]:
+        # the full, non-SVI assignment on the final state (:300-302): K_NA, K_NB and the Sp* of the whole B slice, unblended
+        if a["sigma2_end"] is not None:                        # model_mul of :1087 with the replaced sigma2: once, on the host
+            al, sd = k.to_host([alpha, SigmaDiag], own_pinned=False)
+            model_mul = k.h2d(np.array(al, dtype=np.float64) * np.exp(-np.array(sd, dtype=np.float64) / sigma2))
+        dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance,
+                             _spatial_outlier(sigma2, gamma, samples_s, NA, D))
+        k.align_moments(A64, V4, dev["K_NA"], dev["K_NA_spatial"], dev["K_NA_sigma2"], SigmaDiag, dev["PXB"], B64, dev["K_NB"],
+                        block, origin=org, extra=dev["scalars"])
+        blk = np.array(k.to_host([block])[0], dtype=np.float64)
+        Sp_run, Sp_spatial_run, Sp_sigma2_run = float(blk[9]), float(blk[11]), float(blk[12])
+        if not (Sp_run > 0.0 and np.isfinite(blk).all()):
+            raise _lib.MVFError(f"morpho_iterate_svi: the final full assignment is empty or not finite (Sp = {Sp_run})")
+    # ---- _get_optimal_R (:1437-1469) from the last block: A = (sum xc pc^T)^T on the device's means, or (SVI, last batch) on
+    # the batch's sums over the running Sp ----
+    optimal_R, optimal_t = _optimal_from_block(blk, D, None if svi is None or svi["return_mapping"] else Sp_run)
     oRnA = k.empty(NA, 3, dtype=f64)
     k.align_transform(A64, None, None, None, *_embed(optimal_R, optimal_t), RnA=oRnA)
     names = ("K_NA", "K_NB", "K_NA_spatial", "K_NA_sigma2")
@@ -561,6 +668,9 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     out.update({q: np.array(v, dtype=np.float64) for q, v in zip(("alpha", "SigmaDiag") + names, host[5:])})
     out.update(R=R, t=t, optimal_R=optimal_R, optimal_t=optimal_t, sigma2=sigma2, gamma=gamma, sigma2_variance=sigma2_variance,
                Sp=float(blk[9]), Sp_spatial=float(blk[11]), Sp_sigma2=float(blk[12]))
+    if svi is not None:
+        out.update(Sp=Sp_run, Sp_spatial=Sp_spatial_run, Sp_sigma2=Sp_sigma2_run, batch_size=bs,
+                   batch_perm=np.array(svi["batch_perm"], dtype=np.int64), step_size=step)
     if record:
         out["history"] = {q: np.array(v) for q, v in history.items()}
     ph.mark("result")
@@ -575,3 +685,80 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
         "kernel_type": "euc",
     }
     return out
+
+
+def _svi_batch_size(NB, batch_size=None):
+    """The reference's rule (morpho_class.py:753-756): a tenth of the B slice, at least 1000 cells, at most all of them."""
+    if batch_size is None:
+        return min(max(int(NB / 10), 1000), NB)
+    if int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError("batch_size must be a positive integer")
+    return min(int(batch_size), NB)
+
+
+def _svi_schedule(batch_perm, batch_size, it):
+    """batch_idx of iteration ``it`` (:895-896: the head of the permutation, which is then rolled by batch_size):
+    ``batch_perm[(j - it batch_size) mod NB]``, j < batch_size - what mvf_align_gather reads with start = (-it bs) mod NB."""
+    perm = np.asarray(batch_perm)
+    return perm[(np.arange(batch_size) - it * batch_size) % len(perm)]
+
+
+def _svi_arguments(NB, batch_size, batch_perm, seed):
+    """Validation of morpho_iterate_svi's own arguments (no device needed): (batch_size, batch_perm as int32).  The kernel
+    reads row batch_perm[.] of every B array unchecked, so the permutation is proven here, before any launch."""
+    if NB >= 1 << 31:
+        raise ValueError("morpho_iterate_svi: the B slice must have fewer than 2^31 cells")
+    bs = _svi_batch_size(NB, batch_size)
+    if batch_perm is None:
+        perm = np.random.default_rng(seed).permutation(NB)
+    else:
+        perm = np.asarray(batch_perm)
+        if perm.ndim != 1 or len(perm) != NB or perm.dtype.kind not in "iu":
+            raise ValueError(f"batch_perm must be a 1-D integer array with one entry per B cell ({NB})")
+        if perm.min() < 0 or perm.max() >= NB or not np.array_equal(np.sort(perm), np.arange(NB)):
+            raise ValueError("batch_perm must be a permutation of range(NB): every index exactly once")
+    return bs, np.ascontiguousarray(perm, dtype=np.int32)
+
+
+def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity, probability_type, probability_parameters,
+                       inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter=0, kappa=1.0, gamma_a=1.0,
+                       gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
+                       update_R=True, dtype: str = "float64", device=None, record=True, origin=None, batch_size=None,
+                       batch_perm=None, seed=None, return_mapping=False, guidance=None, sparse_calculation_mode=False,
+                       kernel_type="euc"):
+    """The SVI mode of the same loop - the reference constructor's default, ``SVI_mode=True``
+    (``spateo/alignment/methods/morpho_class.py:136, 283-284, 749-760, 894-896``): every iteration sees ``batch_size`` cells
+    of the B slice and blends what it learns into running averages with ``step_size = min(1, 10 / (iter + 1))``.
+
+    ``batch_size``: None takes the reference's rule ``min(max(int(NB / 10), 1000), NB)``, a number is capped at NB.
+    ``batch_perm``: the initial permutation of ``range(NB)`` (``ValueError`` unless every index occurs exactly once); None
+    draws one from ``np.random.default_rng(seed)``.  Iteration ``it`` takes ``batch_perm[(j - it batch_size) mod NB]``,
+    ``j < batch_size`` - the reference's head-then-``roll``.  Everything else as ``morpho_iterate`` takes it.
+
+    What differs from the dense loop, per iteration: the assignment runs on NA x the batch (``mvf_align_gather`` copies the
+    batch's rows of the coordinates and of every prepared B layer on the device, ``mvf_assign`` follows); ``Sp``,
+    ``Sp_spatial``, ``Sp_sigma2`` are blended (``:1178-1181``) and divide this batch's sums in ``_update_rigid`` and
+    ``_update_sigma2``; gamma counts ``batch_size`` cells (``:1214-1218``); alpha (``mvf_align_alpha_svi``, ``:1240-1247``),
+    ``PXB_term`` (``mvf_align_transform_svi``) and ``SigmaInv`` (``mvf_lincomb3``, on the device) are blended with their
+    running values, which start at zero (``:758-760``) - also when the first non-rigid update comes at ``iter >= 10``, as in
+    the reference; R and t are blended once ``step_size < 1`` (``:1375-1376, 1399-1400``), so ``R`` is no rotation then.
+    The host reads the same one block of 64 float64 per iteration; nothing of size NA, NB or ``batch_size`` crosses the link
+    between the first upload and the result.  After the loop ``sigma2_end`` replaces sigma2; ``return_mapping=True`` runs
+    one full, non-SVI assignment on the final state (``:300-302``), whose ``K_NA``, ``K_NB`` (NB,) and unblended ``Sp*`` are
+    returned and feed ``_get_optimal_R``; otherwise ``_get_optimal_R`` sees the last batch over the running ``Sp``
+    (``:1451-1461``).  The reference's SVI result is not translation covariant (the blended ``Sp`` divides the batch's
+    sums): ``origin`` only re-centres the assignment's operands, as in ``morpho_iterate``.
+
+    Not supported (``NotImplementedError``): what ``morpho_iterate`` refuses but ``SVI_mode``.
+
+    Returns ``morpho_iterate``'s dict - ``K_NA``, ``K_NB`` (``batch_size``,), ``K_NA_spatial``, ``K_NA_sigma2`` of the last
+    batch, ``Sp``, ``Sp_spatial``, ``Sp_sigma2`` the running values (or all of them the full assignment's) - plus
+    ``batch_size``, ``batch_perm``, ``step_size`` (the last); ``history`` gains ``step_size``.  Two calls give equal bits."""
+    a = _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
+                           probability_parameters, inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter,
+                           kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
+                           record, False, guidance, sparse_calculation_mode, kernel_type, origin)
+    bs, perm = _svi_arguments(len(a["XB"]), batch_size, batch_perm, seed)
+    return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
+                    partial_robust_level, nn_init_weight, update_R, dtype, device, record,
+                    svi=dict(batch_size=bs, batch_perm=perm, return_mapping=bool(return_mapping)))
