@@ -508,6 +508,20 @@ int mvf_assign_dense(const void* xa4, int64_t na, const void* xb4, int64_t nb, c
                      const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier, double* K_NA,
                      double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars, double* P,
                      void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream);
+/* The reference's `sparse_calculation_mode` (`get_P_core` -> `_dense_to_sparse(axis=0, descending=True)`, utils.py:1085-1094,
+ * 1369-1404): the k_eff = min(k, na) largest entries of every column of P are kept, 1 <= k <= MVF_ASSIGN_TOPK_MAX (the
+ * per-column lists of a 64-column workgroup live in LDS: 64 x 64 x 12 bytes = 48 KiB at the cap); any other k is an error.
+ * rows (nb x k_eff int32) / vals (nb x k_eff float64): column j's kept entries in the total order (value descending, row
+ * ascending); a column whose terms all underflow has vals = 0 and rows = 0 .. k_eff - 1.  K_NB[j] = the sum of vals[j][.] in
+ * stored order; K_NA and PXB are summed over the kept entries only; K_NA_spatial, K_NA_sigma2 and scalars[0] are the dense
+ * quantities, the same sums as mvf_assign's.  No floating-point atomics: two calls give the same bits, rows included.
+ * (An addition behind version 7: no existing signature or layout changes.) */
+#define MVF_ASSIGN_TOPK_MAX 64
+size_t mvf_assign_topk_workspace_bytes(int64_t na, int64_t nb, int k); /* 0 for an empty side or k outside the range */
+int mvf_assign_topk(const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers, int nlayers,
+                    const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier, int k,
+                    double* K_NA, double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars,
+                    int32_t* rows, double* vals, void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream);
 
 /* ---- alignment: the O(N) glue of one iteration between the assignment and the non-rigid update (mvf_align.hip) ----------
  * With mvf_assign, mvf_gram, mvf_solve_minnorm*, mvf_apply and mvf_pinv_diag these three make the loop of

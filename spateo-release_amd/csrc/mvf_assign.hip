@@ -23,6 +23,16 @@
 // exactly 0 everywhere.  A workgroup is 4 waves on a 64 x 64 tile (each wave 32 x 32: 2 x 2 MFMA blocks); the rows (pass 1) /
 // columns (pass 2) are split over workgroups, every split writes its partial sums to the workspace and a small kernel adds
 // them in split order: no floating-point atomics, two calls give the same bits.
+//
+// mvf_assign_topk (the reference's sparse_calculation_mode: `_dense_to_sparse(axis=0, descending=True)`, methods/utils.py:
+// 1085-1094, 1369-1404) keeps the k largest entries of every column of P.  Within a column P_ij = c3_j u_ij with u_ij = e2_ij m_i
+// q_ij, the summand of S3, and c3_j >= 0: the k largest of a column of P are the k largest of u over the rows.  Pass 1 keeps,
+// per workgroup, a sorted (value, row) list of k per column in LDS in the total order (value descending, row ascending); a
+// wave per column merges the row splits' lists, applies c3 and writes rows / vals / K_NB; pass 2 adds an entry to K_NA / PXB
+// only if its row index is in the column's list.  The k largest of a set under a total order do not depend on the order of
+// insertion: the lists, and with them every output, are the same bits on every call.
+#include <climits>
+
 #include "mvf_common.h"
 
 namespace mvf {
@@ -36,6 +46,10 @@ constexpr int MAX_LAYERS = 4;
 constexpr int MAX_SPLITS = 64;
 constexpr int TARGET_WGS = 1024;  // workgroups a pass aims for (4 per CU)
 constexpr double ASSIGN_EPS = 1e-8;
+constexpr int TOPK_MAX = MVF_ASSIGN_TOPK_MAX;
+constexpr int TOPK_STAGE = 16;    // candidates a column stages per round (more wait for the next round)
+constexpr double TOPK_PREFILTER = 1e-6;  // pass 2 looks a row up in a column's list from this far below its last value on
+static_assert(MAX_SPLITS <= 64, "the merge of the row splits' lists gives every split one lane of a wave");
 
 struct DevLayer {
     const void* X;
@@ -153,6 +167,25 @@ struct Point {
     double x, y, z, n2;
 };
 
+// workspace of mvf_assign_topk behind mvf_assign's: the row splits' lists, lv / lr[split][k][nb_pad]
+struct TopkPlan {
+    int k;  // min(k, na)
+    size_t off_lv, off_lr, total;
+};
+
+TopkPlan make_topk_plan(const Plan& p, int64_t na, int k) {
+    TopkPlan t;
+    t.k = (int)std::min<int64_t>(k, na);
+    size_t o = p.total;
+    t.off_lv = o, o += align_up((size_t)p.rsplit * t.k * p.nb_pad * sizeof(double), 256);
+    t.off_lr = o, o += align_up((size_t)p.rsplit * t.k * p.nb_pad * sizeof(int), 256);
+    t.total = o;
+    return t;
+}
+
+// the total order of a column's entries: value descending, row ascending
+__device__ __forceinline__ bool topk_before(double v, int r, double w, int s) { return v > w || (v == w && r < s); }
+
 template <typename T>
 __device__ __forceinline__ Point load_point(const T* x4, int64_t i) {
     double v[4];
@@ -220,6 +253,176 @@ __global__ __launch_bounds__(256) void assign_pass1_kernel(const T* __restrict__
     part1[((int64_t)blockIdx.y * 4 + k) * nb_pad + (int64_t)blockIdx.x * AT + c] = tot;
 }
 
+// ---- pass 1 of mvf_assign_topk: the column sums as above and, per column, the k largest u = e2 m q of this row split.
+// lval / lrow[p][c]: the list of column c, sorted, always k long (unused places hold (-inf, INT_MAX), which every entry
+// beats).  Per tile a lane compares its 16 values with its columns' last entries; the ones that beat them are staged through
+// per-column integer counters (at most TOPK_STAGE a round, the rest wait) and thread c inserts column c's.
+template <typename T, int KC>
+__global__ __launch_bounds__(256) void assign_pass1_topk_kernel(const T* __restrict__ xa4, int64_t na, const T* __restrict__ xb4,
+                                                                int64_t nb, DevLayers L, const double* __restrict__ mm, double h1,
+                                                                double h2, int64_t rtiles, int64_t nb_pad, int k,
+                                                                double* __restrict__ part1, double* __restrict__ lv,
+                                                                int* __restrict__ lr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, lk = lane >> 4, wi = wave >> 1, wj = wave & 1;
+    const int64_t j0 = (int64_t)blockIdx.x * AT + 32 * wj;
+    const int64_t t_lo = rtiles * blockIdx.y / gridDim.y, t_hi = rtiles * (blockIdx.y + 1) / gridDim.y;
+    __shared__ double lval[KC][AT];
+    __shared__ int lrow[KC][AT];
+    __shared__ double red[4][8][AT];  // after the tiles: the partial sums; between them: the staged candidates
+    __shared__ int scnt[AT];
+    double(*sval)[AT] = reinterpret_cast<double(*)[AT]>(&red[0][0][0]);  // [TOPK_STAGE][AT]
+    int(*srow)[AT] = reinterpret_cast<int(*)[AT]>(&red[2][0][0]);        // [TOPK_STAGE][AT]
+    static_assert(TOPK_STAGE * AT * sizeof(double) <= 2 * 8 * AT * sizeof(double) &&
+                      TOPK_STAGE * AT * sizeof(int) <= 2 * 8 * AT * sizeof(double),
+                  "the staged values lie in red[0..1], their rows in red[2..3]");
+    for (int e = threadIdx.x; e < k * AT; e += 256) lval[e / AT][e % AT] = -HUGE_VAL, lrow[e / AT][e % AT] = INT_MAX;
+    if (threadIdx.x < AT) scnt[threadIdx.x] = 0;
+    __syncthreads();
+    Point cb[2];
+    int col[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) cb[b] = load_point(xb4, std::min<int64_t>(j0 + 16 * b + li, nb - 1)), col[b] = 32 * wj + 16 * b + li;
+    double s[4][2] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+    for (int64_t t = t_lo; t < t_hi; ++t) {
+        const int64_t i0 = t * AT + 32 * wi;
+        f64x4 q[2][2];
+        layer_product<T>(L, i0, j0, na, nb, li, lk, q);
+        double u[2][4][2];
+        unsigned pend = 0;  // bit 8 a + 2 r + b: u[a][r][b] beats the last entry of its column's list and is not staged yet
+        double tv[2];
+        int tr[2];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) tv[b] = lval[k - 1][col[b]], tr[b] = lrow[k - 1][col[b]];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t i = i0 + 16 * a + lk + 4 * r;
+                const bool live = i < na;
+                const Point pa = load_point(xa4, live ? i : na - 1);
+                const double m = live ? mm[i] : 0.0, one = live ? 1.0 : 0.0;
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const double d = sq_dist(pa, cb[b]);
+                    const double e1 = exp(d * h1), e2m = __dmul_rn(exp(d * h2), m);
+                    const double uu = __dmul_rn(e2m, q[a][b][r]);  // the selection key: a product, stored as rounded
+                    s[0][b] += e1 * one;
+                    s[1][b] += e1 * m;
+                    s[2][b] += e2m;
+                    s[3][b] += uu;
+                    u[a][r][b] = uu;
+                    if (live && topk_before(uu, (int)i, tv[b], tr[b])) pend |= 1u << (8 * a + 2 * r + b);
+                }
+            }
+        while (__syncthreads_or(pend != 0)) {
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        const unsigned bit = 1u << (8 * a + 2 * r + b);
+                        if (pend & bit) {
+                            const int slot = atomicAdd(&scnt[col[b]], 1);
+                            if (slot < TOPK_STAGE) {
+                                sval[slot][col[b]] = u[a][r][b];
+                                srow[slot][col[b]] = (int)(i0 + 16 * a + lk + 4 * r);
+                                pend &= ~bit;
+                            }
+                        }
+                    }
+            __syncthreads();
+            if (threadIdx.x < AT) {
+                const int c = threadIdx.x, n = min(scnt[c], TOPK_STAGE);
+                for (int e = 0; e < n; ++e) {
+                    const double v = sval[e][c];
+                    const int row = srow[e][c];
+                    if (!topk_before(v, row, lval[k - 1][c], lrow[k - 1][c])) continue;
+                    int p = k - 1;
+                    while (p > 0 && topk_before(v, row, lval[p - 1][c], lrow[p - 1][c])) {
+                        lval[p][c] = lval[p - 1][c], lrow[p][c] = lrow[p - 1][c];
+                        --p;
+                    }
+                    lval[p][c] = v, lrow[p][c] = row;
+                }
+                scnt[c] = 0;
+            }
+            __syncthreads();
+            if (pend) {  // what waits for the next round is compared with the lists as they are now
+#pragma unroll
+                for (int b = 0; b < 2; ++b) tv[b] = lval[k - 1][col[b]], tr[b] = lrow[k - 1][col[b]];
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int b = 0; b < 2; ++b) {
+                            const unsigned bit = 1u << (8 * a + 2 * r + b);
+                            if ((pend & bit) && !topk_before(u[a][r][b], (int)(i0 + 16 * a + lk + 4 * r), tv[b], tr[b])) pend &= ~bit;
+                        }
+            }
+        }
+    }
+    // (the loop's last barrier lies behind the last insertion)
+    for (int e = threadIdx.x; e < k * AT; e += 256) {
+        const int64_t o = ((int64_t)blockIdx.y * k + e / AT) * nb_pad + (int64_t)blockIdx.x * AT + e % AT;
+        lv[o] = lval[e / AT][e % AT], lr[o] = lrow[e / AT][e % AT];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) red[kk][wi * 4 + lk][32 * wj + 16 * b + li] = s[kk][b];
+    __syncthreads();
+    const int kk = threadIdx.x >> 6, c = threadIdx.x & 63;
+    double tot = 0.0;
+#pragma unroll
+    for (int g = 0; g < 8; ++g) tot += red[kk][g][c];
+    part1[((int64_t)blockIdx.y * 4 + kk) * nb_pad + (int64_t)blockIdx.x * AT + c] = tot;
+}
+
+// ---- the row splits' lists of a column merged by one wave (lane = split, its list's head in registers; k rounds pick the
+// first of the heads in the total order): rows / vals[j][k] = the kept entries of P, K_NB[j] = their sum in stored order
+__global__ __launch_bounds__(256) void assign_topk_merge_kernel(const double* __restrict__ lv, const int* __restrict__ lr,
+                                                                int64_t rsplit, int k, int64_t nb, int64_t nb_pad,
+                                                                const double* __restrict__ fac, int* __restrict__ rows,
+                                                                double* __restrict__ vals, double* __restrict__ K_NB) {
+    const int lane = threadIdx.x & 63;
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= nb) return;
+    const double c3 = fac[4 * j + 2];
+    int ptr = 0;
+    double hv = -HUGE_VAL;
+    int hr = INT_MAX;
+    if (lane < rsplit) hv = lv[((int64_t)lane * k) * nb_pad + j], hr = lr[((int64_t)lane * k) * nb_pad + j];
+    double sum = 0.0;
+    for (int p = 0; p < k; ++p) {
+        double bv = hv;
+        int br = hr, bs = lane;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ov = __shfl_xor(bv, o, 64);
+            const int orow = __shfl_xor(br, o, 64), os = __shfl_xor(bs, o, 64);
+            if (topk_before(ov, orow, bv, br) || (ov == bv && orow == br && os < bs)) bv = ov, br = orow, bs = os;
+        }
+        if (lane == bs) {
+            ++ptr;
+            hv = -HUGE_VAL, hr = INT_MAX;
+            if (ptr < k && lane < rsplit) hv = lv[((int64_t)lane * k + ptr) * nb_pad + j], hr = lr[((int64_t)lane * k + ptr) * nb_pad + j];
+        }
+        if (lane == 0) {
+            // (na >= k rows were offered, so a place holder can only come first behind non-finite values: kept in range)
+            const bool real = br != INT_MAX;
+            const double v = real ? __dmul_rn(c3, bv) : 0.0;
+            rows[j * k + p] = real ? br : p;
+            vals[j * k + p] = v;
+            sum += v;
+        }
+    }
+    if (lane == 0) K_NB[j] = sum;
+}
+
 // ---- column factors: fac[j] = {c1, c2, c3, 0}, K_NB[j] = c3 S3 (the splits added in order)
 __global__ __launch_bounds__(256) void assign_factors_kernel(const double* __restrict__ part1, int64_t rsplit, int64_t nb,
                                                              int64_t nb_pad, double outlier, double* __restrict__ fac,
@@ -242,13 +445,18 @@ __global__ __launch_bounds__(256) void assign_factors_kernel(const double* __res
 }
 
 // ---- pass 2: row sums.  grid (row tiles, column splits); part2[split][na_pad][8] = {sum e1 c1, sum e2 c2, sum e2 q c3,
-// PXB x, y, z, sum e2 c2 d, 0} (the row factor m_i is applied by the reduction)
-template <typename T, bool DENSE>
+// PXB x, y, z, sum e2 c2 d, 0} (the row factor m_i is applied by the reduction).  MODE P2_DENSE writes P as well; P2_TOPK
+// (mvf_assign_topk) adds to sum e2 q c3 and to PXB only the entries whose row is in the column's list trows[j][k]: the
+// comparison with the list's last value tvals[j][k - 1] only spares the look-up, the row indices decide
+enum { P2_PLAIN = 0, P2_DENSE = 1, P2_TOPK = 2 };
+
+template <typename T, int MODE>
 __global__ __launch_bounds__(256) void assign_pass2_kernel(const T* __restrict__ xa4, int64_t na, const T* __restrict__ xb4,
                                                            int64_t nb, DevLayers L, const double* __restrict__ mm, double h1,
                                                            double h2, const double* __restrict__ fac, int64_t ctiles,
-                                                           int64_t na_pad, double* __restrict__ part2,
-                                                           double* __restrict__ P) {
+                                                           int64_t na_pad, double* __restrict__ part2, double* __restrict__ P,
+                                                           const int* __restrict__ trows, const double* __restrict__ tvals,
+                                                           int tk) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, lk = lane >> 4, wi = wave >> 1, wj = wave & 1;
     const int64_t i0 = (int64_t)blockIdx.x * AT + 32 * wi;
@@ -265,6 +473,11 @@ __global__ __launch_bounds__(256) void assign_pass2_kernel(const T* __restrict__
         for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int k = 0; k < 7; ++k) acc[a][r][k] = 0.0;
+    double mi[2][4];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mi[a][r] = MODE == P2_TOPK ? mm[std::min<int64_t>(i0 + 16 * a + lk + 4 * r, na - 1)] : 0.0;
     for (int64_t t = t_lo; t < t_hi; ++t) {
         const int64_t j0 = t * AT + 32 * wj;
         f64x4 q[2][2];
@@ -275,13 +488,26 @@ __global__ __launch_bounds__(256) void assign_pass2_kernel(const T* __restrict__
             const Point cb = load_point(xb4, std::min<int64_t>(j, nb - 1));
             double f[4];
             load4(fac + 4 * j, f);
+            double last = 0.0;
+            if (MODE == P2_TOPK && j < nb) last = tvals[j * tk + tk - 1];
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const double d = sq_dist(pa[a][r], cb);
                     const double e1 = exp(d * h1), e2 = exp(d * h2);
-                    const double t2 = e2 * f[1], t3 = (e2 * q[a][b][r]) * f[2];
+                    const double t2 = e2 * f[1];
+                    double t3 = (e2 * q[a][b][r]) * f[2];
+                    if (MODE == P2_TOPK) {
+                        // (an entry that is exactly 0 adds nothing whether it is kept or not: not looked up)
+                        bool keep = false;
+                        const int64_t i = i0 + 16 * a + lk + 4 * r;
+                        if (j < nb && i < na && t3 != 0.0 && mi[a][r] * t3 >= last - TOPK_PREFILTER * fabs(last)) {
+                            const int* lst = trows + j * tk;
+                            for (int p = 0; p < tk; ++p) keep = keep || lst[p] == (int)i;
+                        }
+                        if (!keep) t3 = 0.0;
+                    }
                     acc[a][r][0] += e1 * f[0];
                     acc[a][r][1] += t2;
                     acc[a][r][2] += t3;
@@ -289,7 +515,7 @@ __global__ __launch_bounds__(256) void assign_pass2_kernel(const T* __restrict__
                     acc[a][r][4] += t3 * cb.y;
                     acc[a][r][5] += t3 * cb.z;
                     acc[a][r][6] += t2 * d;
-                    if (DENSE) {
+                    if (MODE == P2_DENSE) {
                         const int64_t i = i0 + 16 * a + lk + 4 * r;
                         if (i < na && j < nb) P[i * nb + j] = mm[i] * t3;
                     }
@@ -405,23 +631,45 @@ int64_t padded_features(int64_t g, int metric) { return cdiv(metric == MVF_ASSIG
 template <typename T>
 int run_assign(hipStream_t st, const Plan& p, const void* xa4, int64_t na, const void* xb4, int64_t nb, const DevLayers& L,
                const double* mm, double h1, double h2, double outlier, double* K_NA, double* K_NB, double* K_NA_spatial,
-               double* K_NA_sigma2, double* PXB, double* scalars, double* P, char* ws) {
+               double* K_NA_sigma2, double* PXB, double* scalars, double* P, const TopkPlan* tp, int* trows, double* tvals,
+               char* ws) {
     double* part1 = (double*)(ws + p.off_part1);
     double* fac = (double*)(ws + p.off_fac);
     double* part2 = (double*)(ws + p.off_part2);
     double* rows = (double*)(ws + p.off_rows);
-    hipLaunchKernelGGL((assign_pass1_kernel<T>), dim3((unsigned)p.ctiles, (unsigned)p.rsplit), dim3(256), 0, st, (const T*)xa4, na,
-                       (const T*)xb4, nb, L, mm, h1, h2, p.rtiles, p.nb_pad, part1);
+    const dim3 grid1((unsigned)p.ctiles, (unsigned)p.rsplit), grid2((unsigned)p.rtiles, (unsigned)p.csplit);
+    double* lv = tp ? (double*)(ws + tp->off_lv) : nullptr;
+    int* lr = tp ? (int*)(ws + tp->off_lr) : nullptr;
+    const int k = tp ? tp->k : 0;
+#define MVF_PASS1_TOPK(KC)                                                                                                     \
+    hipLaunchKernelGGL((assign_pass1_topk_kernel<T, KC>), grid1, dim3(256), 0, st, (const T*)xa4, na, (const T*)xb4, nb, L, mm, \
+                       h1, h2, p.rtiles, p.nb_pad, k, part1, lv, lr)
+    if (!tp)
+        hipLaunchKernelGGL((assign_pass1_kernel<T>), grid1, dim3(256), 0, st, (const T*)xa4, na, (const T*)xb4, nb, L, mm, h1, h2,
+                           p.rtiles, p.nb_pad, part1);
+    else if (k <= 4)  // the lists' LDS is sized by the template: 3 KiB, 12 KiB or 48 KiB
+        MVF_PASS1_TOPK(4);
+    else if (k <= 16)
+        MVF_PASS1_TOPK(16);
+    else
+        MVF_PASS1_TOPK(TOPK_MAX);
+#undef MVF_PASS1_TOPK
     MVF_LAUNCH_CHECK();
     hipLaunchKernelGGL(assign_factors_kernel, dim3((unsigned)cdiv(p.nb_pad, 256)), dim3(256), 0, st, part1, p.rsplit, nb, p.nb_pad,
                        outlier, fac, K_NB);
     MVF_LAUNCH_CHECK();
-    if (P)
-        hipLaunchKernelGGL((assign_pass2_kernel<T, true>), dim3((unsigned)p.rtiles, (unsigned)p.csplit), dim3(256), 0, st,
-                           (const T*)xa4, na, (const T*)xb4, nb, L, mm, h1, h2, fac, p.ctiles, p.na_pad, part2, P);
+    if (tp) {  // K_NB is written again: the sum of the column's kept entries
+        hipLaunchKernelGGL(assign_topk_merge_kernel, dim3((unsigned)cdiv(nb, 4)), dim3(256), 0, st, lv, lr, p.rsplit, k, nb, p.nb_pad,
+                           fac, trows, tvals, K_NB);
+        MVF_LAUNCH_CHECK();
+        hipLaunchKernelGGL((assign_pass2_kernel<T, P2_TOPK>), grid2, dim3(256), 0, st, (const T*)xa4, na, (const T*)xb4, nb, L, mm,
+                           h1, h2, fac, p.ctiles, p.na_pad, part2, P, trows, tvals, k);
+    } else if (P)
+        hipLaunchKernelGGL((assign_pass2_kernel<T, P2_DENSE>), grid2, dim3(256), 0, st, (const T*)xa4, na, (const T*)xb4, nb, L, mm,
+                           h1, h2, fac, p.ctiles, p.na_pad, part2, P, nullptr, nullptr, 0);
     else
-        hipLaunchKernelGGL((assign_pass2_kernel<T, false>), dim3((unsigned)p.rtiles, (unsigned)p.csplit), dim3(256), 0, st,
-                           (const T*)xa4, na, (const T*)xb4, nb, L, mm, h1, h2, fac, p.ctiles, p.na_pad, part2, P);
+        hipLaunchKernelGGL((assign_pass2_kernel<T, P2_PLAIN>), grid2, dim3(256), 0, st, (const T*)xa4, na, (const T*)xb4, nb, L, mm,
+                           h1, h2, fac, p.ctiles, p.na_pad, part2, P, nullptr, nullptr, 0);
     MVF_LAUNCH_CHECK();
     hipLaunchKernelGGL(assign_rows_kernel, dim3((unsigned)cdiv(na, 256)), dim3(256), 0, st, part2, p.csplit, na, p.na_pad, mm, K_NA,
                        K_NA_spatial, K_NA_sigma2, PXB, rows);
@@ -434,18 +682,24 @@ int run_assign(hipStream_t st, const Plan& p, const void* xa4, int64_t na, const
 int assign_entry(const char* who, const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers,
                  int nlayers, const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier,
                  double* K_NA, double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars, double* P,
-                 bool dense, void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream) {
+                 bool dense, int k, int* trows, double* tvals, void* workspace, size_t workspace_bytes, mvf_dtype dtype,
+                 void* stream) {
+    const bool topk = trows || tvals || k;  // (mvf_assign and mvf_assign_dense pass 0 and null pointers)
+    if (topk) MVF_REQUIRE(k >= 1 && k <= TOPK_MAX, "%s: need 1 <= k <= %d, got %d", who, TOPK_MAX, k);
     if (na == 0 || nb == 0) return 0;
     MVF_REQUIRE(na > 0 && nb > 0, "%s: negative size", who);
     MVF_REQUIRE(na < ((int64_t)1 << 31) && nb < ((int64_t)1 << 31), "%s: too many cells", who);
     MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "%s: bad dtype %d", who, (int)dtype);
     MVF_REQUIRE(nlayers >= 1 && nlayers <= MAX_LAYERS, "%s: need 1 .. %d layers, got %d", who, MAX_LAYERS, nlayers);
     MVF_REQUIRE(xa4 && xb4 && layers && model_mul && K_NA && K_NB && K_NA_spatial && K_NA_sigma2 && PXB && scalars && workspace &&
-                    (P || !dense),
+                    (P || !dense) && ((trows && tvals) || !topk),
                 "%s: null pointer", who);
     MVF_REQUIRE(sigma2 > 0.0 && sigma2_variance > 0.0 && spatial_outlier >= 0.0, "%s: need sigma2 > 0, sigma2_variance > 0, outlier >= 0", who);
     const Plan p = make_plan(na, nb);
-    MVF_REQUIRE(workspace_bytes >= p.total, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, p.total);
+    TopkPlan tp;
+    if (topk) tp = make_topk_plan(p, na, k);
+    const size_t need = topk ? tp.total : p.total;
+    MVF_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
     DevLayers L;
     L.n = nlayers;
     for (int l = 0; l < nlayers; ++l) {
@@ -466,9 +720,9 @@ int assign_entry(const char* who, const void* xa4, int64_t na, const void* xb4, 
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MVF_F32)
         return run_assign<float>(st, p, xa4, na, xb4, nb, L, model_mul, h1, h2, spatial_outlier, K_NA, K_NB, K_NA_spatial,
-                                 K_NA_sigma2, PXB, scalars, P, (char*)workspace);
+                                 K_NA_sigma2, PXB, scalars, P, topk ? &tp : nullptr, trows, tvals, (char*)workspace);
     return run_assign<double>(st, p, xa4, na, xb4, nb, L, model_mul, h1, h2, spatial_outlier, K_NA, K_NB, K_NA_spatial,
-                              K_NA_sigma2, PXB, scalars, P, (char*)workspace);
+                              K_NA_sigma2, PXB, scalars, P, topk ? &tp : nullptr, trows, tvals, (char*)workspace);
 }
 
 }  // namespace
@@ -512,7 +766,8 @@ extern "C" int mvf_assign(const void* xa4, int64_t na, const void* xb4, int64_t 
                           double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars, void* workspace,
                           size_t workspace_bytes, mvf_dtype dtype, void* stream) {
     return assign_entry("mvf_assign", xa4, na, xb4, nb, layers, nlayers, model_mul, sigma2, sigma2_variance, spatial_outlier, K_NA,
-                        K_NB, K_NA_spatial, K_NA_sigma2, PXB, scalars, nullptr, false, workspace, workspace_bytes, dtype, stream);
+                        K_NB, K_NA_spatial, K_NA_sigma2, PXB, scalars, nullptr, false, 0, nullptr, nullptr, workspace, workspace_bytes,
+                        dtype, stream);
 }
 
 extern "C" int mvf_assign_dense(const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers,
@@ -521,5 +776,22 @@ extern "C" int mvf_assign_dense(const void* xa4, int64_t na, const void* xb4, in
                                 double* PXB, double* scalars, double* P, void* workspace, size_t workspace_bytes, mvf_dtype dtype,
                                 void* stream) {
     return assign_entry("mvf_assign_dense", xa4, na, xb4, nb, layers, nlayers, model_mul, sigma2, sigma2_variance, spatial_outlier,
-                        K_NA, K_NB, K_NA_spatial, K_NA_sigma2, PXB, scalars, P, true, workspace, workspace_bytes, dtype, stream);
+                        K_NA, K_NB, K_NA_spatial, K_NA_sigma2, PXB, scalars, P, true, 0, nullptr, nullptr, workspace, workspace_bytes,
+                        dtype, stream);
+}
+
+extern "C" size_t mvf_assign_topk_workspace_bytes(int64_t na, int64_t nb, int k) {
+    if (na <= 0 || nb <= 0 || k < 1 || k > TOPK_MAX) return 0;
+    return make_topk_plan(make_plan(na, nb), na, k).total;
+}
+
+extern "C" int mvf_assign_topk(const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers,
+                               int nlayers, const double* model_mul, double sigma2, double sigma2_variance,
+                               double spatial_outlier, int k, double* K_NA, double* K_NB, double* K_NA_spatial,
+                               double* K_NA_sigma2, double* PXB, double* scalars, int32_t* rows, double* vals, void* workspace,
+                               size_t workspace_bytes, mvf_dtype dtype, void* stream) {
+    MVF_REQUIRE(k >= 1 && k <= TOPK_MAX, "mvf_assign_topk: need 1 <= k <= %d, got %d", TOPK_MAX, k);
+    return assign_entry("mvf_assign_topk", xa4, na, xb4, nb, layers, nlayers, model_mul, sigma2, sigma2_variance, spatial_outlier,
+                        K_NA, K_NB, K_NA_spatial, K_NA_sigma2, PXB, scalars, nullptr, false, k, rows, vals, workspace,
+                        workspace_bytes, dtype, stream);
 }

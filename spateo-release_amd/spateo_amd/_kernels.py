@@ -629,6 +629,32 @@ class HipKernels:
             _lib.check(self.lib.mvf_assign(*head, *tail), "mvf_assign")
         return out
 
+    @_on_device
+    def assign_topk(self, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, spatial_outlier, k):
+        """The assignment step of the reference's sparse_calculation_mode (mvf_assign_topk): the k_eff = min(k, na) largest
+        entries of every column of P are kept.  Returns assign's dict - K_NA, K_NB, PXB of the kept entries, K_NA_spatial,
+        K_NA_sigma2, scalars the dense ones - plus rows (nb, k_eff) int32 and vals (nb, k_eff) float64: column j's entries,
+        value descending, row ascending."""
+        na, nb = xa4.shape[0], xb4.shape[0]
+        k = int(k)
+        ke = min(k, na)
+        f64 = torch.float64
+        arr = (_lib.AssignLayer * len(layers))()
+        for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, layers):
+            s.Xp, s.Yp, s.a, s.b, s.ld = _ptr(Xp), _ptr(Yp), _ptr(a), _ptr(b), int(ld)
+            s.metric, s.prob, s.param = int(metric), int(prob), float(param)
+        out = {"K_NA": self.empty(na, dtype=f64), "K_NB": self.empty(nb, dtype=f64), "K_NA_spatial": self.empty(na, dtype=f64),
+               "K_NA_sigma2": self.empty(na, dtype=f64), "PXB": self.empty(na, 3, dtype=f64), "scalars": self.empty(1, dtype=f64),
+               "rows": self.empty(nb, ke, dtype=torch.int32), "vals": self.empty(nb, ke, dtype=f64)}
+        need = int(self.lib.mvf_assign_topk_workspace_bytes(na, nb, k))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.mvf_assign_topk(_ptr(xa4), na, _ptr(xb4), nb, arr, len(layers), _ptr(model_mul), float(sigma2),
+                                            float(sigma2_variance), float(spatial_outlier), k, _ptr(out["K_NA"]),
+                                            _ptr(out["K_NB"]), _ptr(out["K_NA_spatial"]), _ptr(out["K_NA_sigma2"]),
+                                            _ptr(out["PXB"]), _ptr(out["scalars"]), _ptr(out["rows"]), _ptr(out["vals"]),
+                                            _ptr(ws), need, self.cdtype, self._stream()), "mvf_assign_topk")
+        return out
+
     # ---- the O(N) glue of the alignment loop (mvf_align.hip): device tensors in, device tensors out ----
     @_on_device
     def align_alpha(self, kappa, K_NA_spatial, SigmaDiag, Sp_spatial, sigma2, alpha, model_mul):

@@ -33,6 +33,7 @@ RK45_UNIFORM_TIME, RK45_ARC_LENGTH = 0, 1
 ASSIGN_METRICS = {"euc": 0, "euclidean": 0, "square_euc": 1, "square_euclidean": 1, "kl": 2, "sym_kl": 3, "cos": 4, "cosine": 4}
 ASSIGN_PROBS = {"gauss": 0, "gaussian": 0, "cos": 1, "cosine": 1, "prob": 2}
 ASSIGN_MAX_LAYERS = 4
+ASSIGN_TOPK_MAX = 64  # MVF_ASSIGN_TOPK_MAX: the largest sparse_top_k mvf_assign_topk keeps per column
 ALIGN_MOMENT_DOUBLES = 64
 EVAL_V, EVAL_JAC, EVAL_DIV, EVAL_CURL, EVAL_ACC, EVAL_CURV, EVAL_TORS, EVAL_JDET = 1, 2, 4, 8, 16, 32, 64, 128
 
@@ -111,6 +112,9 @@ SIGNATURES = {
                         _p]),
     "mvf_assign_dense": (_i, [_p, _i64, _p, _i64, C.POINTER(AssignLayer), _i, _p, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p,
                               _sz, _i, _p]),
+    "mvf_assign_topk_workspace_bytes": (_sz, [_i64, _i64, _i]),
+    "mvf_assign_topk": (_i, [_p, _i64, _p, _i64, C.POINTER(AssignLayer), _i, _p, _d, _d, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                             _sz, _i, _p]),
     "mvf_align_alpha": (_i, [_p, _p, _p, _i64, _d, _d, _p, _p, _p]),
     "mvf_align_workspace_bytes": (_sz, [_i64, _i64]),
     "mvf_align_moments": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i64, C.POINTER(C.c_double), _p, _p, _p, _sz, _i, _p]),

@@ -24,14 +24,28 @@ __all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_itera
 RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
 
 
+def _sparse_top_k(sparse_calculation_mode, sparse_top_k, return_P=False):
+    """None (the dense path) or the validated ``sparse_top_k`` of ``sparse_calculation_mode``: the test against the device's
+    cap is made on the requested value, before the reference's clamp to NA."""
+    if not sparse_calculation_mode:
+        return None
+    if isinstance(sparse_top_k, bool) or int(sparse_top_k) != sparse_top_k or sparse_top_k < 1:
+        raise ValueError(f"sparse_top_k must be a positive integer, got {sparse_top_k!r}")
+    if sparse_top_k > _lib.ASSIGN_TOPK_MAX:
+        raise NotImplementedError(f"update_assignment: sparse_calculation_mode with sparse_top_k = {int(sparse_top_k)} is not "
+                                  f"supported: the device keeps at most {_lib.ASSIGN_TOPK_MAX} entries per column of P "
+                                  f"(_lib.ASSIGN_TOPK_MAX; the per-column lists live in LDS)")
+    if return_P:
+        raise ValueError("return_P=True (the dense P) and sparse_calculation_mode=True (P as a scipy.sparse.coo_matrix) "
+                         "exclude each other")
+    return int(sparse_top_k)
+
+
 def _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
-                          probability_parameters, sparse_calculation_mode, return_P):
+                          probability_parameters, return_P):
     """Validation of update_assignment (no device needed): the arrays as float64 and the per-layer (metric, probability
     type, parameter) codes of include/mvf.h."""
     XA, XB = np.asarray(XAHat, dtype=np.float64), np.asarray(coordsB, dtype=np.float64)
-    if sparse_calculation_mode:
-        raise NotImplementedError("update_assignment: sparse_calculation_mode (top-k sparsification of P) needs the dense P "
-                                  "and is not supported")
     if XA.ndim != 2 or XB.ndim != 2 or XA.shape[1] != XB.shape[1]:
         raise AssertionError("X and Y do not have the same number of features.")  # _euc_distance_backend (utils.py:775)
     if XA.shape[1] not in (2, 3):
@@ -84,15 +98,28 @@ def _prepare_layers(k, LA, LB, codes):
     return layers
 
 
-def _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, dense=False):
+def _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, dense=False, top_k=None):
     """The device-resident body of update_assignment (and of every iteration of morpho_iterate): device tensors in, the
-    dict of device tensors of HipKernels.assign out."""
+    dict of device tensors of HipKernels.assign - with ``top_k`` (sparse_calculation_mode) of HipKernels.assign_topk - out."""
+    if top_k is not None:
+        return k.assign_topk(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier), top_k)
     return k.assign(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier), dense=dense)
+
+
+def _coo_from_lists(rows, vals, NA):
+    """The reference's sparse P (`_dense_to_sparse`, utils.py:1369-1404) from the device's lists (NB, k_eff): entries in its
+    order, col = repeat(arange(NB), k_eff)."""
+    from scipy.sparse import coo_matrix
+
+    rows, vals = np.asarray(rows), np.asarray(vals, dtype=np.float64)
+    NB, ke = rows.shape
+    col = np.repeat(np.arange(NB), ke)
+    return coo_matrix((vals.reshape(-1), (rows.reshape(-1).astype(np.int64), col)), shape=(NA, NB))
 
 
 def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity, probability_type,
                       probability_parameters, sigma2, alpha, SigmaDiag, gamma, samples_s, sigma2_variance=1.0,
-                      dtype: str = "float64", device=None, return_P=False, sparse_calculation_mode=False):
+                      dtype: str = "float64", device=None, return_P=False, sparse_calculation_mode=False, sparse_top_k=1024):
     """The assignment step of Spateo's alignment, ``Morpho_pairwise._update_assignment_P``
     (``spateo/alignment/methods/morpho_class.py:1071-1200``) followed by ``get_P_core`` on the dense path
     (``spateo/alignment/methods/utils.py:993-1096``; ``use_chunk`` changes nothing mathematically), on the MI355X as one
@@ -105,8 +132,17 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
     ``"cos"`` / ``"cosine"``; ``probability_type[l]`` in ``"gauss"`` (``exp(-d / (2 probability_parameters[l]))``),
     ``"cos"`` (``1 - d``), ``"prob"`` (``d``); ``alpha`` and ``SigmaDiag`` (NA,); the rest scalars.  ``dtype`` is the
     storage of the coordinates and of the prepared layer operands; distances, exponents and every sum are float64 in
-    both modes.  Not supported (``NotImplementedError``): the ``"label"`` metric, ``sparse_calculation_mode``, more than
+    both modes.  Not supported (``NotImplementedError``): the ``"label"`` metric, ``sparse_calculation_mode`` with
+    ``sparse_top_k`` above ``_lib.ASSIGN_TOPK_MAX`` = 64 (the reference constructor's default, 1024, among them), more than
     4 layers, D outside {2, 3}.
+
+    ``sparse_calculation_mode=True`` with ``1 <= sparse_top_k <= 64`` (``get_P_core`` -> ``_dense_to_sparse(axis=0,
+    descending=True)``, ``utils.py:1085-1094, 1369-1404``; ``mvf_assign_topk``): the ``k_eff = min(sparse_top_k, NA)`` largest
+    entries of every column of ``P`` are kept - on equal values the smaller row - and ``K_NA``, ``K_NB``, ``Sp`` and ``PXB``
+    are formed from them (``morpho_class.py:1171-1198``); ``K_NA_spatial``, ``K_NA_sigma2`` and ``sigma2_related`` stay the
+    dense ones.  The result gains ``P``, a ``scipy.sparse.coo_matrix`` (NA, NB) with the entries in the reference's order
+    (``col = repeat(arange(NB), k_eff)``), and ``topk_rows`` / ``topk_values`` (NB, k_eff): column j's entries, value
+    descending.  ``sparse_top_k < 1`` and ``return_P=True`` in this mode are ``ValueError``.
 
     Returns host float64: ``K_NA``, ``K_NA_spatial``, ``K_NA_sigma2`` (NA,), ``K_NB`` (NB,), ``Sp``, ``Sp_spatial``,
     ``Sp_sigma2``, ``sigma2_related`` (already divided by ``Dim * Sp_sigma2``, ``:1200``), ``PXB = P @ coordsB`` (NA, D)
@@ -120,8 +156,9 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
       ``PXB`` and ``K_NA``."""
     if dtype not in ("float32", "float64"):
         raise ValueError("dtype must be 'float32' or 'float64'")
+    top_k = _sparse_top_k(sparse_calculation_mode, sparse_top_k, return_P)
     XA, XB, LA, LB, codes = _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
-                                                  probability_parameters, sparse_calculation_mode, return_P)
+                                                  probability_parameters, return_P)
     NA, D = XA.shape
     al, sd = np.asarray(alpha, dtype=np.float64).reshape(-1), np.asarray(SigmaDiag, dtype=np.float64).reshape(-1)
     if len(al) != NA or len(sd) != NA:
@@ -133,14 +170,18 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
         out.update(Sp=0.0, Sp_spatial=0.0, Sp_sigma2=0.0, sigma2_related=float("nan"), PXB=np.zeros((NA, D)))
         if return_P:
             out["P"] = np.zeros((NA, len(XB)))
+        if top_k is not None:
+            ke = min(top_k, NA)
+            out["topk_rows"], out["topk_values"] = np.zeros((len(XB), ke), dtype=np.int32), np.zeros((len(XB), ke))
+            out["P"] = _coo_from_lists(out["topk_rows"], out["topk_values"], NA)
         return out
     model_mul = al * np.exp(-sd / sigma2)                                                   # morpho_class.py:1087
     outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
     k = _rt._make_kernels(device, dtype)
     layers = _prepare_layers(k, LA, LB, codes)
     dev = _assign_device(k, k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, outlier,
-                         dense=bool(return_P))
-    keys = list(names) + ["PXB", "scalars"] + (["P"] if return_P else [])
+                         dense=bool(return_P), top_k=top_k)
+    keys = list(names) + ["PXB", "scalars"] + (["P"] if return_P else []) + (["rows", "vals"] if top_k is not None else [])
     host = dict(zip(keys, _rt._to_host(k, [dev[q] for q in keys])))
     out = {q: np.array(host[q], dtype=np.float64) for q in names}
     out["Sp"], out["Sp_spatial"], out["Sp_sigma2"] = (float(out[q].sum()) for q in ("K_NB", "K_NA_spatial", "K_NA_sigma2"))
@@ -148,6 +189,9 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
     out["PXB"] = np.array(host["PXB"][:, :D], dtype=np.float64)
     if return_P:
         out["P"] = np.array(host["P"], dtype=np.float64)
+    if top_k is not None:
+        out["topk_rows"], out["topk_values"] = np.array(host["rows"], dtype=np.int32), np.array(host["vals"], dtype=np.float64)
+        out["P"] = _coo_from_lists(out["topk_rows"], out["topk_values"], NA)
     return out
 
 
@@ -321,7 +365,7 @@ def _digamma(x):
 def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type, probability_parameters,
                        inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, kappa, gamma_a, gamma_b,
                        partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype, record, SVI_mode, guidance,
-                       sparse_calculation_mode, kernel_type, origin):
+                       sparse_calculation_mode, kernel_type, origin, sparse_top_k=1024):
     """Validation of morpho_iterate (no device needed).  Returns the arguments as float64 arrays / floats."""
     if dtype not in ("float32", "float64"):
         raise ValueError("dtype must be 'float32' or 'float64'")
@@ -333,8 +377,9 @@ def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilari
     if kernel_type != "euc":
         raise NotImplementedError(f"morpho_iterate: kernel_type={kernel_type!r} is not supported (only the Euclidean 'euc' "
                                   f"kernel; 'geodist' needs the graph distances of the inducing variables)")
+    top_k = _sparse_top_k(sparse_calculation_mode, sparse_top_k)
     XA, XB, LA, LB, codes = _assignment_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
-                                                  probability_parameters, sparse_calculation_mode, False)
+                                                  probability_parameters, False)
     NA, D = XA.shape
     if NA == 0 or len(XB) == 0:
         raise ValueError("morpho_iterate: both slices need at least one cell")
@@ -372,7 +417,7 @@ def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilari
     if origin is not None:
         org[:D] = np.asarray(origin, dtype=np.float64).reshape(D)
     return dict(XA=XA, XB=XB, LA=LA, LB=LB, codes=codes, ctrl=ctrl, kappa=kap, inliers=inl, samples_s=float(samples_s),
-                origin=org, sigma2_end=None if sigma2_end is None else float(sigma2_end))
+                origin=org, sigma2_end=None if sigma2_end is None else float(sigma2_end), top_k=top_k)
 
 
 def _moved_sums(blk, D, mu_XA, mu_Vn, mu_XB, move_Vn):
@@ -464,7 +509,7 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
                    inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter=0, kappa=1.0, gamma_a=1.0,
                    gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                    update_R=True, dtype: str = "float64", device=None, record=True, origin=None, SVI_mode=False, guidance=None,
-                   sparse_calculation_mode=False, kernel_type="euc"):
+                   sparse_calculation_mode=False, kernel_type="euc", sparse_top_k=1024):
     """The iteration loop of Spateo's pairwise alignment on the MI355X: the non-SVI, dense-path body of
     ``Morpho_pairwise.run`` (``spateo/alignment/methods/morpho_class.py:280-294``: assignment -> gamma -> alpha -> non-rigid
     -> rigid -> ``XAHat`` -> sigma2) for ``max_iter`` iterations from the state ``_initialize_variational_variables`` sets
@@ -493,9 +538,15 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     ``history``; ``"arrays"`` (debugging: it crosses the link every iteration) also ``alpha``, ``XAHat``, ``VnA``, ``K_NA``,
     ``Coff``.
 
-    Not supported (``NotImplementedError``): ``SVI_mode`` (``morpho_iterate_svi`` runs it), ``guidance``, ``sparse_calculation_mode``, the ``"label"`` metric,
-    ``kernel_type="geodist"`` (anything but ``"euc"``), and what ``update_assignment`` / ``update_nonrigid`` refuse (more than
-    4 layers, D outside {2, 3}).
+    ``sparse_calculation_mode=True`` with ``1 <= sparse_top_k <= 64``: every iteration's assignment keeps the ``sparse_top_k``
+    largest entries of each column of ``P`` (``mvf_assign_topk`` in place of ``mvf_assign``, as ``update_assignment`` describes
+    it); nothing else of the iteration changes, the other updates read ``K_NA``, ``K_NB``, ``PXB`` and the scalars.  The result
+    gains ``P``, the last assignment's, as a ``scipy.sparse.coo_matrix`` (NA, NB).
+
+    Not supported (``NotImplementedError``): ``SVI_mode`` (``morpho_iterate_svi`` runs it), ``guidance``,
+    ``sparse_calculation_mode`` with ``sparse_top_k`` above 64 (the default, 1024, is the reference constructor's,
+    ``morpho_class.py:140``), the ``"label"`` metric, ``kernel_type="geodist"`` (anything but ``"euc"``), and what
+    ``update_assignment`` / ``update_nonrigid`` refuse (more than 4 layers, D outside {2, 3}).
 
     Returns a dict of host float64: ``R``, ``t``, ``Coff``, ``VnA``, ``RnA``, ``XAHat``, ``optimal_R``, ``optimal_t``,
     ``optimal_RnA``, ``sigma2``, ``gamma``, ``alpha``, ``SigmaDiag``, ``sigma2_variance``, the last assignment's ``K_NA``,
@@ -504,7 +555,7 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     a = _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
                            probability_parameters, inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter,
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
-                           record, SVI_mode, guidance, sparse_calculation_mode, kernel_type, origin)
+                           record, SVI_mode, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k)
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
                     partial_robust_level, nn_init_weight, update_R, dtype, device, record)
 
@@ -513,7 +564,7 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
              nn_init_weight, update_R, dtype, device, record, svi=None):
     """The loop of morpho_iterate and, with ``svi = dict(batch_size=, batch_perm= (int32, validated), return_mapping=)``, of
     morpho_iterate_svi, on validated arguments ``a`` (_iterate_arguments)."""
-    XA, XB, ctrl, org = a["XA"], a["XB"], a["ctrl"], a["origin"]
+    XA, XB, ctrl, org, top_k = a["XA"], a["XB"], a["ctrl"], a["origin"], a["top_k"]
     NA, D = XA.shape
     NB, m = len(XB), len(ctrl)
     beta, lambdaVF, sigma2, samples_s = float(beta), float(lambdaVF), float(sigma2), a["samples_s"]
@@ -571,9 +622,9 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
         if svi is not None:
             step = min(1.0, 10.0 / (it + 1.0))                 # :894, SVI_deacy = 10
             k.align_gather(perm, (-it * bs) % NB, bs, xb4, B64, layers, xb4_b, B64_b, Yp_b, b_b)
-            dev = _assign_device(k, xa4, xb4_b, layers_b, model_mul, sigma2, sigma2_variance, outlier)
+            dev = _assign_device(k, xa4, xb4_b, layers_b, model_mul, sigma2, sigma2_variance, outlier, top_k=top_k)
         else:
-            dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier)
+            dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, top_k=top_k)
         ph.mark("assign")
         if (it > nonrigid_start_iter or nonrigid) and svi is not None:
             nonrigid = True
@@ -650,7 +701,7 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
             al, sd = k.to_host([alpha, SigmaDiag], own_pinned=False)
             model_mul = k.h2d(np.array(al, dtype=np.float64) * np.exp(-np.array(sd, dtype=np.float64) / sigma2))
         dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance,
-                             _spatial_outlier(sigma2, gamma, samples_s, NA, D))
+                             _spatial_outlier(sigma2, gamma, samples_s, NA, D), top_k=top_k)
         k.align_moments(A64, V4, dev["K_NA"], dev["K_NA_spatial"], dev["K_NA_sigma2"], SigmaDiag, dev["PXB"], B64, dev["K_NB"],
                         block, origin=org, extra=dev["scalars"])
         blk = np.array(k.to_host([block])[0], dtype=np.float64)
@@ -671,6 +722,9 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
     if svi is not None:
         out.update(Sp=Sp_run, Sp_spatial=Sp_spatial_run, Sp_sigma2=Sp_sigma2_run, batch_size=bs,
                    batch_perm=np.array(svi["batch_perm"], dtype=np.int64), step_size=step)
+    if top_k is not None and (svi is None or svi["return_mapping"]):   # the mapping: the last (full) assignment's sparse P
+        rows, vals = k.to_host([dev["rows"], dev["vals"]], own_pinned=False)
+        out["P"] = _coo_from_lists(rows, vals, NA)
     if record:
         out["history"] = {q: np.array(v) for q, v in history.items()}
     ph.mark("result")
@@ -725,7 +779,7 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
                        gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                        update_R=True, dtype: str = "float64", device=None, record=True, origin=None, batch_size=None,
                        batch_perm=None, seed=None, return_mapping=False, guidance=None, sparse_calculation_mode=False,
-                       kernel_type="euc"):
+                       kernel_type="euc", sparse_top_k=1024):
     """The SVI mode of the same loop - the reference constructor's default, ``SVI_mode=True``
     (``spateo/alignment/methods/morpho_class.py:136, 283-284, 749-760, 894-896``): every iteration sees ``batch_size`` cells
     of the B slice and blends what it learns into running averages with ``step_size = min(1, 10 / (iter + 1))``.
@@ -749,6 +803,10 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
     (``:1451-1461``).  The reference's SVI result is not translation covariant (the blended ``Sp`` divides the batch's
     sums): ``origin`` only re-centres the assignment's operands, as in ``morpho_iterate``.
 
+    ``sparse_calculation_mode=True`` with ``1 <= sparse_top_k <= 64``: as in ``morpho_iterate``, on every batch (the clamp is
+    to NA, the columns are the batch's); ``P`` (``scipy.sparse.coo_matrix`` (NA, NB)) is returned only with
+    ``return_mapping=True``, from the closing full assignment (``:299-302``).
+
     Not supported (``NotImplementedError``): what ``morpho_iterate`` refuses but ``SVI_mode``.
 
     Returns ``morpho_iterate``'s dict - ``K_NA``, ``K_NB`` (``batch_size``,), ``K_NA_spatial``, ``K_NA_sigma2`` of the last
@@ -757,7 +815,7 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
     a = _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
                            probability_parameters, inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter,
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
-                           record, False, guidance, sparse_calculation_mode, kernel_type, origin)
+                           record, False, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k)
     bs, perm = _svi_arguments(len(a["XB"]), batch_size, batch_perm, seed)
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
                     partial_robust_level, nn_init_weight, update_R, dtype, device, record,
