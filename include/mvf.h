@@ -468,12 +468,22 @@ typedef enum {
     MVF_ASSIGN_SQRT_EUC = 1,  /* "square_euc" / "square_euclidean": its square root                               */
     MVF_ASSIGN_KL = 2,        /* "kl": rows + 0.01, normalised, log(. + 1e-8)                                     */
     MVF_ASSIGN_SYM_KL = 3,    /* "sym_kl": (kl(x, y) + kl(y, x)) / 2 as one product over 2 g features             */
-    MVF_ASSIGN_COS = 4        /* "cos" / "cosine": 1/2 - 1/2 cosine similarity, norms floored at 1e-8             */
+    MVF_ASSIGN_COS = 4,       /* "cos" / "cosine": 1/2 - 1/2 cosine similarity, norms floored at 1e-8             */
+    MVF_ASSIGN_LABEL = 5      /* "label": d_ij = T[la_i][lb_j], a look-up in the label-transfer table (see below) */
 } mvf_assign_metric;
 typedef enum { MVF_ASSIGN_GAUSS = 0, MVF_ASSIGN_COS_PROB = 1, MVF_ASSIGN_PROB = 2 } mvf_assign_prob;
 #define MVF_ASSIGN_MAX_LAYERS 4
 /* one expression / representation layer (a HOST struct of DEVICE pointers): Xp (na x ld) and Yp (nb x ld) in `dtype`, a (na)
- * and b (nb) float64, all from mvf_assign_prepare; prob: exp(-d / (2 param)) | 1 - d | d  (calc_probability, :974-983) */
+ * and b (nb) float64, all from mvf_assign_prepare; prob: exp(-d / (2 param)) | 1 - d | d  (calc_probability, :974-983).
+ * A LABEL layer (metric MVF_ASSIGN_LABEL; `_label_distance_backend`, utils.py:791-832, 908-910) travels in the same fields:
+ *   Xp  the label-transfer table T, K x L FLOAT64 row-major whatever `dtype`;   ld = L >= 1 (any value, not a multiple of 16);
+ *   a (na) / b (nb)  the cells' labels as integers held in float64, 0 <= a_i < K and 0 <= b_j < L, from
+ *       mvf_assign_label_prepare (the kernels read T[a_i ld + b_j] UNCHECKED: that entry point is what puts them in range);
+ *   Yp  NULL (a label layer has no rows per B cell; a non-null Yp under this metric code is refused as a product layer with
+ *       the wrong code, before its Xp / a / b could be read as table and labels).   d_ij = T[a_i][b_j], no clamp, no square root; prob / param as for every other layer.
+ * K is no field: it is an argument of mvf_assign_label_prepare, which rejects K < 1; mvf_assign, mvf_assign_dense,
+ * mvf_assign_topk and mvf_align_gather reject ld < 1 and null Xp / a / b (the gather: b; it does not look at Yp).  Several label layers may share one
+ * table.  (An addition behind version 7: the struct's layout and every signature are unchanged.) */
 typedef struct {
     const void* Xp;
     const void* Yp;
@@ -484,7 +494,8 @@ typedef struct {
     int prob;
     double param;
 } mvf_assign_layer;
-/* features per prepared row: g (2 g for sym_kl) rounded up to a multiple of 16; 0 for g <= 0 or an unknown metric */
+/* features per prepared row: g (2 g for sym_kl) rounded up to a multiple of 16; 0 for g <= 0, an unknown metric or
+ * MVF_ASSIGN_LABEL (a label layer has no prepared rows) */
 int64_t mvf_assign_padded_features(int64_t g, int metric);
 /* Replaces the per-cell part of `_kl_distance_backend` / `_cosine_distance_backend` / `_euc_distance_backend`
  * (utils.py:683-695, 736-739, 780).  layer: n x g float64 (device); side 0 = the A cells (rows of P), 1 = the B cells.
@@ -492,6 +503,11 @@ int64_t mvf_assign_padded_features(int64_t g, int metric);
  * row constant a_i (side 0) or b_j (side 1), formed from the operands as stored.  n == 0 launches nothing. */
 int mvf_assign_prepare(const double* layer, int64_t n, int64_t g, int metric, int side, void* Lp, int64_t ld, double* ab,
                        mvf_dtype dtype, void* stream);
+/* One side of a label layer: labels (n int32, device) -> ab (n float64, device) = min(max(label, 0), classes - 1), the
+ * representation mvf_assign_layer's a (classes = K) / b (classes = L) hold.  The clamp only keeps the table look-up inside
+ * the table; a label outside 0 .. classes - 1 is the CALLER's error to report (spateo_amd.align does, on the host).
+ * classes < 1 is an error; n == 0 launches nothing. */
+int mvf_assign_label_prepare(const int32_t* labels, int64_t n, int64_t classes, double* ab, void* stream);
 size_t mvf_assign_workspace_bytes(int64_t na, int64_t nb);
 /* xa4 (na x 4) = XAHat, xb4 (nb x 4) = coordsB in the x4 layout (dtype); layers: 1 .. MVF_ASSIGN_MAX_LAYERS host structs;
  * model_mul (na float64) = alpha exp(-SigmaDiag / sigma2) (morpho_class.py:1087); spatial_outlier as get_P_core forms it
@@ -572,8 +588,9 @@ int mvf_align_transform(const double* coordsA, const void* VnA4, const double* P
  * batch_idx[j] = perm[(start + j) mod nb], j < bs - with start = (-iter bs) mod nb the batch `_update_batch` (:894-896) draws
  * at iteration `iter` from the initial `batch_perm`.  One launch copies, bit for bit, into contiguous batch buffers: the rows
  * of xb4 (nb x 4, dtype) -> xb4_out (bs x 4), of coordsB (nb x 3 float64) -> coordsB_out (bs x 3) and, per layer l < nlayers
- * (0 .. MVF_ASSIGN_MAX_LAYERS host structs; only Yp, b and ld are read), of layers[l].Yp (nb x ld, dtype) -> Yp_out[l]
- * (bs x ld) and layers[l].b -> b_out[l] (bs float64).  Yp_out / b_out: HOST arrays of nlayers DEVICE pointers.  The prepared
+ * (0 .. MVF_ASSIGN_MAX_LAYERS host structs; only Yp, b, ld and metric are read), of layers[l].Yp (nb x ld, dtype) -> Yp_out[l]
+ * (bs x ld) and layers[l].b -> b_out[l] (bs float64).  For a layer with metric MVF_ASSIGN_LABEL only b (the B labels) is
+ * gathered: Yp and Yp_out[l] are not read and may be NULL, ld >= 1 is the table's row length.  Yp_out / b_out: HOST arrays of nlayers DEVICE pointers.  The prepared
  * rows move as 16-byte chunks, consecutive lanes on consecutive chunks of a row; xb4, xb4_out, Yp and Yp_out must be 16-byte
  * aligned and ld a multiple of 16.  perm: DEVICE int32, a permutation of 0 .. nb - 1 - the CALLER guarantees it (the kernel
  * reads row perm[.] unchecked); 0 <= start < nb, bs <= nb < 2^31.  bs == 0 launches nothing. */

@@ -416,6 +416,12 @@ extern "C" int mvf_align_gather(const int32_t* perm, int64_t nb, int64_t start, 
     for (int l = 0; l < MVF_ASSIGN_MAX_LAYERS; ++l) {
         ga.ysrc[l] = nullptr, ga.ydst[l] = nullptr, ga.bsrc[l] = nullptr, ga.bdst[l] = nullptr, ga.chunks[l] = 0;
         if (l >= nlayers) continue;
+        if (layers[l].metric == MVF_ASSIGN_LABEL) {  // the B labels travel in b; the table has no rows per cell: nothing else to gather
+            MVF_REQUIRE(layers[l].b && b_out[l], "mvf_align_gather: layer %d: null pointer", l);
+            MVF_REQUIRE(layers[l].ld >= 1, "mvf_align_gather: layer %d: a label layer's ld is the table's row length L >= 1", l);
+            ga.bsrc[l] = layers[l].b, ga.bdst[l] = b_out[l];
+            continue;
+        }
         MVF_REQUIRE(layers[l].Yp && layers[l].b && Yp_out[l] && b_out[l], "mvf_align_gather: layer %d: null pointer", l);
         MVF_REQUIRE(layers[l].ld > 0 && layers[l].ld % 16 == 0, "mvf_align_gather: layer %d: ld = %lld is not a positive multiple of 16",
                     l, (long long)layers[l].ld);

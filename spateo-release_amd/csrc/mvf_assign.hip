@@ -9,6 +9,12 @@
 //   kl      X' = p, Y' = log(q + 1e-8), a = sum p log(p + 1e-8), b = 0, s = 1        (p, q: x + 0.01, row-normalised)
 //   sym_kl  X' = [p, log p'], Y' = [log q', q], a = sum p log p' / 2, b = sum q log q' / 2, s = 1/2   (2 G features)
 //   cos     X' = x / max(|x|, 1e-8), Y' likewise, a = 1/2, b = 0, s = 1/2
+// The one metric that is no product of features is "label" (`_label_distance_backend`, utils.py:791-832): d_ij = T[la_i][lb_j],
+// a look-up in the K x L label-transfer table (float64 whatever the cell dtype) with the cells' labels travelling as
+// integers held in a / b.  layer_product takes that branch per layer (label_distances): 8 row labels, 2 column labels and 16
+// table reads per lane and 32 x 32 block, through the cache (the table is a few hundred bytes and every wave reads it; no LDS
+// is spent on it, of which assign_pass1_topk_kernel<., 64> has none to spare).  No clamp, no square root; the probability is
+// formed by the code that forms it for every other layer.
 // mvf_assign_prepare builds X' / Y' (cell dtype, rows zero-padded to a multiple of 16 features) and a / b (float64) in O(N G);
 // the pairwise part is one tile routine: the layer dot products as v_mfma_f64_16x16x4_f64 (operands widened from the cell
 // dtype, float64 accumulation), the spatial distance from the coordinates and all exponent arithmetic in float64 on VALU.
@@ -59,9 +65,11 @@ struct DevLayer {
     int64_t ld;
     double s;       // d = a_i + b_j - s dot
     double nparam;  // gauss: -1 / (2 p)
-    int post;       // 0 none, 1 clamp at 0, 2 clamp at 0 and square root
+    int post;       // 0 none, 1 clamp at 0, 2 clamp at 0 and square root, POST_LABEL: d = X[a_i][b_j], X the float64 table
     int prob;       // mvf_assign_prob
 };
+
+constexpr int POST_LABEL = 3;
 
 struct DevLayers {
     DevLayer l[MAX_LAYERS];
@@ -94,9 +102,90 @@ __device__ __forceinline__ void load4(const T* p, double (&v)[4]) {
     v[0] = (double)u.x, v[1] = (double)u.y, v[2] = (double)u.z, v[3] = (double)u.w;
 }
 
+__device__ __forceinline__ double layer_probability(const DevLayer& ly, double d) {
+    if (ly.prob == MVF_ASSIGN_GAUSS) return exp(d * ly.nparam);
+    if (ly.prob == MVF_ASSIGN_COS_PROB) return 1.0 - d;
+    return d;
+}
+
+// d[a][b][r] = the layer's distance d(row i0 + 16 a + lk + 4 r, column j0 + 16 b + li) for the wave's 32 x 32 block at (i0, j0),
+// a product layer: d = a_i + b_j - s <X'_i, Y'_j>, clamped at 0 / square-rooted as the metric has it.  Rows / columns beyond the
+// arrays are clamped to the last one (finite values, masked by the callers).
+template <typename T>
+__device__ __forceinline__ void product_distances(const DevLayer& ly, int64_t i0, int64_t j0, int64_t na, int64_t nb, int li, int lk,
+                                                  f64x4 (&acc)[2][2]) {
+    const int64_t ld = ly.ld;
+    // A operand of the MFMA: row li of block a, features 4 lk .. 4 lk + 3 of the k-step; B operand: column li of block b
+    const T* pa[2];
+    const T* pb[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        pa[h] = (const T*)ly.X + std::min<int64_t>(i0 + 16 * h + li, na - 1) * ld + 4 * lk;
+        pb[h] = (const T*)ly.Y + std::min<int64_t>(j0 + 16 * h + li, nb - 1) * ld + 4 * lk;
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
+    double na_[2][4], nb_[2][4];  // the next k-step's operands fly during this step's MFMAs
+#pragma unroll
+    for (int h = 0; h < 2; ++h) load4(pa[h], na_[h]), load4(pb[h], nb_[h]);
+    for (int64_t k0 = 0; k0 < ld; k0 += AKS) {
+        double fa[2][4], fb[2][4];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) fa[h][t] = na_[h][t], fb[h][t] = nb_[h][t];
+        if (k0 + AKS < ld) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) load4(pa[h] + k0 + AKS, na_[h]), load4(pb[h] + k0 + AKS, nb_[h]);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+                    acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a][t], fb[b][t], acc[a][b], 0, 0, 0);
+    }
+    // D[row lk + 4 r of block a][column li of block b] sits in acc[a][b][r] of lane (li, lk)
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double ai = ly.a[std::min<int64_t>(i0 + 16 * a + lk + 4 * r, na - 1)];
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const double bj = ly.b[std::min<int64_t>(j0 + 16 * b + li, nb - 1)];
+                double d = (ai + bj) - ly.s * acc[a][b][r];
+                if (ly.post >= 1) d = fmax(d, 0.0);
+                if (ly.post == 2) d = sqrt(d);
+                acc[a][b][r] = d;
+            }
+        }
+}
+
+// The same for a label layer: d = T[la_i][lb_j], T = ly.X (float64, row length ly.ld), the labels integers held in ly.a / ly.b.
+// 8 row labels, 2 column labels and 16 table reads per lane; no clamp, no square root.
+__device__ __forceinline__ void label_distances(const DevLayer& ly, int64_t i0, int64_t j0, int64_t na, int64_t nb, int li, int lk,
+                                                f64x4 (&acc)[2][2]) {
+    const double* tab = (const double*)ly.X;
+    int64_t cj[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) cj[b] = (int64_t)ly.b[std::min<int64_t>(j0 + 16 * b + li, nb - 1)];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double* row = tab + (int64_t)ly.a[std::min<int64_t>(i0 + 16 * a + lk + 4 * r, na - 1)] * ly.ld;
+#pragma unroll
+            for (int b = 0; b < 2; ++b) acc[a][b][r] = row[cj[b]];
+        }
+}
+
 // q[a][b][r] = product over the layers of the probability of d(row i0 + 16 a + lk + 4 r, column j0 + 16 b + li), for the
-// wave's 32 x 32 block at (i0, j0).  Rows / columns beyond the arrays are clamped to the last one (finite values, masked by
-// the callers).
+// wave's 32 x 32 block at (i0, j0).  The branch between the two kinds of layer is the same on every lane; the probability is
+// formed by one piece of code for both.
 template <typename T>
 __device__ __forceinline__ void layer_product(const DevLayers& L, int64_t i0, int64_t j0, int64_t na, int64_t nb, int li, int lk,
                                               f64x4 (&q)[2][2]) {
@@ -106,60 +195,17 @@ __device__ __forceinline__ void layer_product(const DevLayers& L, int64_t i0, in
         for (int b = 0; b < 2; ++b) q[a][b] = f64x4{1.0, 1.0, 1.0, 1.0};
     for (int l = 0; l < L.n; ++l) {
         const DevLayer& ly = L.l[l];
-        const int64_t ld = ly.ld;
-        // A operand of the MFMA: row li of block a, features 4 lk .. 4 lk + 3 of the k-step; B operand: column li of block b
-        const T* pa[2];
-        const T* pb[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            pa[h] = (const T*)ly.X + std::min<int64_t>(i0 + 16 * h + li, na - 1) * ld + 4 * lk;
-            pb[h] = (const T*)ly.Y + std::min<int64_t>(j0 + 16 * h + li, nb - 1) * ld + 4 * lk;
-        }
         f64x4 acc[2][2];
+        if (ly.post == POST_LABEL)
+            label_distances(ly, i0, j0, na, nb, li, lk, acc);
+        else
+            product_distances<T>(ly, i0, j0, na, nb, li, lk, acc);
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int b = 0; b < 2; ++b) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
-        double na_[2][4], nb_[2][4];  // the next k-step's operands fly during this step's MFMAs
+            for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) load4(pa[h], na_[h]), load4(pb[h], nb_[h]);
-        for (int64_t k0 = 0; k0 < ld; k0 += AKS) {
-            double fa[2][4], fb[2][4];
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) fa[h][t] = na_[h][t], fb[h][t] = nb_[h][t];
-            if (k0 + AKS < ld) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) load4(pa[h] + k0 + AKS, na_[h]), load4(pb[h] + k0 + AKS, nb_[h]);
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-                        acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a][t], fb[b][t], acc[a][b], 0, 0, 0);
-        }
-        // D[row lk + 4 r of block a][column li of block b] sits in acc[a][b][r] of lane (li, lk)
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double ai = ly.a[std::min<int64_t>(i0 + 16 * a + lk + 4 * r, na - 1)];
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const double bj = ly.b[std::min<int64_t>(j0 + 16 * b + li, nb - 1)];
-                    double d = (ai + bj) - ly.s * acc[a][b][r];
-                    if (ly.post >= 1) d = fmax(d, 0.0);
-                    if (ly.post == 2) d = sqrt(d);
-                    double p;
-                    if (ly.prob == MVF_ASSIGN_GAUSS) p = exp(d * ly.nparam);
-                    else if (ly.prob == MVF_ASSIGN_COS_PROB) p = 1.0 - d;
-                    else p = d;
-                    q[a][b][r] *= p;
-                }
-            }
+                for (int b = 0; b < 2; ++b) q[a][b][r] *= layer_probability(ly, acc[a][b][r]);
     }
 }
 
@@ -626,6 +672,13 @@ __global__ __launch_bounds__(256) void assign_prepare_kernel(const double* __res
     if (lane == 0) ab[i] = cst;
 }
 
+// labels as the label branch reads them: integers held in float64, clamped into the table
+__global__ __launch_bounds__(256) void assign_label_prepare_kernel(const int32_t* __restrict__ labels, int64_t n, int classes,
+                                                                   double* __restrict__ ab) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) ab[i] = (double)min(max(labels[i], 0), classes - 1);
+}
+
 int64_t padded_features(int64_t g, int metric) { return cdiv(metric == MVF_ASSIGN_SYM_KL ? 2 * g : g, AKS) * AKS; }
 
 template <typename T>
@@ -704,16 +757,24 @@ int assign_entry(const char* who, const void* xa4, int64_t na, const void* xb4, 
     L.n = nlayers;
     for (int l = 0; l < nlayers; ++l) {
         const mvf_assign_layer& s = layers[l];
-        MVF_REQUIRE(s.Xp && s.Yp && s.a && s.b, "%s: null pointer in layer %d", who, l);
-        MVF_REQUIRE(s.ld >= AKS && s.ld % AKS == 0, "%s: layer %d: ld must be a positive multiple of %d", who, l, AKS);
-        MVF_REQUIRE(s.metric >= MVF_ASSIGN_EUC && s.metric <= MVF_ASSIGN_COS, "%s: layer %d: bad metric %d", who, l, s.metric);
+        MVF_REQUIRE(s.metric >= MVF_ASSIGN_EUC && s.metric <= MVF_ASSIGN_LABEL, "%s: layer %d: bad metric %d", who, l, s.metric);
+        const bool label = s.metric == MVF_ASSIGN_LABEL;  // Xp: the table, ld its row length, Yp NULL
+        // (a layer that carries prepared B rows is a product layer: with the label code its Xp / a / b would be read as table
+        // and labels, unchecked - refused before anything is launched)
+        MVF_REQUIRE(!label || !s.Yp, "%s: layer %d: bad metric %d for a layer with Yp set (a label layer has no Yp: pass NULL)", who, l,
+                    s.metric);
+        MVF_REQUIRE(s.Xp && (s.Yp || label) && s.a && s.b, "%s: null pointer in layer %d", who, l);
+        if (label)
+            MVF_REQUIRE(s.ld >= 1 && s.ld < ((int64_t)1 << 31), "%s: layer %d: a label layer's ld is the table's row length L >= 1", who, l);
+        else
+            MVF_REQUIRE(s.ld >= AKS && s.ld % AKS == 0, "%s: layer %d: ld must be a positive multiple of %d", who, l, AKS);
         MVF_REQUIRE(s.prob >= MVF_ASSIGN_GAUSS && s.prob <= MVF_ASSIGN_PROB, "%s: layer %d: bad probability type %d", who, l, s.prob);
         MVF_REQUIRE(s.prob != MVF_ASSIGN_GAUSS || s.param > 0.0, "%s: layer %d: a gauss layer needs a parameter > 0", who, l);
         DevLayer& d = L.l[l];
         d.X = s.Xp, d.Y = s.Yp, d.a = s.a, d.b = s.b, d.ld = s.ld, d.prob = s.prob;
         d.nparam = s.prob == MVF_ASSIGN_GAUSS ? -1.0 / (2.0 * s.param) : 0.0;
         d.s = s.metric <= MVF_ASSIGN_SQRT_EUC ? 2.0 : (s.metric == MVF_ASSIGN_KL ? 1.0 : 0.5);
-        d.post = s.metric == MVF_ASSIGN_EUC ? 1 : (s.metric == MVF_ASSIGN_SQRT_EUC ? 2 : 0);
+        d.post = label ? POST_LABEL : (s.metric == MVF_ASSIGN_EUC ? 1 : (s.metric == MVF_ASSIGN_SQRT_EUC ? 2 : 0));
     }
     for (int l = nlayers; l < MAX_LAYERS; ++l) L.l[l] = L.l[0];
     const double h1 = -1.0 / (2.0 * (sigma2 / sigma2_variance)), h2 = -1.0 / (2.0 * sigma2);
@@ -752,6 +813,18 @@ extern "C" int mvf_assign_prepare(const double* layer, int64_t n, int64_t g, int
     else
         hipLaunchKernelGGL(assign_prepare_kernel<double>, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, layer, n, g, metric, side,
                            (double*)Lp, ld, ab);
+    MVF_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mvf_assign_label_prepare(const int32_t* labels, int64_t n, int64_t classes, double* ab, void* stream) {
+    if (n == 0) return 0;
+    MVF_REQUIRE(n > 0 && cdiv(n, 256) < ((int64_t)1 << 31), "mvf_assign_label_prepare: bad cell count");
+    MVF_REQUIRE(classes >= 1 && classes < ((int64_t)1 << 31), "mvf_assign_label_prepare: need 1 <= classes < 2^31, got %lld",
+                (long long)classes);
+    MVF_REQUIRE(labels && ab, "mvf_assign_label_prepare: null pointer");
+    hipLaunchKernelGGL(assign_label_prepare_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, labels, n,
+                       (int)classes, ab);
     MVF_LAUNCH_CHECK();
     return 0;
 }

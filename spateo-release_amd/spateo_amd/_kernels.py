@@ -604,9 +604,20 @@ class HipKernels:
         return Lp, ab, ld
 
     @_on_device
+    def assign_label_prepare(self, labels, classes):
+        """One side of a label layer: host integer labels (n,), validated by the caller to lie in 0 .. classes - 1 -> device
+        float64 (n,), the labels as mvf_assign_layer's a / b hold them  (mvf_assign_label_prepare)."""
+        lab = self.h2d(np.ascontiguousarray(labels, dtype=np.int32))
+        ab = self.empty(lab.shape[0], dtype=torch.float64)
+        _lib.check(self.lib.mvf_assign_label_prepare(_ptr(lab), lab.shape[0], int(classes), _ptr(ab), self._stream()),
+                   "mvf_assign_label_prepare")
+        return ab
+
+    @_on_device
     def assign(self, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, spatial_outlier, dense=False):
         """The fused assignment step (mvf_assign / mvf_assign_dense).  layers: [(Xp, Yp, a, b, ld, metric, prob, param)]
-        of device tensors from assign_prepare.  Returns device float64 tensors {K_NA, K_NB, K_NA_spatial, K_NA_sigma2,
+        of device tensors from assign_prepare; a label layer is (table (K, L) float64, None, labels A, labels B, L,
+        _lib.ASSIGN_LABEL, prob, param) with the labels from assign_label_prepare.  Returns device float64 tensors {K_NA, K_NB, K_NA_spatial, K_NA_sigma2,
         PXB (na, 3), scalars (1,) = sum P_sigma2 d [, P (na, nb)]}."""
         na, nb = xa4.shape[0], xb4.shape[0]
         f64 = torch.float64
@@ -700,10 +711,13 @@ class HipKernels:
         if xb4_out.shape[0] < bs or B_out.shape[0] < bs or len(Yp_out) != len(layers) or len(b_out) != len(layers):
             raise ValueError("align_gather: the batch buffers do not fit the batch")
         arr = (_lib.AssignLayer * max(len(layers), 1))()
-        for s, (_, Yp, _, b, ld, *_) , Yo, bo in zip(arr, layers, Yp_out, b_out):
-            if Yp.shape != (nb, ld) or b.shape != (nb,) or Yo.shape[0] < bs or Yo.shape[1] != ld or bo.shape[0] < bs:
+        for s, (_, Yp, _, b, ld, metric, *_), Yo, bo in zip(arr, layers, Yp_out, b_out):
+            if metric == _lib.ASSIGN_LABEL:     # only the B labels (b) are gathered: the table has no rows per cell
+                if b.shape != (nb,) or bo.shape[0] < bs:
+                    raise ValueError("align_gather: a layer's buffers do not fit")
+            elif Yp.shape != (nb, ld) or b.shape != (nb,) or Yo.shape[0] < bs or Yo.shape[1] != ld or bo.shape[0] < bs:
                 raise ValueError("align_gather: a layer's buffers do not fit")
-            s.Yp, s.b, s.ld = _ptr(Yp), _ptr(b), int(ld)
+            s.Yp, s.b, s.ld, s.metric = _ptr(Yp), _ptr(b), int(ld), int(metric)
         import ctypes
 
         vp = ctypes.c_void_p * max(len(layers), 1)

@@ -30,7 +30,9 @@ MVF_COMM_ID_BYTES = 128
 RED_SUM, RED_MIN = 0, 1
 GRAM_TILES, GRAM_RHS, GRAM_REDUCE, GRAM_REDUCE_RHS = 1, 2, 4, 8
 RK45_UNIFORM_TIME, RK45_ARC_LENGTH = 0, 1
-ASSIGN_METRICS = {"euc": 0, "euclidean": 0, "square_euc": 1, "square_euclidean": 1, "kl": 2, "sym_kl": 3, "cos": 4, "cosine": 4}
+ASSIGN_METRICS = {"euc": 0, "euclidean": 0, "square_euc": 1, "square_euclidean": 1, "kl": 2, "sym_kl": 3, "cos": 4, "cosine": 4,
+                  "label": 5}
+ASSIGN_LABEL = 5  # MVF_ASSIGN_LABEL: the layer is a pair of label vectors and the shared label-transfer table
 ASSIGN_PROBS = {"gauss": 0, "gaussian": 0, "cos": 1, "cosine": 1, "prob": 2}
 ASSIGN_MAX_LAYERS = 4
 ASSIGN_TOPK_MAX = 64  # MVF_ASSIGN_TOPK_MAX: the largest sparse_top_k mvf_assign_topk keeps per column
@@ -107,6 +109,7 @@ SIGNATURES = {
                                 _d, _d, _i, _i, _i, _p, _p, _p, _i, _p]),
     "mvf_assign_padded_features": (_i64, [_i64, _i]),
     "mvf_assign_prepare": (_i, [_p, _i64, _i64, _i, _i, _p, _i64, _p, _i, _p]),
+    "mvf_assign_label_prepare": (_i, [_p, _i64, _i64, _p, _p]),
     "mvf_assign_workspace_bytes": (_sz, [_i64, _i64]),
     "mvf_assign": (_i, [_p, _i64, _p, _i64, C.POINTER(AssignLayer), _i, _p, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _sz, _i,
                         _p]),

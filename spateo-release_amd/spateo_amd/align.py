@@ -19,7 +19,8 @@ from . import _runtime as _rt
 from .engine import SparseVFCEngine, _consistent_K
 from .vectorfield import vector_field_function
 
-__all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate", "morpho_iterate_svi"]
+__all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate", "morpho_iterate_svi",
+           "label_transfer_matrix"]
 
 RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
 
@@ -41,18 +42,70 @@ def _sparse_top_k(sparse_calculation_mode, sparse_top_k, return_P=False):
     return int(sparse_top_k)
 
 
+def label_transfer_matrix(catA, catB, label_transfer_dict=None):
+    """The K x L label-transfer table of a ``"label"`` layer from the two slices' category lists, as the reference builds it
+    (``check_label_transfer`` / ``generate_label_transfer_dict``, ``spateo/alignment/methods/utils.py:264-312, 376-436``):
+    ``T[j, k] = label_transfer_dict[catA[j]][catB[k]]``, rounded to float32 as there and returned as float64.  Without a
+    dictionary the default one is used: 10 where both slices carry the same category and 1 elsewhere, every row divided by
+    its sum ``+ 1e-8``.  Labels are then the positions in ``catA`` / ``catB`` (``.cat.codes`` of the ``obs`` column)."""
+    if label_transfer_dict is not None and not isinstance(label_transfer_dict, dict):
+        raise ValueError("label_transfer_dict should be a list or a dictionary.")  # (utils.py:300)
+    catA, catB = list(catA), list(catB)
+    if label_transfer_dict is None:
+        raw = np.array([[10.0 if ca == cb else 1.0 for cb in catB] for ca in catA], dtype=np.float64).reshape(len(catA), len(catB))
+        table = raw / (raw.sum(1, keepdims=True) + 1e-8)
+    else:
+        for ca in catA:
+            if ca not in label_transfer_dict:
+                raise KeyError(f"Category '{ca}' from catA not found in label_transfer_dict.")
+            for cb in catB:
+                if cb not in label_transfer_dict[ca]:
+                    raise KeyError(f"Category '{cb}' from catB not found in label_transfer_dict['{ca}'].")
+        table = np.array([[label_transfer_dict[ca][cb] for cb in catB] for ca in catA], dtype=np.float64).reshape(len(catA), len(catB))
+    return table.astype(np.float32).astype(np.float64)
+
+
+class LabelTransferRequired(AssertionError, NotImplementedError):
+    """A ``"label"`` layer without ``label_transfer``: the reference's assertion (``calc_distance``, ``utils.py:909``) with its
+    text.  Also a ``NotImplementedError``, which is what this call - a label layer and no table, the only one earlier versions
+    could be given - raised when the metric was refused: callers that catch it to fall back keep working."""
+
+
+def _label_arguments(A, B, NA, NB, table):
+    """One label layer's two label vectors (validated, int64).  `table`: the validated K x L table or None."""
+    A, B = np.asarray(A), np.asarray(B)
+    if table is None:
+        raise LabelTransferRequired("label_transfer must be provided for metric 'label'.")  # calc_distance (utils.py:909)
+    assert A.ndim == 1, "X should be a 1-dimensional array."                            # _label_distance_backend (:818-828)
+    assert B.ndim == 1, "Y should be a 1-dimensional array."
+    assert np.issubdtype(A.dtype, np.integer) and np.issubdtype(B.dtype, np.integer), "X should contain integer values."
+    if len(A) != NA or len(B) != NB:
+        raise ValueError("every layer must have one row per cell of its slice")
+    K, L = table.shape
+    if len(A) and (A.min() < 0 or A.max() >= K):
+        raise ValueError(f"a label layer's A labels must lie in 0 .. {K - 1}, the rows of label_transfer")
+    if len(B) and (B.min() < 0 or B.max() >= L):
+        raise ValueError(f"a label layer's B labels must lie in 0 .. {L - 1}, the columns of label_transfer")
+    return A.astype(np.int64), B.astype(np.int64)
+
+
 def _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
-                          probability_parameters, return_P):
-    """Validation of update_assignment (no device needed): the arrays as float64 and the per-layer (metric, probability
-    type, parameter) codes of include/mvf.h."""
+                          probability_parameters, return_P, label_transfer=None):
+    """Validation of update_assignment (no device needed): the arrays as float64 (a label layer's as int64), the per-layer
+    (metric, probability type, parameter) codes of include/mvf.h and the label-transfer table as float64 (K, L) or None."""
     XA, XB = np.asarray(XAHat, dtype=np.float64), np.asarray(coordsB, dtype=np.float64)
     if XA.ndim != 2 or XB.ndim != 2 or XA.shape[1] != XB.shape[1]:
         raise AssertionError("X and Y do not have the same number of features.")  # _euc_distance_backend (utils.py:775)
     if XA.shape[1] not in (2, 3):
         raise NotImplementedError(f"update_assignment: spatial coordinates must be 2-D or 3-D, got D = {XA.shape[1]}")
-    LA = [np.asarray(a, dtype=np.float64) for a in (exp_layers_A if isinstance(exp_layers_A, (list, tuple)) else [exp_layers_A])]
-    LB = [np.asarray(b, dtype=np.float64) for b in (exp_layers_B if isinstance(exp_layers_B, (list, tuple)) else [exp_layers_B])]
+    LA = list(exp_layers_A) if isinstance(exp_layers_A, (list, tuple)) else [exp_layers_A]
+    LB = list(exp_layers_B) if isinstance(exp_layers_B, (list, tuple)) else [exp_layers_B]
     n_layers = len(LA)
+    table = None
+    if label_transfer is not None:
+        table = np.ascontiguousarray(label_transfer, dtype=np.float64)
+        if table.ndim != 2 or table.shape[0] < 1 or table.shape[1] < 1 or not np.isfinite(table).all():
+            raise ValueError("label_transfer must be a finite 2-D (K, L) array with K, L >= 1")
     as_list = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n_layers  # noqa: E731
     metrics, kinds = as_list(dissimilarity), as_list(probability_type)
     params = [None] * n_layers if probability_parameters is None else as_list(probability_parameters)
@@ -62,16 +115,17 @@ def _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilar
     if n_layers > _lib.ASSIGN_MAX_LAYERS:
         raise NotImplementedError(f"update_assignment: at most {_lib.ASSIGN_MAX_LAYERS} layers are supported, got {n_layers}")
     codes = []
-    for A, B, met, kind, par in zip(LA, LB, metrics, kinds, params):
-        if met == "label":
-            raise NotImplementedError("update_assignment: the 'label' metric (a label-transfer table lookup, not a product "
-                                      "of features) is not supported")
+    for l, (met, kind, par) in enumerate(zip(metrics, kinds, params)):
         if met not in _lib.ASSIGN_METRICS:
             raise ValueError(f"Unsupported dissimilarity metric: {met}")
-        if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1]:
-            raise AssertionError("X and Y do not have the same number of features.")
-        if len(A) != len(XA) or len(B) != len(XB):
-            raise ValueError("every layer must have one row per cell of its slice")
+        if met == "label":
+            LA[l], LB[l] = _label_arguments(LA[l], LB[l], len(XA), len(XB), table)
+        else:
+            A, B = LA[l], LB[l] = np.asarray(LA[l], dtype=np.float64), np.asarray(LB[l], dtype=np.float64)
+            if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1]:
+                raise AssertionError("X and Y do not have the same number of features.")
+            if len(A) != len(XA) or len(B) != len(XB):
+                raise ValueError("every layer must have one row per cell of its slice")
         if str(kind).lower() not in _lib.ASSIGN_PROBS:
             raise ValueError(f"Unsupported probability type: {kind}")  # calc_probability (utils.py:983)
         prob = _lib.ASSIGN_PROBS[str(kind).lower()]
@@ -81,17 +135,24 @@ def _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilar
     if return_P and len(XA) * len(XB) > RETURN_P_MAX_ENTRIES:
         raise ValueError(f"return_P=True materialises NA x NB = {len(XA) * len(XB)} entries; the cap is "
                          f"{RETURN_P_MAX_ENTRIES} (align.RETURN_P_MAX_ENTRIES)")
-    return XA, XB, LA, LB, codes
+    return XA, XB, LA, LB, codes, table
 
 
 def _spatial_outlier(sigma2, gamma, samples_s, NA, D):
     return float(np.power(2 * np.pi * sigma2, D / 2) * (1 - gamma) / (gamma * (samples_s * NA)))  # utils.py:1051-1053
 
 
-def _prepare_layers(k, LA, LB, codes):
-    """Upload and prepare both sides of every layer (mvf_assign_prepare): the operands no iteration changes."""
+def _prepare_layers(k, LA, LB, codes, table=None):
+    """Upload and prepare both sides of every layer (mvf_assign_prepare; a label layer: mvf_assign_label_prepare and the
+    one float64 table its kind shares): the operands no iteration changes."""
     layers = []
+    T = None
     for A, B, (metric, prob, param) in zip(LA, LB, codes):
+        if metric == _lib.ASSIGN_LABEL:
+            T = k.h2d(table) if T is None else T
+            K, L = table.shape
+            layers.append((T, None, k.assign_label_prepare(A, K), k.assign_label_prepare(B, L), L, metric, prob, param))
+            continue
         Xp, a, ld = k.assign_prepare(A, metric, 0)
         Yp, b, _ = k.assign_prepare(B, metric, 1)
         layers.append((Xp, Yp, a, b, ld, metric, prob, param))
@@ -119,7 +180,8 @@ def _coo_from_lists(rows, vals, NA):
 
 def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity, probability_type,
                       probability_parameters, sigma2, alpha, SigmaDiag, gamma, samples_s, sigma2_variance=1.0,
-                      dtype: str = "float64", device=None, return_P=False, sparse_calculation_mode=False, sparse_top_k=1024):
+                      dtype: str = "float64", device=None, return_P=False, sparse_calculation_mode=False, sparse_top_k=1024,
+                      label_transfer=None):
     """The assignment step of Spateo's alignment, ``Morpho_pairwise._update_assignment_P``
     (``spateo/alignment/methods/morpho_class.py:1071-1200``) followed by ``get_P_core`` on the dense path
     (``spateo/alignment/methods/utils.py:993-1096``; ``use_chunk`` changes nothing mathematically), on the MI355X as one
@@ -132,7 +194,18 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
     ``"cos"`` / ``"cosine"``; ``probability_type[l]`` in ``"gauss"`` (``exp(-d / (2 probability_parameters[l]))``),
     ``"cos"`` (``1 - d``), ``"prob"`` (``d``); ``alpha`` and ``SigmaDiag`` (NA,); the rest scalars.  ``dtype`` is the
     storage of the coordinates and of the prepared layer operands; distances, exponents and every sum are float64 in
-    both modes.  Not supported (``NotImplementedError``): the ``"label"`` metric, ``sparse_calculation_mode`` with
+    both modes.
+
+    ``dissimilarity[l] = "label"`` (what the reference forces for ``rep_field="obs"``, ``morpho_class.py:412-415``, usually
+    with ``probability_type[l] = "prob"``): ``exp_layers_A[l]`` (NA,) and ``exp_layers_B[l]`` (NB,) are 1-D INTEGER arrays,
+    one label per cell, and the layer's distance is ``label_transfer[labelA_i, labelB_j]`` (``_label_distance_backend``,
+    ``utils.py:791-832``) - ``label_transfer`` (K, L), finite, required then (``label_transfer_matrix`` builds the reference's
+    from the category lists); several label layers share it, as in ``calc_distance``.  The table stays float64 in both modes.
+    A float or 2-D label array, a missing table: the reference's ``AssertionError``; a label outside the table, a table that
+    is not 2-D and finite: ``ValueError``.  The three probability types apply to it as to any distance; ``"gauss"`` needs its
+    parameter.
+
+    Not supported (``NotImplementedError``): ``sparse_calculation_mode`` with
     ``sparse_top_k`` above ``_lib.ASSIGN_TOPK_MAX`` = 64 (the reference constructor's default, 1024, among them), more than
     4 layers, D outside {2, 3}.
 
@@ -157,8 +230,8 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
     if dtype not in ("float32", "float64"):
         raise ValueError("dtype must be 'float32' or 'float64'")
     top_k = _sparse_top_k(sparse_calculation_mode, sparse_top_k, return_P)
-    XA, XB, LA, LB, codes = _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
-                                                  probability_parameters, return_P)
+    XA, XB, LA, LB, codes, table = _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
+                                                         probability_type, probability_parameters, return_P, label_transfer)
     NA, D = XA.shape
     al, sd = np.asarray(alpha, dtype=np.float64).reshape(-1), np.asarray(SigmaDiag, dtype=np.float64).reshape(-1)
     if len(al) != NA or len(sd) != NA:
@@ -178,7 +251,7 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
     model_mul = al * np.exp(-sd / sigma2)                                                   # morpho_class.py:1087
     outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
     k = _rt._make_kernels(device, dtype)
-    layers = _prepare_layers(k, LA, LB, codes)
+    layers = _prepare_layers(k, LA, LB, codes, table)
     dev = _assign_device(k, k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, outlier,
                          dense=bool(return_P), top_k=top_k)
     keys = list(names) + ["PXB", "scalars"] + (["P"] if return_P else []) + (["rows", "vals"] if top_k is not None else [])
@@ -365,7 +438,7 @@ def _digamma(x):
 def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type, probability_parameters,
                        inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, kappa, gamma_a, gamma_b,
                        partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype, record, SVI_mode, guidance,
-                       sparse_calculation_mode, kernel_type, origin, sparse_top_k=1024):
+                       sparse_calculation_mode, kernel_type, origin, sparse_top_k=1024, label_transfer=None):
     """Validation of morpho_iterate (no device needed).  Returns the arguments as float64 arrays / floats."""
     if dtype not in ("float32", "float64"):
         raise ValueError("dtype must be 'float32' or 'float64'")
@@ -378,8 +451,8 @@ def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilari
         raise NotImplementedError(f"morpho_iterate: kernel_type={kernel_type!r} is not supported (only the Euclidean 'euc' "
                                   f"kernel; 'geodist' needs the graph distances of the inducing variables)")
     top_k = _sparse_top_k(sparse_calculation_mode, sparse_top_k)
-    XA, XB, LA, LB, codes = _assignment_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
-                                                  probability_parameters, False)
+    XA, XB, LA, LB, codes, table = _assignment_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
+                                                         probability_type, probability_parameters, False, label_transfer)
     NA, D = XA.shape
     if NA == 0 or len(XB) == 0:
         raise ValueError("morpho_iterate: both slices need at least one cell")
@@ -416,7 +489,7 @@ def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilari
     org = np.zeros(3)
     if origin is not None:
         org[:D] = np.asarray(origin, dtype=np.float64).reshape(D)
-    return dict(XA=XA, XB=XB, LA=LA, LB=LB, codes=codes, ctrl=ctrl, kappa=kap, inliers=inl, samples_s=float(samples_s),
+    return dict(XA=XA, XB=XB, LA=LA, LB=LB, codes=codes, table=table, ctrl=ctrl, kappa=kap, inliers=inl, samples_s=float(samples_s),
                 origin=org, sigma2_end=None if sigma2_end is None else float(sigma2_end), top_k=top_k)
 
 
@@ -509,7 +582,7 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
                    inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter=0, kappa=1.0, gamma_a=1.0,
                    gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                    update_R=True, dtype: str = "float64", device=None, record=True, origin=None, SVI_mode=False, guidance=None,
-                   sparse_calculation_mode=False, kernel_type="euc", sparse_top_k=1024):
+                   sparse_calculation_mode=False, kernel_type="euc", sparse_top_k=1024, label_transfer=None):
     """The iteration loop of Spateo's pairwise alignment on the MI355X: the non-SVI, dense-path body of
     ``Morpho_pairwise.run`` (``spateo/alignment/methods/morpho_class.py:280-294``: assignment -> gamma -> alpha -> non-rigid
     -> rigid -> ``XAHat`` -> sigma2) for ``max_iter`` iterations from the state ``_initialize_variational_variables`` sets
@@ -525,7 +598,8 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     sigma2 with its floors 1e-3 and, below iteration 100, 1e-2 (``:1426-1435``), and ``sigma2_variance``.
 
     ``coordsA`` (NA, D) / ``coordsB`` (NB, D), D in {2, 3}, as the caller has normalised them; layers, ``dissimilarity``,
-    ``probability_type``, ``probability_parameters`` as ``update_assignment`` takes them; ``inducing_variables`` (M, D) and
+    ``probability_type``, ``probability_parameters`` and ``label_transfer`` (for ``"label"`` layers: 1-D integer label arrays, prepared
+    once with the other layers) as ``update_assignment`` takes them; ``inducing_variables`` (M, D) and
     ``beta`` as ``update_nonrigid``; ``sigma2`` the initial value (``_init_guess_sigma2`` in the reference).  Defaults are the
     reference constructor's (``morpho_class.py:133-152``: ``nn_init_weight=1.0``, ``gamma_a = gamma_b = 1.0``, ``kappa=1.0``,
     ``partial_robust_level=10``); ``kappa`` is a float or an (NA,) array; ``samples_s`` defaults to the larger bounding-box
@@ -545,7 +619,7 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
 
     Not supported (``NotImplementedError``): ``SVI_mode`` (``morpho_iterate_svi`` runs it), ``guidance``,
     ``sparse_calculation_mode`` with ``sparse_top_k`` above 64 (the default, 1024, is the reference constructor's,
-    ``morpho_class.py:140``), the ``"label"`` metric, ``kernel_type="geodist"`` (anything but ``"euc"``), and what
+    ``morpho_class.py:140``), ``kernel_type="geodist"`` (anything but ``"euc"``), and what
     ``update_assignment`` / ``update_nonrigid`` refuse (more than 4 layers, D outside {2, 3}).
 
     Returns a dict of host float64: ``R``, ``t``, ``Coff``, ``VnA``, ``RnA``, ``XAHat``, ``optimal_R``, ``optimal_t``,
@@ -555,7 +629,7 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     a = _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
                            probability_parameters, inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter,
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
-                           record, SVI_mode, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k)
+                           record, SVI_mode, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer)
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
                     partial_robust_level, nn_init_weight, update_R, dtype, device, record)
 
@@ -572,7 +646,7 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
     f64 = torch.float64
     ph = _rt._Phases(k.device)   # {setup, assign, nonrigid, glue, result: seconds} in last_fit_profile() under PROFILE_FITS
     # ---- uploaded / built once ----
-    layers = _prepare_layers(k, a["LA"], a["LB"], a["codes"])
+    layers = _prepare_layers(k, a["LA"], a["LB"], a["codes"], a["table"])
     has_origin = bool(np.any(org != 0.0))
     xa4 = k.to_x4(XA, org[:D] if has_origin else None)       # XAHat of iteration 0 = coordsA, as update_assignment uploads it
     xb4 = k.to_x4(XB, org[:D] if has_origin else None)
@@ -594,7 +668,9 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
         bs, NB_eff = int(svi["batch_size"]), int(svi["batch_size"])
         perm = k.h2d(svi["batch_perm"])
         xb4_b, B64_b = k.empty(bs, 4), k.empty(bs, 3, dtype=f64)
-        Yp_b, b_b = [k.empty(bs, L[4]) for L in layers], [k.empty(bs, dtype=f64) for L in layers]
+        # (a label layer has no rows per B cell: its batch is the gathered labels b alone)
+        Yp_b = [None if L[5] == _lib.ASSIGN_LABEL else k.empty(bs, L[4]) for L in layers]
+        b_b = [k.empty(bs, dtype=f64) for L in layers]
         layers_b = [(L[0], Yb, L[2], bb) + tuple(L[4:]) for L, Yb, bb in zip(layers, Yp_b, b_b)]
         PXB_term.zero_()                                       # the running PXB_term and SigmaInv start at 0 (:759-760)
         S_run = k.zeros(m, m, dtype=f64)
@@ -779,7 +855,7 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
                        gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                        update_R=True, dtype: str = "float64", device=None, record=True, origin=None, batch_size=None,
                        batch_perm=None, seed=None, return_mapping=False, guidance=None, sparse_calculation_mode=False,
-                       kernel_type="euc", sparse_top_k=1024):
+                       kernel_type="euc", sparse_top_k=1024, label_transfer=None):
     """The SVI mode of the same loop - the reference constructor's default, ``SVI_mode=True``
     (``spateo/alignment/methods/morpho_class.py:136, 283-284, 749-760, 894-896``): every iteration sees ``batch_size`` cells
     of the B slice and blends what it learns into running averages with ``step_size = min(1, 10 / (iter + 1))``.
@@ -790,7 +866,8 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
     ``j < batch_size`` - the reference's head-then-``roll``.  Everything else as ``morpho_iterate`` takes it.
 
     What differs from the dense loop, per iteration: the assignment runs on NA x the batch (``mvf_align_gather`` copies the
-    batch's rows of the coordinates and of every prepared B layer on the device, ``mvf_assign`` follows); ``Sp``,
+    batch's rows of the coordinates and of every prepared B layer - of a ``"label"`` layer the B labels - on the device,
+    ``mvf_assign`` follows); ``Sp``,
     ``Sp_spatial``, ``Sp_sigma2`` are blended (``:1178-1181``) and divide this batch's sums in ``_update_rigid`` and
     ``_update_sigma2``; gamma counts ``batch_size`` cells (``:1214-1218``); alpha (``mvf_align_alpha_svi``, ``:1240-1247``),
     ``PXB_term`` (``mvf_align_transform_svi``) and ``SigmaInv`` (``mvf_lincomb3``, on the device) are blended with their
@@ -815,7 +892,7 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
     a = _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
                            probability_parameters, inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter,
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
-                           record, False, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k)
+                           record, False, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer)
     bs, perm = _svi_arguments(len(a["XB"]), batch_size, batch_perm, seed)
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
                     partial_robust_level, nn_init_weight, update_R, dtype, device, record,
