@@ -539,6 +539,25 @@ int mvf_assign_topk(const void* xa4, int64_t na, const void* xb4, int64_t nb, co
                     double* K_NA, double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars,
                     int32_t* rows, double* vals, void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream);
 
+/* Column statistics of ONE layer's na x nb distance matrix d_ij, which is never written: what the code in front of the
+ * reference's loop reduces its matrices to (`_init_guess_sigma2`, utils.py:1339-1354; `_init_probability_parameters`,
+ * morpho_class.py:771-820; the mutual nearest neighbours of `_coarse_rigid_alignment`, :898-1041).  layer: ONE host struct as
+ * mvf_assign_prepare / mvf_assign_label_prepare fill it (prob and param are not read); spatial distances are an "euc" layer
+ * of the D coordinates.  Out (device, float64 whatever `dtype`), per column j over the rows i < na:
+ *   cmin (nb)          min_i d_ij;
+ *   rows / vals        for k > 0 (nb x k_eff int32 / float64, k_eff = min(k, na), mvf_assign_topk's layout): column j's k_eff
+ *                      smallest entries in the total order (value ascending, row ascending); not touched for k == 0 (may be NULL);
+ *   sums (2)           sum_ij d_ij and sum_ij d_ij^2 over the na x nb entries.
+ * 0 <= k <= MVF_ASSIGN_TOPK_MAX.  The statistics of every ROW are the same call with the operands exchanged (Xp <-> Yp, a <-> b,
+ * na <-> nb; a label layer: the transposed table and its row length): both kinds of distance are symmetric in how their
+ * operands enter, and "kl" keeps its asymmetry because the operands are prepared per side.  Pass 1's tiling and row split;
+ * every split writes partials that are combined in split order, minima and lists do not depend on the order: no
+ * floating-point atomics, two calls give the same bits.  na < 1, nb < 1, k outside the range, a null pointer, a bad layer and a
+ * small workspace are errors, reported before anything is launched.  (An addition behind version 7.) */
+size_t mvf_assign_layer_stats_workspace_bytes(int64_t na, int64_t nb, int k); /* 0 for an empty side or k outside the range */
+int mvf_assign_layer_stats(const mvf_assign_layer* layer, int64_t na, int64_t nb, int k, double* cmin, int32_t* rows,
+                           double* vals, double* sums, void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream);
+
 /* ---- alignment: the O(N) glue of one iteration between the assignment and the non-rigid update (mvf_align.hip) ----------
  * With mvf_assign, mvf_gram, mvf_solve_minnorm*, mvf_apply and mvf_pinv_diag these three make the loop of
  * `Morpho_pairwise.run` (spateo/alignment/methods/morpho_class.py:280-294) device resident: per iteration the host reads

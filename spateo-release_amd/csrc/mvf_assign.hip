@@ -37,6 +37,12 @@
 // wave per column merges the row splits' lists, applies c3 and writes rows / vals / K_NB; pass 2 adds an entry to K_NA / PXB
 // only if its row index is in the column's list.  The k largest of a set under a total order do not depend on the order of
 // insertion: the lists, and with them every output, are the same bits on every call.
+//
+// mvf_assign_layer_stats (what the reference computes in front of its loop from three more materialised matrices:
+// `_init_guess_sigma2`, `_init_probability_parameters`, the nearest voxels of `_coarse_rigid_alignment`) reduces ONE layer's
+// distance matrix, on the same tile routine and with pass 1's grid, to per-column minima, per-column lists of the k smallest
+// entries (the lists of mvf_assign_topk with the order turned round) and the sums of d and d^2; the statistics of the rows are
+// the same call with the operands exchanged.
 #include <climits>
 
 #include "mvf_common.h"
@@ -469,6 +475,191 @@ __global__ __launch_bounds__(256) void assign_topk_merge_kernel(const double* __
     if (lane == 0) K_NB[j] = sum;
 }
 
+// ---- mvf_assign_layer_stats: column statistics of ONE layer's distance matrix, for the alignment's start state (what
+// `_init_guess_sigma2`, `_init_probability_parameters` and `_coarse_rigid_alignment` reduce their na x nb matrices to).  Pass 1's
+// tiling, row split and workgroup shape; per column and row split: the minimum, the sum and the sum of squares of d over the
+// live rows and, for KC > 0, the k SMALLEST entries as pass 1 of mvf_assign_topk keeps the k largest: the same sorted lists in
+// LDS and the same staging, in the total order (value ascending, row ascending); unused places hold (+inf, INT_MAX).
+// part[split][{min, sum, sum of squares}][nb_pad]
+__device__ __forceinline__ bool stats_before(double v, int r, double w, int s) { return v < w || (v == w && r < s); }
+
+template <typename T, int KC>
+__global__ __launch_bounds__(256) void layer_stats_kernel(DevLayer ly, int64_t na, int64_t nb, int64_t rtiles, int64_t nb_pad,
+                                                          int k, double* __restrict__ part, double* __restrict__ lv,
+                                                          int* __restrict__ lr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, lk = lane >> 4, wi = wave >> 1, wj = wave & 1;
+    const int64_t j0 = (int64_t)blockIdx.x * AT + 32 * wj;
+    const int64_t t_lo = rtiles * blockIdx.y / gridDim.y, t_hi = rtiles * (blockIdx.y + 1) / gridDim.y;
+    __shared__ double lval[KC ? KC : 1][AT];
+    __shared__ int lrow[KC ? KC : 1][AT];
+    __shared__ double red[4][8][AT];  // after the tiles: the partial statistics; between them: the staged candidates
+    __shared__ int scnt[AT];
+    double(*sval)[AT] = reinterpret_cast<double(*)[AT]>(&red[0][0][0]);  // [TOPK_STAGE][AT]
+    int(*srow)[AT] = reinterpret_cast<int(*)[AT]>(&red[2][0][0]);        // [TOPK_STAGE][AT]
+    static_assert(TOPK_STAGE * AT * sizeof(double) <= 2 * 8 * AT * sizeof(double) &&
+                      TOPK_STAGE * AT * sizeof(int) <= 2 * 8 * AT * sizeof(double),
+                  "the staged values lie in red[0..1], their rows in red[2..3]");
+    if (KC) {
+        for (int e = threadIdx.x; e < k * AT; e += 256) lval[e / AT][e % AT] = HUGE_VAL, lrow[e / AT][e % AT] = INT_MAX;
+        if (threadIdx.x < AT) scnt[threadIdx.x] = 0;
+        __syncthreads();
+    }
+    int col[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) col[b] = 32 * wj + 16 * b + li;
+    double mn[2] = {HUGE_VAL, HUGE_VAL}, s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
+    for (int64_t t = t_lo; t < t_hi; ++t) {
+        const int64_t i0 = t * AT + 32 * wi;
+        f64x4 d[2][2];
+        if (ly.post == POST_LABEL)
+            label_distances(ly, i0, j0, na, nb, li, lk, d);
+        else
+            product_distances<T>(ly, i0, j0, na, nb, li, lk, d);
+        unsigned pend = 0;  // bit 8 a + 2 r + b: d[a][b][r] beats the last entry of its column's list and is not staged yet
+        double tv[2] = {0.0, 0.0};
+        int tr[2] = {0, 0};
+        if (KC) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b) tv[b] = lval[k - 1][col[b]], tr[b] = lrow[k - 1][col[b]];
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t i = i0 + 16 * a + lk + 4 * r;
+                if (i >= na) continue;  // a padded row (clamped to the last one by the tile routine) is in no statistic
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const double v = d[a][b][r];
+                    mn[b] = fmin(mn[b], v);
+                    s1[b] += v;
+                    s2[b] += v * v;
+                    if (KC && stats_before(v, (int)i, tv[b], tr[b])) pend |= 1u << (8 * a + 2 * r + b);
+                }
+            }
+        while (KC && __syncthreads_or(pend != 0)) {
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        const unsigned bit = 1u << (8 * a + 2 * r + b);
+                        if (pend & bit) {
+                            const int slot = atomicAdd(&scnt[col[b]], 1);
+                            if (slot < TOPK_STAGE) {
+                                sval[slot][col[b]] = d[a][b][r];
+                                srow[slot][col[b]] = (int)(i0 + 16 * a + lk + 4 * r);
+                                pend &= ~bit;
+                            }
+                        }
+                    }
+            __syncthreads();
+            if (threadIdx.x < AT) {
+                const int c = threadIdx.x, n = min(scnt[c], TOPK_STAGE);
+                for (int e = 0; e < n; ++e) {
+                    const double v = sval[e][c];
+                    const int row = srow[e][c];
+                    if (!stats_before(v, row, lval[k - 1][c], lrow[k - 1][c])) continue;
+                    int p = k - 1;
+                    while (p > 0 && stats_before(v, row, lval[p - 1][c], lrow[p - 1][c])) {
+                        lval[p][c] = lval[p - 1][c], lrow[p][c] = lrow[p - 1][c];
+                        --p;
+                    }
+                    lval[p][c] = v, lrow[p][c] = row;
+                }
+                scnt[c] = 0;
+            }
+            __syncthreads();
+            if (pend) {  // what waits for the next round is compared with the lists as they are now
+#pragma unroll
+                for (int b = 0; b < 2; ++b) tv[b] = lval[k - 1][col[b]], tr[b] = lrow[k - 1][col[b]];
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int b = 0; b < 2; ++b) {
+                            const unsigned bit = 1u << (8 * a + 2 * r + b);
+                            if ((pend & bit) && !stats_before(d[a][b][r], (int)(i0 + 16 * a + lk + 4 * r), tv[b], tr[b])) pend &= ~bit;
+                        }
+            }
+        }
+    }
+    if (KC) {  // (the loop's last barrier lies behind the last insertion)
+        for (int e = threadIdx.x; e < k * AT; e += 256) {
+            const int64_t o = ((int64_t)blockIdx.y * k + e / AT) * nb_pad + (int64_t)blockIdx.x * AT + e % AT;
+            lv[o] = lval[e / AT][e % AT], lr[o] = lrow[e / AT][e % AT];
+        }
+        __syncthreads();
+    }
+    // the 8 (row half, lane group) partials of every column, combined in a fixed order
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        red[0][wi * 4 + lk][col[b]] = mn[b];
+        red[1][wi * 4 + lk][col[b]] = s1[b];
+        red[2][wi * 4 + lk][col[b]] = s2[b];
+    }
+    __syncthreads();
+    const int kk = threadIdx.x >> 6, c = threadIdx.x & 63;
+    if (kk == 3) return;
+    double tot = red[kk][0][c];
+#pragma unroll
+    for (int g = 1; g < 8; ++g) tot = kk == 0 ? fmin(tot, red[kk][g][c]) : tot + red[kk][g][c];
+    part[((int64_t)blockIdx.y * 3 + kk) * nb_pad + (int64_t)blockIdx.x * AT + c] = tot;
+}
+
+// the row splits' statistics of a column combined in split order: cmin[j], and the column's two sums colsum[{0, 1}][nb_pad]
+__global__ __launch_bounds__(256) void layer_stats_columns_kernel(const double* __restrict__ part, int64_t rsplit, int64_t nb,
+                                                                  int64_t nb_pad, double* __restrict__ cmin,
+                                                                  double* __restrict__ colsum) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= nb) return;  // a padded column (clamped to the last one by the tile routine) is in no statistic
+    double mn = HUGE_VAL, s1 = 0.0, s2 = 0.0;
+    for (int64_t sp = 0; sp < rsplit; ++sp) {
+        mn = fmin(mn, part[(sp * 3 + 0) * nb_pad + j]);
+        s1 += part[(sp * 3 + 1) * nb_pad + j];
+        s2 += part[(sp * 3 + 2) * nb_pad + j];
+    }
+    cmin[j] = mn, colsum[j] = s1, colsum[nb_pad + j] = s2;
+}
+
+// the row splits' lists of a column merged by one wave, as assign_topk_merge_kernel does it, in stats_before's order:
+// rows / vals[j][k] = the column's k smallest entries
+__global__ __launch_bounds__(256) void layer_stats_merge_kernel(const double* __restrict__ lv, const int* __restrict__ lr,
+                                                                int64_t rsplit, int k, int64_t nb, int64_t nb_pad,
+                                                                int* __restrict__ rows, double* __restrict__ vals) {
+    const int lane = threadIdx.x & 63;
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= nb) return;
+    int ptr = 0;
+    double hv = HUGE_VAL;
+    int hr = INT_MAX;
+    if (lane < rsplit) hv = lv[((int64_t)lane * k) * nb_pad + j], hr = lr[((int64_t)lane * k) * nb_pad + j];
+    for (int p = 0; p < k; ++p) {
+        double bv = hv;
+        int br = hr, bs = lane;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ov = __shfl_xor(bv, o, 64);
+            const int orow = __shfl_xor(br, o, 64), os = __shfl_xor(bs, o, 64);
+            if (stats_before(ov, orow, bv, br) || (ov == bv && orow == br && os < bs)) bv = ov, br = orow, bs = os;
+        }
+        if (lane == bs) {
+            ++ptr;
+            hv = HUGE_VAL, hr = INT_MAX;
+            if (ptr < k && lane < rsplit) hv = lv[((int64_t)lane * k + ptr) * nb_pad + j], hr = lr[((int64_t)lane * k + ptr) * nb_pad + j];
+        }
+        if (lane == 0) {
+            // (na >= k rows were offered, so a place holder can only come first behind non-finite values: kept in range)
+            const bool real = br != INT_MAX;
+            rows[j * k + p] = real ? br : p;
+            vals[j * k + p] = real ? bv : 0.0;
+        }
+    }
+}
+
 // ---- column factors: fac[j] = {c1, c2, c3, 0}, K_NB[j] = c3 S3 (the splits added in order)
 __global__ __launch_bounds__(256) void assign_factors_kernel(const double* __restrict__ part1, int64_t rsplit, int64_t nb,
                                                              int64_t nb_pad, double outlier, double* __restrict__ fac,
@@ -732,6 +923,31 @@ int run_assign(hipStream_t st, const Plan& p, const void* xa4, int64_t na, const
     return 0;
 }
 
+// one host layer validated and translated for the kernels; `probability`: the layer's prob / param are read (the passes of
+// mvf_assign*) or ignored (mvf_assign_layer_stats)
+int check_layer(const char* who, int l, const mvf_assign_layer& s, bool probability, DevLayer& d) {
+    MVF_REQUIRE(s.metric >= MVF_ASSIGN_EUC && s.metric <= MVF_ASSIGN_LABEL, "%s: layer %d: bad metric %d", who, l, s.metric);
+    const bool label = s.metric == MVF_ASSIGN_LABEL;  // Xp: the table, ld its row length, Yp NULL
+    // (a layer that carries prepared B rows is a product layer: with the label code its Xp / a / b would be read as table
+    // and labels, unchecked - refused before anything is launched)
+    MVF_REQUIRE(!label || !s.Yp, "%s: layer %d: bad metric %d for a layer with Yp set (a label layer has no Yp: pass NULL)", who, l,
+                s.metric);
+    MVF_REQUIRE(s.Xp && (s.Yp || label) && s.a && s.b, "%s: null pointer in layer %d", who, l);
+    if (label)
+        MVF_REQUIRE(s.ld >= 1 && s.ld < ((int64_t)1 << 31), "%s: layer %d: a label layer's ld is the table's row length L >= 1", who, l);
+    else
+        MVF_REQUIRE(s.ld >= AKS && s.ld % AKS == 0, "%s: layer %d: ld must be a positive multiple of %d", who, l, AKS);
+    if (probability) {
+        MVF_REQUIRE(s.prob >= MVF_ASSIGN_GAUSS && s.prob <= MVF_ASSIGN_PROB, "%s: layer %d: bad probability type %d", who, l, s.prob);
+        MVF_REQUIRE(s.prob != MVF_ASSIGN_GAUSS || s.param > 0.0, "%s: layer %d: a gauss layer needs a parameter > 0", who, l);
+    }
+    d.X = s.Xp, d.Y = s.Yp, d.a = s.a, d.b = s.b, d.ld = s.ld, d.prob = probability ? s.prob : MVF_ASSIGN_PROB;
+    d.nparam = probability && s.prob == MVF_ASSIGN_GAUSS ? -1.0 / (2.0 * s.param) : 0.0;
+    d.s = s.metric <= MVF_ASSIGN_SQRT_EUC ? 2.0 : (s.metric == MVF_ASSIGN_KL ? 1.0 : 0.5);
+    d.post = label ? POST_LABEL : (s.metric == MVF_ASSIGN_EUC ? 1 : (s.metric == MVF_ASSIGN_SQRT_EUC ? 2 : 0));
+    return 0;
+}
+
 int assign_entry(const char* who, const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers,
                  int nlayers, const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier,
                  double* K_NA, double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars, double* P,
@@ -755,27 +971,8 @@ int assign_entry(const char* who, const void* xa4, int64_t na, const void* xb4, 
     MVF_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
     DevLayers L;
     L.n = nlayers;
-    for (int l = 0; l < nlayers; ++l) {
-        const mvf_assign_layer& s = layers[l];
-        MVF_REQUIRE(s.metric >= MVF_ASSIGN_EUC && s.metric <= MVF_ASSIGN_LABEL, "%s: layer %d: bad metric %d", who, l, s.metric);
-        const bool label = s.metric == MVF_ASSIGN_LABEL;  // Xp: the table, ld its row length, Yp NULL
-        // (a layer that carries prepared B rows is a product layer: with the label code its Xp / a / b would be read as table
-        // and labels, unchecked - refused before anything is launched)
-        MVF_REQUIRE(!label || !s.Yp, "%s: layer %d: bad metric %d for a layer with Yp set (a label layer has no Yp: pass NULL)", who, l,
-                    s.metric);
-        MVF_REQUIRE(s.Xp && (s.Yp || label) && s.a && s.b, "%s: null pointer in layer %d", who, l);
-        if (label)
-            MVF_REQUIRE(s.ld >= 1 && s.ld < ((int64_t)1 << 31), "%s: layer %d: a label layer's ld is the table's row length L >= 1", who, l);
-        else
-            MVF_REQUIRE(s.ld >= AKS && s.ld % AKS == 0, "%s: layer %d: ld must be a positive multiple of %d", who, l, AKS);
-        MVF_REQUIRE(s.prob >= MVF_ASSIGN_GAUSS && s.prob <= MVF_ASSIGN_PROB, "%s: layer %d: bad probability type %d", who, l, s.prob);
-        MVF_REQUIRE(s.prob != MVF_ASSIGN_GAUSS || s.param > 0.0, "%s: layer %d: a gauss layer needs a parameter > 0", who, l);
-        DevLayer& d = L.l[l];
-        d.X = s.Xp, d.Y = s.Yp, d.a = s.a, d.b = s.b, d.ld = s.ld, d.prob = s.prob;
-        d.nparam = s.prob == MVF_ASSIGN_GAUSS ? -1.0 / (2.0 * s.param) : 0.0;
-        d.s = s.metric <= MVF_ASSIGN_SQRT_EUC ? 2.0 : (s.metric == MVF_ASSIGN_KL ? 1.0 : 0.5);
-        d.post = label ? POST_LABEL : (s.metric == MVF_ASSIGN_EUC ? 1 : (s.metric == MVF_ASSIGN_SQRT_EUC ? 2 : 0));
-    }
+    for (int l = 0; l < nlayers; ++l)
+        if (const int rc = check_layer(who, l, layers[l], true, L.l[l])) return rc;
     for (int l = nlayers; l < MAX_LAYERS; ++l) L.l[l] = L.l[0];
     const double h1 = -1.0 / (2.0 * (sigma2 / sigma2_variance)), h2 = -1.0 / (2.0 * sigma2);
     hipStream_t st = (hipStream_t)stream;
@@ -784,6 +981,62 @@ int assign_entry(const char* who, const void* xa4, int64_t na, const void* xb4, 
                                  K_NA_sigma2, PXB, scalars, P, topk ? &tp : nullptr, trows, tvals, (char*)workspace);
     return run_assign<double>(st, p, xa4, na, xb4, nb, L, model_mul, h1, h2, spatial_outlier, K_NA, K_NB, K_NA_spatial,
                               K_NA_sigma2, PXB, scalars, P, topk ? &tp : nullptr, trows, tvals, (char*)workspace);
+}
+
+// workspace of mvf_assign_layer_stats: part[rsplit][3][nb_pad], colsum[2][nb_pad], the row splits' lists lv / lr[split][k][nb_pad]
+struct StatsPlan {
+    Plan p;
+    int k;  // min(k, na)
+    size_t off_part, off_col, off_lv, off_lr, total;
+};
+
+StatsPlan make_stats_plan(int64_t na, int64_t nb, int k) {
+    StatsPlan t;
+    t.p = make_plan(na, nb);
+    t.k = (int)std::min<int64_t>(k, na);
+    size_t o = 0;
+    t.off_part = o, o += align_up((size_t)t.p.rsplit * 3 * t.p.nb_pad * sizeof(double), 256);
+    t.off_col = o, o += align_up((size_t)2 * t.p.nb_pad * sizeof(double), 256);
+    t.off_lv = o, o += align_up((size_t)t.p.rsplit * t.k * t.p.nb_pad * sizeof(double), 256);
+    t.off_lr = o, o += align_up((size_t)t.p.rsplit * t.k * t.p.nb_pad * sizeof(int), 256);
+    t.total = o;
+    return t;
+}
+
+template <typename T>
+int run_layer_stats(hipStream_t st, const StatsPlan& t, const DevLayer& ly, int64_t na, int64_t nb, double* cmin, int* rows,
+                    double* vals, double* sums, char* ws) {
+    const Plan& p = t.p;
+    double* part = (double*)(ws + t.off_part);
+    double* colsum = (double*)(ws + t.off_col);
+    double* lv = (double*)(ws + t.off_lv);
+    int* lr = (int*)(ws + t.off_lr);
+    const dim3 grid((unsigned)p.ctiles, (unsigned)p.rsplit);
+#define MVF_LAYER_STATS(KC) \
+    hipLaunchKernelGGL((layer_stats_kernel<T, KC>), grid, dim3(256), 0, st, ly, na, nb, p.rtiles, p.nb_pad, t.k, part, lv, lr)
+    if (t.k == 0)
+        MVF_LAYER_STATS(0);
+    else if (t.k <= 4)  // the lists' LDS is sized by the template, as in pass 1 of mvf_assign_topk
+        MVF_LAYER_STATS(4);
+    else if (t.k <= 16)
+        MVF_LAYER_STATS(16);
+    else
+        MVF_LAYER_STATS(TOPK_MAX);
+#undef MVF_LAYER_STATS
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(layer_stats_columns_kernel, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, st, part, p.rsplit, nb, p.nb_pad, cmin,
+                       colsum);
+    MVF_LAUNCH_CHECK();
+    for (int q = 0; q < 2; ++q) {
+        hipLaunchKernelGGL(assign_sum_kernel, dim3(1), dim3(256), 0, st, colsum + q * p.nb_pad, nb, sums + q);
+        MVF_LAUNCH_CHECK();
+    }
+    if (t.k) {
+        hipLaunchKernelGGL(layer_stats_merge_kernel, dim3((unsigned)cdiv(nb, 4)), dim3(256), 0, st, lv, lr, p.rsplit, t.k, nb, p.nb_pad,
+                           rows, vals);
+        MVF_LAUNCH_CHECK();
+    }
+    return 0;
 }
 
 }  // namespace
@@ -867,4 +1120,27 @@ extern "C" int mvf_assign_topk(const void* xa4, int64_t na, const void* xb4, int
     return assign_entry("mvf_assign_topk", xa4, na, xb4, nb, layers, nlayers, model_mul, sigma2, sigma2_variance, spatial_outlier,
                         K_NA, K_NB, K_NA_spatial, K_NA_sigma2, PXB, scalars, nullptr, false, k, rows, vals, workspace,
                         workspace_bytes, dtype, stream);
+}
+
+extern "C" size_t mvf_assign_layer_stats_workspace_bytes(int64_t na, int64_t nb, int k) {
+    if (na <= 0 || nb <= 0 || k < 0 || k > TOPK_MAX) return 0;
+    return make_stats_plan(na, nb, k).total;
+}
+
+extern "C" int mvf_assign_layer_stats(const mvf_assign_layer* layer, int64_t na, int64_t nb, int k, double* cmin, int32_t* rows,
+                                      double* vals, double* sums, void* workspace, size_t workspace_bytes, mvf_dtype dtype,
+                                      void* stream) {
+    const char* who = "mvf_assign_layer_stats";
+    MVF_REQUIRE(k >= 0 && k <= TOPK_MAX, "%s: need 0 <= k <= %d, got %d", who, TOPK_MAX, k);
+    MVF_REQUIRE(na >= 1 && nb >= 1, "%s: need na >= 1 and nb >= 1", who);
+    MVF_REQUIRE(na < ((int64_t)1 << 31) && nb < ((int64_t)1 << 31), "%s: too many cells", who);
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "%s: bad dtype %d", who, (int)dtype);
+    MVF_REQUIRE(layer && cmin && sums && workspace && ((rows && vals) || k == 0), "%s: null pointer", who);
+    DevLayer ly;
+    if (const int rc = check_layer(who, 0, *layer, false, ly)) return rc;
+    const StatsPlan t = make_stats_plan(na, nb, k);
+    MVF_REQUIRE(workspace_bytes >= t.total, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, t.total);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MVF_F32) return run_layer_stats<float>(st, t, ly, na, nb, cmin, rows, vals, sums, (char*)workspace);
+    return run_layer_stats<double>(st, t, ly, na, nb, cmin, rows, vals, sums, (char*)workspace);
 }

@@ -666,6 +666,31 @@ class HipKernels:
                                             _ptr(ws), need, self.cdtype, self._stream()), "mvf_assign_topk")
         return out
 
+    @_on_device
+    def assign_layer_stats(self, layer, na, nb, k=0):
+        """Column statistics of one layer's (na, nb) distance matrix (mvf_assign_layer_stats).  layer: one tuple as assign
+        takes them (prob and param are not read).  Returns device tensors {cmin (nb,) float64, sums (2,) float64 = sum d,
+        sum d^2} and, for k > 0, rows (nb, k_eff) int32 / vals (nb, k_eff) float64, k_eff = min(k, na): column j's smallest
+        entries, value ascending, row ascending.  The statistics of the rows: the same call on the exchanged layer
+        (Yp, Xp, b, a, ...) with na and nb exchanged."""
+        na, nb, k = int(na), int(nb), int(k)
+        ke = min(k, na)
+        f64 = torch.float64
+        arr = (_lib.AssignLayer * 1)()
+        Xp, Yp, a, b, ld, metric, prob, param = layer
+        s = arr[0]
+        s.Xp, s.Yp, s.a, s.b, s.ld = _ptr(Xp), _ptr(Yp), _ptr(a), _ptr(b), int(ld)
+        s.metric, s.prob, s.param = int(metric), int(prob), float(param)
+        out = {"cmin": self.empty(nb, dtype=f64), "sums": self.empty(2, dtype=f64)}
+        if k > 0:
+            out["rows"], out["vals"] = self.empty(nb, ke, dtype=torch.int32), self.empty(nb, ke, dtype=f64)
+        need = int(self.lib.mvf_assign_layer_stats_workspace_bytes(na, nb, k))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.mvf_assign_layer_stats(arr, na, nb, k, _ptr(out["cmin"]), _ptr(out.get("rows")), _ptr(out.get("vals")),
+                                                   _ptr(out["sums"]), _ptr(ws), need, self.cdtype, self._stream()),
+                   "mvf_assign_layer_stats")
+        return out
+
     # ---- the O(N) glue of the alignment loop (mvf_align.hip): device tensors in, device tensors out ----
     @_on_device
     def align_alpha(self, kappa, K_NA_spatial, SigmaDiag, Sp_spatial, sigma2, alpha, model_mul):

@@ -20,7 +20,7 @@ from .engine import SparseVFCEngine, _consistent_K
 from .vectorfield import vector_field_function
 
 __all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate", "morpho_iterate_svi",
-           "label_transfer_matrix"]
+           "label_transfer_matrix", "init_sigma2", "init_probability_parameters", "coarse_rigid_alignment", "morpho_start"]
 
 RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
 
@@ -90,14 +90,14 @@ def _label_arguments(A, B, NA, NB, table):
 
 
 def _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
-                          probability_parameters, return_P, label_transfer=None):
-    """Validation of update_assignment (no device needed): the arrays as float64 (a label layer's as int64), the per-layer
+                          probability_parameters, return_P, label_transfer=None, who="update_assignment"):
+    """Validation of update_assignment (no device needed; `who`: the public function named in a refusal): the arrays as float64 (a label layer's as int64), the per-layer
     (metric, probability type, parameter) codes of include/mvf.h and the label-transfer table as float64 (K, L) or None."""
     XA, XB = np.asarray(XAHat, dtype=np.float64), np.asarray(coordsB, dtype=np.float64)
     if XA.ndim != 2 or XB.ndim != 2 or XA.shape[1] != XB.shape[1]:
         raise AssertionError("X and Y do not have the same number of features.")  # _euc_distance_backend (utils.py:775)
     if XA.shape[1] not in (2, 3):
-        raise NotImplementedError(f"update_assignment: spatial coordinates must be 2-D or 3-D, got D = {XA.shape[1]}")
+        raise NotImplementedError(f"{who}: spatial coordinates must be 2-D or 3-D, got D = {XA.shape[1]}")
     LA = list(exp_layers_A) if isinstance(exp_layers_A, (list, tuple)) else [exp_layers_A]
     LB = list(exp_layers_B) if isinstance(exp_layers_B, (list, tuple)) else [exp_layers_B]
     n_layers = len(LA)
@@ -113,7 +113,7 @@ def _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilar
         raise ValueError("exp_layers_A, exp_layers_B, dissimilarity, probability_type and probability_parameters must list "
                          "the same (non-zero) number of layers")
     if n_layers > _lib.ASSIGN_MAX_LAYERS:
-        raise NotImplementedError(f"update_assignment: at most {_lib.ASSIGN_MAX_LAYERS} layers are supported, got {n_layers}")
+        raise NotImplementedError(f"{who}: at most {_lib.ASSIGN_MAX_LAYERS} layers are supported, got {n_layers}")
     codes = []
     for l, (met, kind, par) in enumerate(zip(metrics, kinds, params)):
         if met not in _lib.ASSIGN_METRICS:
@@ -897,3 +897,414 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
                     partial_robust_level, nn_init_weight, update_R, dtype, device, record,
                     svi=dict(batch_size=bs, batch_perm=perm, return_mapping=bool(return_mapping)))
+
+
+# ---- the start state: what the reference computes in front of the loop (morpho_class.py:700-747, 771-820, 845-852, 898-1041) ----
+def _draw(n, idx, subsample, rng, name):
+    """The rows of one side a start-state function works on: the indices given (validated) or, above ``subsample`` rows, a
+    draw without replacement from ``rng`` - np.arange(n) otherwise, as the reference has it."""
+    if idx is not None:
+        raw = np.asarray(idx)
+        if raw.ndim != 1 or len(raw) == 0 or not np.issubdtype(raw.dtype, np.integer):
+            raise ValueError(f"{name} must be a non-empty 1-D integer array")
+        if raw.min() < 0 or raw.max() >= n:
+            raise ValueError(f"{name}: indices must lie in 0 .. {n - 1}")
+        if len(np.unique(raw)) != len(raw):
+            raise ValueError(f"{name}: indices must not repeat (the reference draws without replacement)")
+        return raw.astype(np.int64)
+    if isinstance(subsample, bool) or int(subsample) != subsample or subsample < 1:
+        raise ValueError(f"the subsample size must be a positive integer, got {subsample!r}")
+    return rng.choice(n, int(subsample), replace=False) if n > subsample else np.arange(n)
+
+
+def _coords_pair(coordsA, coordsB, who):
+    XA, XB = np.asarray(coordsA, dtype=np.float64), np.asarray(coordsB, dtype=np.float64)
+    if XA.ndim != 2 or XB.ndim != 2 or XA.shape[1] != XB.shape[1]:
+        raise AssertionError("X and Y do not have the same number of features.")  # _euc_distance_backend (utils.py:775)
+    if XA.shape[1] not in (2, 3):
+        raise NotImplementedError(f"{who}: spatial coordinates must be 2-D or 3-D, got D = {XA.shape[1]}")
+    if len(XA) == 0 or len(XB) == 0:
+        raise ValueError(f"{who}: both slices need at least one cell")
+    return XA, XB
+
+
+def _product_layer(k, A, B, metric):
+    """Both sides of one product layer prepared for mvf_assign_layer_stats: the tuple HipKernels.assign_layer_stats takes."""
+    Xp, a, ld = k.assign_prepare(A, metric, 0)
+    Yp, b, _ = k.assign_prepare(B, metric, 1)
+    return (Xp, Yp, a, b, ld, metric, _lib.ASSIGN_PROBS["prob"], 0.0)
+
+
+def _exchanged(layer):
+    """The layer whose column statistics are `layer`'s row statistics: Xp <-> Yp, a <-> b (the caller exchanges na and nb)."""
+    Xp, Yp, a, b, ld, metric, prob, param = layer
+    return (Yp, Xp, b, a, ld, metric, prob, param)
+
+
+def init_sigma2(coordsA, coordsB, *, sigma2_init_scale=1.0, subsample=20000, subsample_A=None, subsample_B=None, seed=0,
+                dtype: str = "float64", device=None):
+    """The loop's initial ``sigma2``: ``sigma2_init_scale * _init_guess_sigma2(coordsA, coordsB)`` of the reference
+    (``spateo/alignment/methods/utils.py:1339-1354``, ``morpho_class.py:710``), from the sum of squares that
+    ``mvf_assign_layer_stats`` forms over the spatial distance matrix (the coordinates as an ``"euc"`` layer of D features):
+    the matrix is never written.  ``coordsA`` are the coordinates AFTER the coarse alignment, as in the reference.
+
+    Two things are the reference's and are reproduced: its ``"euc"`` distance already is the squared distance and is squared
+    once more (``:1352``), and the sum is divided by ``D * nA_sub * nA_sub``, not by ``D * nA_sub * nB_sub`` (``:1353``).
+
+    Above ``subsample`` cells a side is subsampled: ``subsample_A`` / ``subsample_B`` are the row indices to use (what the
+    reference draws with ``np.random.choice``); without them the draw is ``np.random.default_rng(seed).choice``, A first -
+    NOT the reference's stream.  Returns a float."""
+    if dtype not in ("float32", "float64"):
+        raise ValueError("dtype must be 'float32' or 'float64'")
+    XA, XB = _coords_pair(coordsA, coordsB, "init_sigma2")
+    rng = np.random.default_rng(seed)
+    iA = _draw(len(XA), subsample_A, subsample, rng, "subsample_A")
+    iB = _draw(len(XB), subsample_B, subsample, rng, "subsample_B")
+    k = _rt._shared_kernels(device, dtype)
+    stats = k.assign_layer_stats(_product_layer(k, XA[iA], XB[iB], _lib.ASSIGN_METRICS["euc"]), len(iA), len(iB))
+    sum_sq = float(_rt._to_host(k, [stats["sums"]])[0][1])
+    # utils.py:1352-1353: SpatialDistMat**2 of the already squared distance, over D * nA_sub * nA_sub
+    return float(sigma2_init_scale) * (sum_sq / (XA.shape[1] * len(iA) * len(iA)))
+
+
+def _start_layers(exp_layers_A, exp_layers_B, dissimilarity, probability_type, probability_parameters, label_transfer, who):
+    """The layer lists validated as update_assignment validates them, a missing Gaussian parameter allowed.  Returns (LA,
+    LB, codes, table, params, estimate): params the parameters as given, estimate the layers whose parameter is to be found."""
+    LA = list(exp_layers_A) if isinstance(exp_layers_A, (list, tuple)) else [exp_layers_A]
+    LB = list(exp_layers_B) if isinstance(exp_layers_B, (list, tuple)) else [exp_layers_B]
+    if len(LA) < 1 or len(LA) != len(LB):
+        raise ValueError("exp_layers_A and exp_layers_B must list the same (non-zero) number of layers")
+    n = len(LA)
+    as_list = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n  # noqa: E731
+    metrics, kinds = as_list(dissimilarity), as_list(probability_type)
+    params = [None] * n if probability_parameters is None else as_list(probability_parameters)
+    if not (len(metrics) == len(kinds) == len(params) == n):
+        raise ValueError("exp_layers_A, exp_layers_B, dissimilarity, probability_type and probability_parameters must list "
+                         "the same (non-zero) number of layers")
+    estimate = [l for l in range(n) if params[l] is None and str(kinds[l]).lower() == "gauss"]   # morpho_class.py:803-805
+    for l in estimate:
+        if metrics[l] == "label":  # the reference calls calc_distance without a table there (:813) and fails
+            raise ValueError(f"{who}: layer {l} is a 'label' layer with probability type 'gauss' and no parameter; the "
+                             f"reference cannot estimate it either - pass probability_parameters[{l}]")
+    NA, NB = len(np.asarray(LA[0])), len(np.asarray(LB[0]))
+    filled = [1.0 if l in estimate else params[l] for l in range(n)]
+    _, _, LA, LB, codes, table = _assignment_arguments(np.zeros((NA, 2)), np.zeros((NB, 2)), LA, LB, metrics, kinds, filled, False,
+                                                       label_transfer, who)
+    return LA, LB, codes, table, params, estimate
+
+
+def _estimate_parameters(k, LA, LB, codes, estimate, iA, iB):
+    """`_init_probability_parameters` (morpho_class.py:813-817) for the layers `estimate` on the rows iA / iB."""
+    found = {}
+    for l in estimate:
+        layer = _product_layer(k, LA[l][iA], LB[l][iB], codes[l][0])
+        # the minima over B for every A cell: the column minima of the exchanged call
+        stats = k.assign_layer_stats(_exchanged(layer), len(iB), len(iA))
+        row_min = np.sort(np.asarray(_rt._to_host(k, [stats["cmin"]])[0], dtype=np.float64))
+        found[l] = max(float(row_min[int(len(iA) * 0.05)]) / 5, 0.01)
+    return found
+
+
+def init_probability_parameters(exp_layers_A, exp_layers_B, *, dissimilarity, probability_type, probability_parameters=None,
+                                subsample=20000, subsample_A=None, subsample_B=None, seed=0, label_transfer=None,
+                                dtype: str = "float64", device=None):
+    """The per-layer Gaussian parameters the reference estimates in front of the loop,
+    ``Morpho_pairwise._init_probability_parameters`` (``spateo/alignment/methods/morpho_class.py:771-820``): for every
+    ``"gauss"`` layer whose parameter is ``None``, the minimum over the (subsampled) B cells of the layer distance of every
+    (subsampled) A cell - ``mvf_assign_layer_stats`` with the operands exchanged, no matrix is written -, sorted, the entry at
+    index ``int(nA_sub * 0.05)``, divided by 5 and floored at 0.01 (``:813-817``).  Parameters that were given and layers of
+    another probability type pass through.  A ``"label"`` layer that would need estimating is a ``ValueError`` (the reference
+    fails there: it calls ``calc_distance`` without the table).
+
+    Layers and lists as ``update_assignment`` takes them.  ``subsample_A`` / ``subsample_B``: the row indices to use (one set
+    for every estimated layer; the reference draws per layer with ``np.random.choice``); without them the draw is
+    ``np.random.default_rng(seed).choice``, A first - NOT the reference's stream.  Returns the list of parameters."""
+    if dtype not in ("float32", "float64"):
+        raise ValueError("dtype must be 'float32' or 'float64'")
+    LA, LB, codes, _, params, estimate = _start_layers(exp_layers_A, exp_layers_B, dissimilarity, probability_type,
+                                                       probability_parameters, label_transfer, "init_probability_parameters")
+    rng = np.random.default_rng(seed)
+    iA = _draw(len(LA[0]), subsample_A, subsample, rng, "subsample_A")
+    iB = _draw(len(LB[0]), subsample_B, subsample, rng, "subsample_B")
+    out = list(params)
+    if estimate:
+        k = _rt._shared_kernels(device, dtype)
+        for l, v in _estimate_parameters(k, LA, LB, codes, estimate, iA, iB).items():
+            out[l] = v
+    return out
+
+
+def _voxel_data(coords, gene_exp, voxel_num):
+    """``voxel_data`` (utils.py:1283-1336) without its loop over all voxels: a point can lie within ``voxel_size / 2`` only of
+    the grid nodes whose index along every axis is within reach, so every point visits those few and the reference's own test
+    ``sqrt(sum((coords - voxel_coord)**2)) < voxel_size / 2`` decides.  Returns (voxel_coords, voxel_gene_exps) of the
+    occupied voxels in the reference's order (``np.meshgrid``'s)."""
+    from scipy.sparse import csr_matrix
+
+    N, D = coords.shape
+    lo, hi = coords.min(0), coords.max(0)
+    voxel_size = np.sqrt(np.prod(hi - lo)) / (np.sqrt(N) / 5)
+    steps = (hi - lo) / int(np.sqrt(voxel_num))
+    axes = [np.arange(a, b, s) for a, b, s in zip(lo, hi, steps)]
+    grid = np.stack(np.meshgrid(*axes), axis=-1)          # (n1, n0[, n2], D): meshgrid's "xy" order
+    nodes = grid.reshape(-1, D)
+    index_of = np.arange(len(nodes)).reshape(grid.shape[:-1])
+    radius = voxel_size / 2
+    first = [np.floor((coords[:, d] - radius - lo[d]) / steps[d]).astype(np.int64) - 1 for d in range(D)]
+    span = [int(np.max(np.floor((coords[:, d] + radius - lo[d]) / steps[d]).astype(np.int64) + 1 - first[d])) + 1 for d in range(D)]
+    vox, pts = [], []
+    every = np.arange(N)
+    for off in np.ndindex(*span):
+        idx = [first[d] + off[d] for d in range(D)]
+        ok = np.ones(N, dtype=bool)
+        for d in range(D):
+            ok &= (idx[d] >= 0) & (idx[d] < len(axes[d]))
+        p = every[ok]
+        ax = [idx[d][ok] for d in range(D)]
+        v = index_of[(ax[1], ax[0]) + tuple(ax[2:])]     # meshgrid puts the second axis first
+        dists = np.sqrt(np.sum((coords[p] - nodes[v]) ** 2, axis=1))
+        keep = dists < radius
+        vox.append(v[keep]), pts.append(p[keep])
+    vox, pts = np.concatenate(vox), np.concatenate(pts)
+    member = csr_matrix((np.ones(len(vox)), (vox, pts)), shape=(len(nodes), N))
+    count = np.asarray(member.sum(1)).reshape(-1)
+    used = count > 0
+    means = np.asarray(member[used] @ gene_exp) / count[used][:, None]
+    return nodes[used], means
+
+
+PAIR_FIT_ITERATIONS = 100   # utils.py:1238
+PAIR_FIT_ANNEAL_AFTER = 20  # the expression weights flatten from the iteration after this one on (:1268-1271)
+
+
+def _weighted_rigid_fit(src, dst, w, total):
+    """The proper rotation R and translation t that minimise sum_i w_i |dst_i - R src_i - t|^2 (weighted Kabsch; the last
+    singular direction takes the sign that keeps det R = +1).  src, dst (n, D), w (n, 1); ``total`` is what the weighted
+    centroids are divided by - the caller's sum of w before its floor, as in the reference (:1247-1248, 1263-1265)."""
+    c_src, c_dst = (w * src).sum(0) / total, (w * dst).sum(0) / total
+    U, _, Vt = np.linalg.svd((dst - c_dst).T @ (w * (src - c_src)))
+    sign = np.ones(src.shape[1])
+    sign[-1] = np.linalg.det(U @ Vt)
+    R = (U * sign) @ Vt
+    return R, c_dst - c_src @ R.T
+
+
+def _inlier_posterior(resid2, w, sigma2, gamma, volume, D):
+    """Per pair, the probability of being an inlier: an isotropic Gaussian of the squared residual, weighted by the pair's
+    expression weight, against a uniform outlier density over ``volume`` carrying the largest weight (:1258-1260)."""
+    inlier = np.exp(-resid2 / (2 * sigma2)) * w
+    outlier = w.max() * (1 - gamma) * (2 * np.pi * sigma2) ** (D / 2) / (gamma * volume)
+    return inlier / (inlier + outlier)
+
+
+def _pair_inlier_fit(src, dst, expr_dist):
+    """What the reference's ``inlier_from_NN`` (``utils.py:1220-1280``) computes, in this project's own form: an EM fit of one
+    rigid motion to matched pairs src -> dst (n, D) that may be wrong.  Every pair carries an expression weight
+    ``exp(-temper * d)`` with d its expression distance scaled so that the largest becomes 2 ln 10; per iteration a weighted
+    rigid fit, the inlier posteriors (floored at 1e-6 once their sum is taken), the inlier fraction clamped to [0.01, 0.99]
+    and the residual variance; after the first 21 iterations ``temper`` falls geometrically towards 0.1 and the weights are
+    renormalised to a maximum of 1.  The posteriors returned are evaluated once more at variance 1e-2 and inlier fraction
+    0.1 (:1273-1279).  Returns (posterior (n, 1), R, t, inlier fraction of that last evaluation)."""
+    n, D = src.shape
+    d = np.maximum(expr_dist, 0)
+    d = d / (d.max() / (np.log(10) * 2))
+    volume = max(np.prod(np.ptp(src, axis=0)), np.prod(np.ptp(dst, axis=0)))
+    temper = 1.0
+    cooling = (0.1 / temper) ** (1 / (PAIR_FIT_ITERATIONS - PAIR_FIT_ANNEAL_AFTER))
+    w = np.exp(-d * temper)
+    post, mass = w.copy(), w.sum()
+    sigma2, fraction = ((src - dst) ** 2).sum() / (D * n), 0.5
+    for it in range(PAIR_FIT_ITERATIONS):
+        R, t = _weighted_rigid_fit(src, dst, post, mass)
+        resid2 = ((dst - (src @ R.T + t)) ** 2).sum(1, keepdims=True)
+        post = _inlier_posterior(resid2, w, sigma2, fraction, volume, D)
+        mass = post.sum()
+        fraction = min(max(mass / n, 0.01), 0.99)
+        post = np.maximum(post, 1e-6)
+        sigma2 = (resid2 * post).sum() / (D * mass)
+        if it > PAIR_FIT_ANNEAL_AFTER:
+            temper *= cooling
+            w = np.exp(-d * temper)
+            w = w / w.max()
+    post = _inlier_posterior(resid2, w, 1e-2, 0.1, volume, D)
+    return post, R, t, min(max(post.sum() / n, 0.01), 0.99)
+
+
+INLIER_RANK = 20  # morpho_class.py:1020: the inlier threshold is the 21st largest P (at most 0.5), so 22 pairs are the least
+
+
+def _coarse_arguments(coordsA, coordsB, init_A, init_B, metric, nn_init_top_K, n_sampling, subsample_A, subsample_B, rng, dtype):
+    if dtype not in ("float32", "float64"):
+        raise ValueError("dtype must be 'float32' or 'float64'")
+    XA, XB = _coords_pair(coordsA, coordsB, "coarse_rigid_alignment")
+    if metric not in _lib.ASSIGN_METRICS or metric == "label":
+        raise ValueError(f"coarse_rigid_alignment: metric must be one of the product metrics (the reference uses 'kl' for "
+                         f"init_field='layer' and 'euc' otherwise), got {metric!r}")
+    FA, FB = np.asarray(init_A, dtype=np.float64), np.asarray(init_B, dtype=np.float64)
+    if FA.ndim != 2 or FB.ndim != 2 or FA.shape[1] != FB.shape[1] or FA.shape[1] < 1:
+        raise AssertionError("X and Y do not have the same number of features.")
+    if len(FA) != len(XA) or len(FB) != len(XB):
+        raise ValueError("init_A and init_B must have one row per cell of their slice")
+    if isinstance(nn_init_top_K, bool) or int(nn_init_top_K) != nn_init_top_K or nn_init_top_K < 1:
+        raise ValueError(f"nn_init_top_K must be a positive integer, got {nn_init_top_K!r}")
+    if nn_init_top_K > _lib.ASSIGN_TOPK_MAX:
+        raise NotImplementedError(f"coarse_rigid_alignment: nn_init_top_K = {int(nn_init_top_K)} is not supported: the device "
+                                  f"keeps at most {_lib.ASSIGN_TOPK_MAX} neighbours per voxel (_lib.ASSIGN_TOPK_MAX)")
+    iA = _draw(len(XA), subsample_A, n_sampling, rng, "subsample_A")
+    iB = _draw(len(XB), subsample_B, n_sampling, rng, "subsample_B")
+    return XA, XB, FA, FB, iA, iB
+
+
+def coarse_rigid_alignment(coordsA, coordsB, init_A, init_B, *, metric, nn_init_top_K=10, allow_flip=False, init_transform=True,
+                           n_sampling=20000, subsample_A=None, subsample_B=None, seed=0, dtype: str = "float64", device=None):
+    """The coarse rigid alignment of the reference's ``nn_init``, ``Morpho_pairwise._coarse_rigid_alignment``
+    (``spateo/alignment/methods/morpho_class.py:898-1041``): both slices (subsampled above ``n_sampling`` cells) are
+    voxelised (``voxel_data``, ``utils.py:1283-1336``, with ``voxel_num = max(min(int(N / 20), 1000), 100)``), the voxels'
+    mean representations ``init_A`` (NA, G) / ``init_B`` (NB, G) are compared with ``metric`` (the reference: ``"kl"`` for
+    ``init_field="layer"``, ``"euc"`` otherwise), the ``nn_init_top_K`` nearest voxels of every voxel either way make the
+    matched pairs (``:976-998``), and the fit of ``inlier_from_NN`` (``utils.py:1220-1280``) gives R, t and the pairs' inlier
+    probabilities; with ``allow_flip`` the mirrored fit replaces it when its gamma is larger (``:1007-1019``).
+
+    The voxelisation and ``inlier_from_NN`` (100 iterations on a few thousand pairs) are host NumPy; the voxel x voxel
+    distance matrix is never written: both lists of nearest voxels come from two ``mvf_assign_layer_stats`` calls with
+    ``k = top_K``, the second with the operands exchanged.  Within a voxel's list the pairs are ordered by distance where
+    ``np.argpartition`` leaves them unordered; every sum over the pairs is the same set of terms.  ``top_K`` is capped at the
+    smaller voxel count minus one (the reference counts down after an exception); ``nn_init_top_K`` above 64 is refused
+    (``NotImplementedError``: the lists' cap); at least 22 pairs are needed for the inlier threshold (``:1020``), fewer is a
+    ``ValueError``.
+
+    ``subsample_A`` / ``subsample_B``: the row indices to use; without them the draw is
+    ``np.random.default_rng(seed).choice``, A first - NOT the reference's stream.
+
+    Returns ``inliers = (inlier_A, inlier_B, inlier_P)`` as ``morpho_iterate`` takes them (``inlier_A`` transformed when
+    ``init_transform``), ``inlier_pairs`` (n, 2) (the pairs' B voxel and A voxel), ``init_R`` (D, D), ``init_t`` (D,) and
+    ``coordsA``, transformed by ``coordsA @ init_R.T + init_t`` when ``init_transform`` (``:1033-1035``)."""
+    rng = np.random.default_rng(seed)
+    XA, XB, FA, FB, iA, iB = _coarse_arguments(coordsA, coordsB, init_A, init_B, metric, nn_init_top_K, n_sampling, subsample_A,
+                                               subsample_B, rng, dtype)
+    D = XA.shape[1]
+    vA, gA = _voxel_data(XA[iA], FA[iA], max(min(int(len(iA) / 20), 1000), 100))
+    vB, gB = _voxel_data(XB[iB], FB[iB], max(min(int(len(iB) / 20), 1000), 100))
+    N, M = len(vA), len(vB)
+    top_K = min(int(nn_init_top_K), min(N, M) - 1)
+    if top_K < 1 or top_K * (N + M) < INLIER_RANK + 2:
+        raise ValueError(f"coarse_rigid_alignment: {N} x {M} occupied voxels with top_K = {top_K} give fewer than "
+                         f"{INLIER_RANK + 2} matched pairs; the inlier threshold needs that many")
+    k = _rt._shared_kernels(device, dtype)
+    layer = _product_layer(k, gA, gB, _lib.ASSIGN_METRICS[metric])
+    cols = k.assign_layer_stats(layer, N, M, top_K)                  # per B voxel: its top_K A voxels
+    rows = k.assign_layer_stats(_exchanged(layer), M, N, top_K)      # per A voxel: its top_K B voxels
+    c_rows, c_vals, r_rows, r_vals = _rt._to_host(k, [cols["rows"], cols["vals"], rows["rows"], rows["vals"]])
+    # the pair list (B voxel, A voxel) in the reference's order (:976-998): every B voxel's neighbours, then every A voxel's
+    NN1 = np.stack([np.repeat(np.arange(M), top_K), np.asarray(c_rows, dtype=np.int64).reshape(-1)], axis=1)
+    NN2 = np.stack([np.asarray(r_rows, dtype=np.int64).reshape(-1), np.repeat(np.arange(N), top_K)], axis=1)
+    NN = np.vstack((NN1, NN2))
+    distance = np.r_[np.asarray(c_vals, dtype=np.float64).reshape(-1), np.asarray(r_vals, dtype=np.float64).reshape(-1)][:, None]
+    src, dst = vA[NN[:, 1], :], vB[NN[:, 0], :]
+    post, R, t, fraction = _pair_inlier_fit(src, dst, distance)
+    if allow_flip:
+        # the same fit to the slice mirrored in its last axis; kept when it explains more pairs (morpho_class.py:1007-1019)
+        mirror = np.diag([1.0] * (D - 1) + [-1.0])
+        m_post, m_R, m_t, m_fraction = _pair_inlier_fit(src @ mirror, dst, distance)
+        if m_fraction > fraction:
+            post, R, t = m_post, m_R @ mirror, m_t
+    # inliers: the pairs above the 21st largest posterior, or above 0.5 where that is larger (:1020-1023)
+    cut = min(np.sort(post[:, 0])[-(INLIER_RANK + 1)], 0.5)
+    keep = np.flatnonzero(post[:, 0] > cut)
+    inlier_A, inlier_B, out_A = src[keep], dst[keep], XA
+    if init_transform:
+        inlier_A, out_A = inlier_A @ R.T + t, XA @ R.T + t
+    return dict(inliers=(inlier_A, inlier_B, post[keep]), inlier_pairs=NN[keep], init_R=R, init_t=np.asarray(t).reshape(-1),
+                coordsA=out_A)
+
+
+class _Start(dict):
+    """What morpho_start returns: the keyword arguments of morpho_iterate / morpho_iterate_svi it computed, as a dict, and
+    beside them - as attributes, so that ``**start`` stays what the loops take - ``coordsA`` (after the coarse transform),
+    ``init_R`` and ``init_t``.  ``copy()``, ``copy.copy`` and pickling keep the attributes; ``dict(start)`` is the plain
+    keyword dict."""
+
+    def copy(self):
+        return self.__copy__()
+
+    def __copy__(self):
+        new = _Start(self)
+        new.__dict__.update(self.__dict__)
+        return new
+
+    def __reduce__(self):
+        return (_Start, (dict(self),), dict(self.__dict__))
+
+
+def morpho_start(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity, probability_type, probability_parameters=None,
+                 inducing_variables_num=300, nn_init=True, init_layer_A=None, init_layer_B=None, init_metric="kl",
+                 nn_init_top_K=10, allow_flip=False, init_transform=True, n_sampling=20000, subsample=20000,
+                 sigma2_init_scale=1.0, subsample_A=None, subsample_B=None, inducing_idx=None, seed=0, label_transfer=None,
+                 dtype: str = "float64", device=None):
+    """Everything ``Morpho_pairwise`` computes in front of its loop, in the reference's order: the inducing variables
+    (``_construct_kernel``, ``morpho_class.py:845-852``: unique rows of ``coordsA``, ``inducing_variables_num`` of them - the
+    reference constructor's ``K``), with ``nn_init`` the coarse rigid alignment of ``init_layer_A`` / ``init_layer_B`` under
+    ``init_metric`` (``coarse_rigid_alignment``; default: the first layer), and then, on the transformed ``coordsA``,
+    ``sigma2`` (``init_sigma2``), the missing Gaussian parameters (``init_probability_parameters``) and ``samples_s``, the
+    larger bounding-box volume (``:738-741``).
+
+    Returns ``start``, a dict of ``probability_parameters``, ``inducing_variables``, ``sigma2``, ``samples_s`` and ``inliers``
+    (None without ``nn_init``) with the attributes ``start.coordsA`` (the transformed coordinates), ``start.init_R`` and
+    ``start.init_t``: ``morpho_iterate(start.coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity=, probability_type=,
+    beta=, lambdaVF=, max_iter=, **start)`` runs the loop from it, and likewise ``morpho_iterate_svi``.
+
+    The reference builds ``U`` and ``GammaSparse`` from ``coordsA`` BEFORE the coarse transform and lets the transform move
+    ``coordsA`` alone.  Here the inducing variables are returned moved by the same ``init_R``, ``init_t``: the Gaussian
+    kernel depends on distances only and a rigid motion, a flip included, keeps them, so ``U = con_K(coordsA,
+    inducing_variables)`` and ``GammaSparse`` are the reference's.
+
+    ``subsample_A`` / ``subsample_B`` (used by all three subsampled stages) and ``inducing_idx`` (rows of the unique
+    ``coordsA``) pin what the reference draws with ``np.random.choice``; without them the draws are
+    ``np.random.default_rng(seed)``'s - NOT the reference's stream."""
+    from .preprocess import unique_rows
+
+    XA, XB = _coords_pair(coordsA, coordsB, "morpho_start")
+    LA, LB, codes, _, params, estimate = _start_layers(exp_layers_A, exp_layers_B, dissimilarity, probability_type,
+                                                       probability_parameters, label_transfer, "morpho_start")
+    if len(LA[0]) != len(XA) or len(LB[0]) != len(XB):
+        raise ValueError("every layer must have one row per cell of its slice")
+    if isinstance(inducing_variables_num, bool) or int(inducing_variables_num) != inducing_variables_num or inducing_variables_num < 1:
+        raise ValueError("inducing_variables_num must be a positive integer")
+    # one stream for every draw of our own, A before B: the rows of sigma2 and of the parameters first (what init_sigma2 and
+    # init_probability_parameters draw from the same seed), then the coarse alignment's, then the inducing variables
+    rng = np.random.default_rng(seed)
+    iA = _draw(len(XA), subsample_A, subsample, rng, "subsample_A")
+    iB = _draw(len(XB), subsample_B, subsample, rng, "subsample_B")
+    FA = LA[0] if init_layer_A is None else init_layer_A
+    FB = LB[0] if init_layer_B is None else init_layer_B
+    out = _Start(inliers=None)
+    R, t = np.eye(XA.shape[1]), np.zeros(XA.shape[1])
+    moved = XA
+    if nn_init:
+        if init_layer_A is None and codes[0][0] == _lib.ASSIGN_LABEL:
+            raise ValueError("morpho_start: nn_init needs init_layer_A / init_layer_B when the first layer is a label layer")
+        cA, cB = (iA, iB) if n_sampling == subsample else (subsample_A, subsample_B)
+        _, _, _, _, cA, cB = _coarse_arguments(XA, XB, FA, FB, init_metric, nn_init_top_K, n_sampling, cA, cB, rng, dtype)
+        # (its refusals - fewer than 22 pairs among them - come before the device is touched: unique_rows follows it)
+        c = coarse_rigid_alignment(XA, XB, FA, FB, metric=init_metric, nn_init_top_K=nn_init_top_K, allow_flip=allow_flip,
+                                   init_transform=init_transform, subsample_A=cA, subsample_B=cB, dtype=dtype, device=device)
+        out["inliers"], R, t = c["inliers"], c["init_R"], c["init_t"]
+        if init_transform:
+            moved = c["coordsA"]
+    elif dtype not in ("float32", "float64"):
+        raise ValueError("dtype must be 'float32' or 'float64'")
+    # ---- _construct_kernel's draw (:845-852), on coordsA as given; the chosen rows move with the slice ----
+    uniq, uniq_idx = unique_rows(XA, device=device)
+    pick = _draw(len(uniq), inducing_idx, int(inducing_variables_num), rng, "inducing_idx")
+    ctrl, XA = moved[uniq_idx[pick], :], moved
+    out["sigma2"] = init_sigma2(XA, XB, sigma2_init_scale=sigma2_init_scale, subsample_A=iA, subsample_B=iB, dtype=dtype,
+                                device=device)
+    out["probability_parameters"] = list(params)
+    if estimate:
+        k = _rt._shared_kernels(device, dtype)
+        for l, v in _estimate_parameters(k, LA, LB, codes, estimate, iA, iB).items():
+            out["probability_parameters"][l] = v
+    out["inducing_variables"] = ctrl
+    out["samples_s"] = float(max(np.prod(XA.max(0) - XA.min(0)), np.prod(XB.max(0) - XB.min(0))))   # :738-741
+    out.coordsA, out.init_R, out.init_t = XA, R, t
+    return out
