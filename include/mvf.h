@@ -503,6 +503,19 @@ int64_t mvf_assign_padded_features(int64_t g, int metric);
  * row constant a_i (side 0) or b_j (side 1), formed from the operands as stored.  n == 0 launches nothing. */
 int mvf_assign_prepare(const double* layer, int64_t n, int64_t g, int metric, int side, void* Lp, int64_t ld, double* ab,
                        mvf_dtype dtype, void* stream);
+/* The same from the CSR arrays of a sparse layer (device): indptr (n + 1 int64, non-decreasing, indptr[0] >= 0 - the CALLER
+ * checks that, spateo_amd does on the host), indices (int32) and data (float32 if data_is_f32, else float64), n rows and
+ * g < 2^31 columns.  Lp and ab are, bit for bit, what mvf_assign_prepare writes for the dense float64 matrix
+ * M[i][indices[e]] = (double)data[e], zeros elsewhere: one wave per row expands the row into a staging row of g float64
+ * inside `workspace` and runs the dense entry point's row routine on it, so no n x g buffer exists on the device either.
+ * The column indices of a row must be distinct (any order); an entry whose index lies outside [0, g) is skipped, never
+ * used as an address.  workspace: at least mvf_assign_prepare_csr_min_workspace_bytes(g) (four staging rows), 8-byte
+ * aligned; more rows are used when they fit, and the result does not depend on the size.  No atomics: two calls give the
+ * same bits.  n == 0 launches nothing.  (An addition behind version 7.) */
+size_t mvf_assign_prepare_csr_min_workspace_bytes(int64_t g);
+int mvf_assign_prepare_csr(const int64_t* indptr, const int32_t* indices, const void* data, int data_is_f32, int64_t n, int64_t g,
+                           int metric, int side, void* Lp, int64_t ld, double* ab, void* workspace, size_t workspace_bytes,
+                           mvf_dtype dtype, void* stream);
 /* One side of a label layer: labels (n int32, device) -> ab (n float64, device) = min(max(label, 0), classes - 1), the
  * representation mvf_assign_layer's a (classes = K) / b (classes = L) hold.  The clamp only keeps the table look-up inside
  * the table; a label outside 0 .. classes - 1 is the CALLER's error to report (spateo_amd.align does, on the host).

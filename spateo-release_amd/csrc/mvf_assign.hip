@@ -813,14 +813,11 @@ __global__ __launch_bounds__(256) void assign_sum_kernel(const double* __restric
 // ---- operand preparation: one wave per cell
 __device__ __forceinline__ double wave_all_sum(double v) { return __shfl(wave_sum(v), 0, 64); }
 
+// one row of one side of one product layer, by the 64 lanes of one wave: x (g float64) -> o (ld, cell dtype; the tail zero);
+// returns the row constant on every lane.  Sums run lane-strided over k and then across the wave: every caller gets the
+// same bits for the same x.
 template <typename T>
-__global__ __launch_bounds__(256) void assign_prepare_kernel(const double* __restrict__ Lraw, int64_t n, int64_t g, int metric,
-                                                             int side, T* __restrict__ Lp, int64_t ld, double* __restrict__ ab) {
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    const double* x = Lraw + i * g;
-    T* o = Lp + i * ld;
+__device__ __forceinline__ double assign_prepare_row(const double* x, int64_t g, int metric, int side, T* o, int64_t ld, int lane) {
     double cst = 0.0;
     if (metric == MVF_ASSIGN_EUC || metric == MVF_ASSIGN_SQRT_EUC) {
         double s = 0.0;
@@ -860,7 +857,49 @@ __global__ __launch_bounds__(256) void assign_prepare_kernel(const double* __res
     }
     const int64_t gp = metric == MVF_ASSIGN_SYM_KL ? 2 * g : g;
     for (int64_t k = gp + lane; k < ld; k += 64) o[k] = (T)0;
+    return cst;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void assign_prepare_kernel(const double* __restrict__ Lraw, int64_t n, int64_t g, int metric,
+                                                             int side, T* __restrict__ Lp, int64_t ld, double* __restrict__ ab) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const double cst = assign_prepare_row<T>(Lraw + i * g, g, metric, side, Lp + i * ld, ld, lane);
     if (lane == 0) ab[i] = cst;
+}
+
+// ---- the same from CSR: each wave owns one staging row of g float64 (all zero between rows), scatters a CSR row into it,
+// runs assign_prepare_row on it and takes its entries out again; a block walks rows blockIdx.x * 4 + wave, + 4 gridDim.x, ...
+// An entry whose column is outside [0, g) is skipped, never used as an address.  The barriers order the stores and loads of
+// different lanes on one staging row (the loop's trip count is uniform over the block; a wave past n only idles).
+template <typename T, typename V>
+__global__ __launch_bounds__(256) void assign_prepare_csr_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                                                                 const V* __restrict__ data, int64_t n, int64_t g, int metric, int side,
+                                                                 T* Lp, int64_t ld, double* ab, double* stage) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* x = stage + ((int64_t)blockIdx.x * 4 + wave) * g;
+    for (int64_t base = (int64_t)blockIdx.x * 4; base < n; base += (int64_t)gridDim.x * 4) {
+        const int64_t i = base + wave;
+        const bool active = i < n;
+        const int64_t e0 = active ? indptr[i] : 0, e1 = active ? indptr[i + 1] : 0;
+        for (int64_t e = e0 + lane; e < e1; e += 64) {
+            const int64_t c = indices[e];
+            if (c >= 0 && c < g) x[c] = (double)data[e];
+        }
+        __syncthreads();
+        if (active) {
+            const double cst = assign_prepare_row<T>(x, g, metric, side, Lp + i * ld, ld, lane);
+            if (lane == 0) ab[i] = cst;
+        }
+        __syncthreads();
+        for (int64_t e = e0 + lane; e < e1; e += 64) {
+            const int64_t c = indices[e];
+            if (c >= 0 && c < g) x[c] = 0.0;
+        }
+        __syncthreads();
+    }
 }
 
 // labels as the label branch reads them: integers held in float64, clamped into the table
@@ -869,6 +908,8 @@ __global__ __launch_bounds__(256) void assign_label_prepare_kernel(const int32_t
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) ab[i] = (double)min(max(labels[i], 0), classes - 1);
 }
+
+constexpr int CSR_MAX_BLOCKS = 4096;  // staging blocks of mvf_assign_prepare_csr: 16 per CU of a 256-CU device
 
 int64_t padded_features(int64_t g, int metric) { return cdiv(metric == MVF_ASSIGN_SYM_KL ? 2 * g : g, AKS) * AKS; }
 
@@ -1066,6 +1107,51 @@ extern "C" int mvf_assign_prepare(const double* layer, int64_t n, int64_t g, int
     else
         hipLaunchKernelGGL(assign_prepare_kernel<double>, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, layer, n, g, metric, side,
                            (double*)Lp, ld, ab);
+    MVF_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t mvf_assign_prepare_csr_min_workspace_bytes(int64_t g) {
+    if (g <= 0) return 0;
+    return (size_t)g * 4 * sizeof(double);  // one block: four waves, one staging row each
+}
+
+extern "C" int mvf_assign_prepare_csr(const int64_t* indptr, const int32_t* indices, const void* data, int data_is_f32, int64_t n,
+                                      int64_t g, int metric, int side, void* Lp, int64_t ld, double* ab, void* workspace,
+                                      size_t workspace_bytes, mvf_dtype dtype, void* stream) {
+    if (n == 0) return 0;
+    MVF_REQUIRE(n > 0 && g > 0, "mvf_assign_prepare_csr: need n >= 0 and g > 0");
+    MVF_REQUIRE(g < ((int64_t)1 << 31), "mvf_assign_prepare_csr: column indices are int32, g must be below 2^31");
+    MVF_REQUIRE(metric >= MVF_ASSIGN_EUC && metric <= MVF_ASSIGN_COS, "mvf_assign_prepare_csr: bad metric %d", metric);
+    MVF_REQUIRE(side == 0 || side == 1, "mvf_assign_prepare_csr: side must be 0 (A) or 1 (B)");
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "mvf_assign_prepare_csr: bad dtype %d", (int)dtype);
+    MVF_REQUIRE(ld == padded_features(g, metric), "mvf_assign_prepare_csr: ld must be mvf_assign_padded_features(g, metric)");
+    MVF_REQUIRE(indptr && indices && data && Lp && ab && workspace, "mvf_assign_prepare_csr: null pointer");
+    const size_t row_bytes = (size_t)g * sizeof(double);
+    MVF_REQUIRE(workspace_bytes >= 4 * row_bytes, "mvf_assign_prepare_csr: workspace of %zu bytes, need %zu", workspace_bytes,
+                4 * row_bytes);
+    MVF_REQUIRE(((uintptr_t)workspace & 7) == 0, "mvf_assign_prepare_csr: the workspace must be 8-byte aligned");
+    // as many blocks (of four staging rows) as fit, no more than the rows ask for and than keep the device busy
+    int64_t blocks = (int64_t)(workspace_bytes / (4 * row_bytes));
+    blocks = std::min(blocks, std::min(cdiv(n, 4), (int64_t)CSR_MAX_BLOCKS));
+    hipStream_t st = (hipStream_t)stream;
+    MVF_CHECK_HIP(hipMemsetAsync(workspace, 0, (size_t)blocks * 4 * row_bytes, st));
+    const dim3 grid((unsigned)blocks), block(256);
+#define MVF_PREPARE_CSR(T, V)                                                                                                    \
+    hipLaunchKernelGGL((assign_prepare_csr_kernel<T, V>), grid, block, 0, st, indptr, indices, (const V*)data, n, g, metric, side, \
+                       (T*)Lp, ld, ab, (double*)workspace)
+    if (dtype == MVF_F32) {
+        if (data_is_f32)
+            MVF_PREPARE_CSR(float, float);
+        else
+            MVF_PREPARE_CSR(float, double);
+    } else {
+        if (data_is_f32)
+            MVF_PREPARE_CSR(double, float);
+        else
+            MVF_PREPARE_CSR(double, double);
+    }
+#undef MVF_PREPARE_CSR
     MVF_LAUNCH_CHECK();
     return 0;
 }

@@ -18,6 +18,41 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def is_sparse(layer):
+    """A scipy.sparse matrix / array (SciPy is imported only where one may have been handed in)."""
+    if isinstance(layer, (np.ndarray, list, tuple)) or torch.is_tensor(layer):
+        return False
+    import scipy.sparse as sp
+
+    return sp.issparse(layer)
+
+
+CSR_STAGING_MAX_BYTES = 64 << 20  # staging rows of mvf_assign_prepare_csr (g float64 each): at most this much, and
+CSR_STAGING_MAX_ROWS = 16384      # no more rows than the library launches blocks of four for
+
+
+def csr_arrays(layer):
+    """A scipy.sparse layer -> (indptr int64, indices int32, data float32 | float64, n, g), the host arrays
+    mvf_assign_prepare_csr reads, in O(nnz): canonical CSR (duplicates summed on a copy), integer counts cast to
+    float64.  indptr is checked here (non-decreasing from >= 0, ending inside `data`), before anything is launched."""
+    m = layer.tocsr()
+    n, g = m.shape
+    if g > np.iinfo(np.int32).max:
+        raise ValueError(f"a sparse layer may have at most 2^31 - 1 columns (int32 column indices), got {g}")
+    indptr = np.asarray(m.indptr)
+    if indptr.shape != (n + 1,) or indptr[0] < 0 or (np.diff(indptr) < 0).any() or indptr[-1] > len(m.data) or len(m.indices) != len(m.data):
+        raise ValueError("malformed CSR layer: indptr must have n + 1 non-decreasing entries from >= 0 that end inside data")
+    if not m.has_canonical_format:
+        m = m.copy()
+        m.sum_duplicates()
+        indptr = np.asarray(m.indptr)
+    data = np.asarray(m.data)
+    if data.dtype not in (np.float32, np.float64):
+        data = data.astype(np.float64)
+    return (np.ascontiguousarray(indptr, dtype=np.int64), np.ascontiguousarray(m.indices, dtype=np.int32),
+            np.ascontiguousarray(data), int(n), int(g))
+
+
 def _on_device(fn):
     """Run a kernel method with the instance's GPU as the thread's current HIP device: libmvf launches on the stream it
     is handed, but hipFuncSetAttribute / hipMemsetAsync / occupancy queries inside it act on the CURRENT device, which
@@ -593,7 +628,11 @@ class HipKernels:
     @_on_device
     def assign_prepare(self, layer, metric, side):
         """One side (0 = A cells, 1 = B cells) of one layer of the assignment step: host (n, g) float64 -> device
-        (X' or Y' (n, ld) in the cell dtype, a or b (n,) float64, ld)  (mvf_assign_prepare)."""
+        (X' or Y' (n, ld) in the cell dtype, a or b (n,) float64, ld)  (mvf_assign_prepare).  A scipy.sparse layer goes up
+        as its CSR arrays and is expanded row by row on the device (mvf_assign_prepare_csr): the same bits, and no (n, g)
+        float64 array on either side of the link."""
+        if is_sparse(layer):
+            return self._assign_prepare_csr(layer, metric, side)
         L = np.ascontiguousarray(layer, dtype=np.float64)
         n, g = L.shape
         ld = int(self.lib.mvf_assign_padded_features(g, int(metric)))
@@ -601,6 +640,27 @@ class HipKernels:
         ab = self.empty(n, dtype=torch.float64)
         _lib.check(self.lib.mvf_assign_prepare(_ptr(self.h2d(L)), n, g, int(metric), int(side), _ptr(Lp), ld, _ptr(ab),
                                                self.cdtype, self._stream()), "mvf_assign_prepare")
+        return Lp, ab, ld
+
+    def _assign_prepare_csr(self, layer, metric, side):
+        indptr, indices, data, n, g = csr_arrays(layer)
+        ld = int(self.lib.mvf_assign_padded_features(g, int(metric)))
+        Lp = self.empty(n, ld)
+        ab = self.empty(n, dtype=torch.float64)
+        if n == 0:
+            return Lp, ab, ld
+        if len(data) == 0:  # an all-zero layer: the arrays still need an address
+            indices, data = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=data.dtype)
+        need = int(self.lib.mvf_assign_prepare_csr_min_workspace_bytes(g))
+        rows = min(-(-n // 4) * 4, CSR_STAGING_MAX_ROWS, max(4, CSR_STAGING_MAX_BYTES // (8 * g) // 4 * 4))
+        ws = self.empty(max(need, rows * g * 8) // 8, dtype=torch.float64)
+        # (the three uploads stay referenced until the launch is queued: a tensor dropped right after its address is taken
+        # hands its block back to the allocator, and the next upload may be given the same address)
+        d_indptr, d_indices, d_data = self.h2d(indptr), self.h2d(indices), self.h2d(data)
+        _lib.check(self.lib.mvf_assign_prepare_csr(_ptr(d_indptr), _ptr(d_indices), _ptr(d_data),
+                                                   int(data.dtype == np.float32), n, g, int(metric), int(side), _ptr(Lp), ld,
+                                                   _ptr(ab), _ptr(ws), ws.numel() * 8, self.cdtype, self._stream()),
+                   "mvf_assign_prepare_csr")
         return Lp, ab, ld
 
     @_on_device

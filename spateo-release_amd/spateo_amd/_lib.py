@@ -109,6 +109,8 @@ SIGNATURES = {
                                 _d, _d, _i, _i, _i, _p, _p, _p, _i, _p]),
     "mvf_assign_padded_features": (_i64, [_i64, _i]),
     "mvf_assign_prepare": (_i, [_p, _i64, _i64, _i, _i, _p, _i64, _p, _i, _p]),
+    "mvf_assign_prepare_csr_min_workspace_bytes": (_sz, [_i64]),
+    "mvf_assign_prepare_csr": (_i, [_p, _p, _p, _i, _i64, _i64, _i, _i, _p, _i64, _p, _p, _sz, _i, _p]),
     "mvf_assign_label_prepare": (_i, [_p, _i64, _i64, _p, _p]),
     "mvf_assign_workspace_bytes": (_sz, [_i64, _i64]),
     "mvf_assign": (_i, [_p, _i64, _p, _i64, C.POINTER(AssignLayer), _i, _p, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _sz, _i,

@@ -16,11 +16,13 @@ import torch
 
 from . import _lib
 from . import _runtime as _rt
+from ._kernels import is_sparse
 from .engine import SparseVFCEngine, _consistent_K
 from .vectorfield import vector_field_function
 
 __all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate", "morpho_iterate_svi",
-           "label_transfer_matrix", "init_sigma2", "init_probability_parameters", "coarse_rigid_alignment", "morpho_start"]
+           "label_transfer_matrix", "init_sigma2", "init_probability_parameters", "coarse_rigid_alignment", "morpho_start",
+           "Morpho_pairwise", "morpho_align"]
 
 RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
 
@@ -121,10 +123,11 @@ def _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilar
         if met == "label":
             LA[l], LB[l] = _label_arguments(LA[l], LB[l], len(XA), len(XB), table)
         else:
-            A, B = LA[l], LB[l] = np.asarray(LA[l], dtype=np.float64), np.asarray(LB[l], dtype=np.float64)
+            # a scipy.sparse layer stays sparse (HipKernels.assign_prepare expands its CSR arrays on the device)
+            A, B = LA[l], LB[l] = [v.tocsr() if is_sparse(v) else np.asarray(v, dtype=np.float64) for v in (LA[l], LB[l])]
             if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1]:
                 raise AssertionError("X and Y do not have the same number of features.")
-            if len(A) != len(XA) or len(B) != len(XB):
+            if A.shape[0] != len(XA) or B.shape[0] != len(XB):
                 raise ValueError("every layer must have one row per cell of its slice")
         if str(kind).lower() not in _lib.ASSIGN_PROBS:
             raise ValueError(f"Unsupported probability type: {kind}")  # calc_probability (utils.py:983)
@@ -136,6 +139,11 @@ def _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilar
         raise ValueError(f"return_P=True materialises NA x NB = {len(XA) * len(XB)} entries; the cap is "
                          f"{RETURN_P_MAX_ENTRIES} (align.RETURN_P_MAX_ENTRIES)")
     return XA, XB, LA, LB, codes, table
+
+
+def _n_rows(layer):
+    """Rows of a layer as handed in: a scipy.sparse matrix is asked for its shape, never converted."""
+    return layer.shape[0] if is_sparse(layer) else len(np.asarray(layer))
 
 
 def _spatial_outlier(sigma2, gamma, samples_s, NA, D):
@@ -582,7 +590,7 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
                    inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter=0, kappa=1.0, gamma_a=1.0,
                    gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                    update_R=True, dtype: str = "float64", device=None, record=True, origin=None, SVI_mode=False, guidance=None,
-                   sparse_calculation_mode=False, kernel_type="euc", sparse_top_k=1024, label_transfer=None):
+                   sparse_calculation_mode=False, kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False):
     """The iteration loop of Spateo's pairwise alignment on the MI355X: the non-SVI, dense-path body of
     ``Morpho_pairwise.run`` (``spateo/alignment/methods/morpho_class.py:280-294``: assignment -> gamma -> alpha -> non-rigid
     -> rigid -> ``XAHat`` -> sigma2) for ``max_iter`` iterations from the state ``_initialize_variational_variables`` sets
@@ -617,6 +625,10 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     it); nothing else of the iteration changes, the other updates read ``K_NA``, ``K_NB``, ``PXB`` and the scalars.  The result
     gains ``P``, the last assignment's, as a ``scipy.sparse.coo_matrix`` (NA, NB).
 
+    ``return_P=True`` (the dense path only; ``ValueError`` with ``sparse_calculation_mode`` and above
+    ``RETURN_P_MAX_ENTRIES`` entries): the last iteration's assignment runs through ``mvf_assign_dense`` and the result gains
+    its ``P`` (NA, NB), the reference's ``self.P`` after ``run()``.  Every other output keeps its bits.
+
     Not supported (``NotImplementedError``): ``SVI_mode`` (``morpho_iterate_svi`` runs it), ``guidance``,
     ``sparse_calculation_mode`` with ``sparse_top_k`` above 64 (the default, 1024, is the reference constructor's,
     ``morpho_class.py:140``), ``kernel_type="geodist"`` (anything but ``"euc"``), and what
@@ -630,14 +642,30 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
                            probability_parameters, inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter,
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
                            record, SVI_mode, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer)
+    return_P = _return_P_argument(return_P, a["top_k"], len(a["XA"]), len(a["XB"]))
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
-                    partial_robust_level, nn_init_weight, update_R, dtype, device, record)
+                    partial_robust_level, nn_init_weight, update_R, dtype, device, record, return_P=return_P)
+
+
+def _return_P_argument(return_P, top_k, NA, NB_last):
+    """``return_P`` of the loops, validated: the dense P of the last assignment (NA x NB_last) excludes the top-k mode and
+    is capped like update_assignment's."""
+    if not return_P:
+        return False
+    if top_k is not None:
+        raise ValueError("return_P=True (the dense P) and sparse_calculation_mode=True (P as a scipy.sparse.coo_matrix) "
+                         "exclude each other")
+    if NA * NB_last > RETURN_P_MAX_ENTRIES:
+        raise ValueError(f"return_P=True materialises {NA} x {NB_last} = {NA * NB_last} entries; the cap is "
+                         f"{RETURN_P_MAX_ENTRIES} (align.RETURN_P_MAX_ENTRIES)")
+    return True
 
 
 def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b, partial_robust_level,
-             nn_init_weight, update_R, dtype, device, record, svi=None):
+             nn_init_weight, update_R, dtype, device, record, svi=None, return_P=False):
     """The loop of morpho_iterate and, with ``svi = dict(batch_size=, batch_perm= (int32, validated), return_mapping=)``, of
-    morpho_iterate_svi, on validated arguments ``a`` (_iterate_arguments)."""
+    morpho_iterate_svi, on validated arguments ``a`` (_iterate_arguments).  ``return_P``: the LAST assignment executed - the
+    last iteration's, or the closing full one - runs through mvf_assign_dense."""
     XA, XB, ctrl, org, top_k = a["XA"], a["XB"], a["ctrl"], a["origin"], a["top_k"]
     NA, D = XA.shape
     NB, m = len(XB), len(ctrl)
@@ -693,14 +721,16 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
     k.align_transform(A64, V4, None, None, R3, t3, RnA=RnA, XAHat=XAHat)
     dev = blk = None
     ph.mark("setup")
+    closing = svi is not None and svi["return_mapping"]       # a full assignment follows the loop
     for it in range(int(max_iter)):
         outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
+        dense = bool(return_P) and not closing and it == int(max_iter) - 1
         if svi is not None:
             step = min(1.0, 10.0 / (it + 1.0))                 # :894, SVI_deacy = 10
             k.align_gather(perm, (-it * bs) % NB, bs, xb4, B64, layers, xb4_b, B64_b, Yp_b, b_b)
-            dev = _assign_device(k, xa4, xb4_b, layers_b, model_mul, sigma2, sigma2_variance, outlier, top_k=top_k)
+            dev = _assign_device(k, xa4, xb4_b, layers_b, model_mul, sigma2, sigma2_variance, outlier, dense=dense, top_k=top_k)
         else:
-            dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, top_k=top_k)
+            dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, dense=dense, top_k=top_k)
         ph.mark("assign")
         if (it > nonrigid_start_iter or nonrigid) and svi is not None:
             nonrigid = True
@@ -777,7 +807,7 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
             al, sd = k.to_host([alpha, SigmaDiag], own_pinned=False)
             model_mul = k.h2d(np.array(al, dtype=np.float64) * np.exp(-np.array(sd, dtype=np.float64) / sigma2))
         dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance,
-                             _spatial_outlier(sigma2, gamma, samples_s, NA, D), top_k=top_k)
+                             _spatial_outlier(sigma2, gamma, samples_s, NA, D), dense=bool(return_P), top_k=top_k)
         k.align_moments(A64, V4, dev["K_NA"], dev["K_NA_spatial"], dev["K_NA_sigma2"], SigmaDiag, dev["PXB"], B64, dev["K_NB"],
                         block, origin=org, extra=dev["scalars"])
         blk = np.array(k.to_host([block])[0], dtype=np.float64)
@@ -801,6 +831,8 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
     if top_k is not None and (svi is None or svi["return_mapping"]):   # the mapping: the last (full) assignment's sparse P
         rows, vals = k.to_host([dev["rows"], dev["vals"]], own_pinned=False)
         out["P"] = _coo_from_lists(rows, vals, NA)
+    if return_P:
+        out["P"] = np.array(k.to_host([dev["P"]], own_pinned=False)[0], dtype=np.float64)
     if record:
         out["history"] = {q: np.array(v) for q, v in history.items()}
     ph.mark("result")
@@ -855,7 +887,7 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
                        gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                        update_R=True, dtype: str = "float64", device=None, record=True, origin=None, batch_size=None,
                        batch_perm=None, seed=None, return_mapping=False, guidance=None, sparse_calculation_mode=False,
-                       kernel_type="euc", sparse_top_k=1024, label_transfer=None):
+                       kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False):
     """The SVI mode of the same loop - the reference constructor's default, ``SVI_mode=True``
     (``spateo/alignment/methods/morpho_class.py:136, 283-284, 749-760, 894-896``): every iteration sees ``batch_size`` cells
     of the B slice and blends what it learns into running averages with ``step_size = min(1, 10 / (iter + 1))``.
@@ -884,6 +916,10 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
     to NA, the columns are the batch's); ``P`` (``scipy.sparse.coo_matrix`` (NA, NB)) is returned only with
     ``return_mapping=True``, from the closing full assignment (``:299-302``).
 
+    ``return_P=True`` (dense path only, capped as in ``morpho_iterate``): the last assignment executed runs through
+    ``mvf_assign_dense`` and its ``P`` is returned - the last batch's, (NA, ``batch_size``) with the columns in the batch's
+    order, or with ``return_mapping=True`` the closing full one's, (NA, NB).  Every other output keeps its bits.
+
     Not supported (``NotImplementedError``): what ``morpho_iterate`` refuses but ``SVI_mode``.
 
     Returns ``morpho_iterate``'s dict - ``K_NA``, ``K_NB`` (``batch_size``,), ``K_NA_spatial``, ``K_NA_sigma2`` of the last
@@ -894,9 +930,10 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
                            record, False, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer)
     bs, perm = _svi_arguments(len(a["XB"]), batch_size, batch_perm, seed)
+    return_P = _return_P_argument(return_P, a["top_k"], len(a["XA"]), len(a["XB"]) if return_mapping else bs)
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
                     partial_robust_level, nn_init_weight, update_R, dtype, device, record,
-                    svi=dict(batch_size=bs, batch_perm=perm, return_mapping=bool(return_mapping)))
+                    svi=dict(batch_size=bs, batch_perm=perm, return_mapping=bool(return_mapping)), return_P=return_P)
 
 
 # ---- the start state: what the reference computes in front of the loop (morpho_class.py:700-747, 771-820, 845-852, 898-1041) ----
@@ -986,7 +1023,7 @@ def _start_layers(exp_layers_A, exp_layers_B, dissimilarity, probability_type, p
         if metrics[l] == "label":  # the reference calls calc_distance without a table there (:813) and fails
             raise ValueError(f"{who}: layer {l} is a 'label' layer with probability type 'gauss' and no parameter; the "
                              f"reference cannot estimate it either - pass probability_parameters[{l}]")
-    NA, NB = len(np.asarray(LA[0])), len(np.asarray(LB[0]))
+    NA, NB = _n_rows(LA[0]), _n_rows(LB[0])
     filled = [1.0 if l in estimate else params[l] for l in range(n)]
     _, _, LA, LB, codes, table = _assignment_arguments(np.zeros((NA, 2)), np.zeros((NB, 2)), LA, LB, metrics, kinds, filled, False,
                                                        label_transfer, who)
@@ -1024,8 +1061,8 @@ def init_probability_parameters(exp_layers_A, exp_layers_B, *, dissimilarity, pr
     LA, LB, codes, _, params, estimate = _start_layers(exp_layers_A, exp_layers_B, dissimilarity, probability_type,
                                                        probability_parameters, label_transfer, "init_probability_parameters")
     rng = np.random.default_rng(seed)
-    iA = _draw(len(LA[0]), subsample_A, subsample, rng, "subsample_A")
-    iB = _draw(len(LB[0]), subsample_B, subsample, rng, "subsample_B")
+    iA = _draw(_n_rows(LA[0]), subsample_A, subsample, rng, "subsample_A")
+    iB = _draw(_n_rows(LB[0]), subsample_B, subsample, rng, "subsample_B")
     out = list(params)
     if estimate:
         k = _rt._shared_kernels(device, dtype)
@@ -1038,7 +1075,7 @@ def _voxel_data(coords, gene_exp, voxel_num):
     """``voxel_data`` (utils.py:1283-1336) without its loop over all voxels: a point can lie within ``voxel_size / 2`` only of
     the grid nodes whose index along every axis is within reach, so every point visits those few and the reference's own test
     ``sqrt(sum((coords - voxel_coord)**2)) < voxel_size / 2`` decides.  Returns (voxel_coords, voxel_gene_exps) of the
-    occupied voxels in the reference's order (``np.meshgrid``'s)."""
+    occupied voxels in the reference's order (``np.meshgrid``'s).  ``gene_exp`` may be a scipy.sparse matrix (float64)."""
     from scipy.sparse import csr_matrix
 
     N, D = coords.shape
@@ -1069,7 +1106,8 @@ def _voxel_data(coords, gene_exp, voxel_num):
     member = csr_matrix((np.ones(len(vox)), (vox, pts)), shape=(len(nodes), N))
     count = np.asarray(member.sum(1)).reshape(-1)
     used = count > 0
-    means = np.asarray(member[used] @ gene_exp) / count[used][:, None]
+    sums = member[used] @ gene_exp                     # a sparse layer: a sparse product, dense only as voxels x g
+    means = (sums.toarray() if is_sparse(sums) else np.asarray(sums)) / count[used][:, None]
     return nodes[used], means
 
 
@@ -1140,10 +1178,10 @@ def _coarse_arguments(coordsA, coordsB, init_A, init_B, metric, nn_init_top_K, n
     if metric not in _lib.ASSIGN_METRICS or metric == "label":
         raise ValueError(f"coarse_rigid_alignment: metric must be one of the product metrics (the reference uses 'kl' for "
                          f"init_field='layer' and 'euc' otherwise), got {metric!r}")
-    FA, FB = np.asarray(init_A, dtype=np.float64), np.asarray(init_B, dtype=np.float64)
+    FA, FB = (v.tocsr() if is_sparse(v) else np.asarray(v, dtype=np.float64) for v in (init_A, init_B))
     if FA.ndim != 2 or FB.ndim != 2 or FA.shape[1] != FB.shape[1] or FA.shape[1] < 1:
         raise AssertionError("X and Y do not have the same number of features.")
-    if len(FA) != len(XA) or len(FB) != len(XB):
+    if FA.shape[0] != len(XA) or FB.shape[0] != len(XB):
         raise ValueError("init_A and init_B must have one row per cell of their slice")
     if isinstance(nn_init_top_K, bool) or int(nn_init_top_K) != nn_init_top_K or nn_init_top_K < 1:
         raise ValueError(f"nn_init_top_K must be a positive integer, got {nn_init_top_K!r}")
@@ -1250,7 +1288,8 @@ def morpho_start(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity,
 
     Returns ``start``, a dict of ``probability_parameters``, ``inducing_variables``, ``sigma2``, ``samples_s`` and ``inliers``
     (None without ``nn_init``) with the attributes ``start.coordsA`` (the transformed coordinates), ``start.init_R`` and
-    ``start.init_t``: ``morpho_iterate(start.coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity=, probability_type=,
+    ``start.init_t`` (and ``start.inducing_rows``, the rows of ``coordsA`` the inducing variables were taken from):
+    ``morpho_iterate(start.coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity=, probability_type=,
     beta=, lambdaVF=, max_iter=, **start)`` runs the loop from it, and likewise ``morpho_iterate_svi``.
 
     The reference builds ``U`` and ``GammaSparse`` from ``coordsA`` BEFORE the coarse transform and lets the transform move
@@ -1266,7 +1305,7 @@ def morpho_start(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity,
     XA, XB = _coords_pair(coordsA, coordsB, "morpho_start")
     LA, LB, codes, _, params, estimate = _start_layers(exp_layers_A, exp_layers_B, dissimilarity, probability_type,
                                                        probability_parameters, label_transfer, "morpho_start")
-    if len(LA[0]) != len(XA) or len(LB[0]) != len(XB):
+    if _n_rows(LA[0]) != len(XA) or _n_rows(LB[0]) != len(XB):
         raise ValueError("every layer must have one row per cell of its slice")
     if isinstance(inducing_variables_num, bool) or int(inducing_variables_num) != inducing_variables_num or inducing_variables_num < 1:
         raise ValueError("inducing_variables_num must be a positive integer")
@@ -1307,4 +1346,9 @@ def morpho_start(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity,
     out["inducing_variables"] = ctrl
     out["samples_s"] = float(max(np.prod(XA.max(0) - XA.min(0)), np.prod(XB.max(0) - XB.min(0))))   # :738-741
     out.coordsA, out.init_R, out.init_t = XA, R, t
+    out.inducing_rows = np.asarray(uniq_idx[pick], dtype=np.int64)   # the rows of coordsA the inducing variables are
     return out
+
+
+# the reference's top-level API on the stages above (its module reads this one's names at call time)
+from ._morpho_pairwise import Morpho_pairwise, morpho_align  # noqa: E402
