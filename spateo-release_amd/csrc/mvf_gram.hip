@@ -603,6 +603,258 @@ __global__ __launch_bounds__(256, MVF_CACHED_WPS) void gram_cached_kernel(const 
     }
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// float32 cached path, column panels SHARED by the four waves of a workgroup (gram_cached_kernel_shared_cols).
+// In gram_cached_kernel<float> every wave loads and widens the 8 column blocks of its tile itself: 8 of its 12 float64
+// VALU instructions per k-step repeat what the three other waves do, and float64 VALU time is additive to the MFMA time.
+// Here wave w loads column blocks 2w, 2w + 1 only (edge shape: block w), widens them ONCE and writes them as float64 into an
+// LDS ring; after one workgroup barrier per group of UG k-steps every wave reads its column operands with ds_read_b64.
+// Per wave and k-step: 4 v_cvt_f64_f32 + 2 v_mul_f64 (10 + 2), 4 operand loads (10).  The row operands, the exact P K
+// product, the MFMAs and their order are those of cached_block: G keeps its bits.
+// Ring: SC_SLOTS slots of UG k-steps x 8 blocks x 64 lanes x 8 bytes; lane l of block b of k-step q of a slot sits at
+// ((slot UG + q) 8 + b) 64 + l doubles (conflict-free for ds_read_b64).  Per group g every wave: barrier g; read group g
+// from slot g % SC_SLOTS and wait for it; MFMAs of the first k-step; widen and write ITS blocks of group g + 1; MFMAs of the
+// second k-step.  Read after write: group g + 1 is written behind barrier g and read behind barrier g + 1.  Write after read:
+// a wave that writes slot (g + 1) % SC_SLOTS has passed barrier g, so every wave has finished its reads of groups < g.
+// The LDS traffic is inline assembly: hipcc merges ds_read_b64 pairs 512 bytes apart into ds_read2st64_b64 (4 x the LDS
+// cycles) and sinks LDS prefetches below the MFMAs.  The compiler does not count these operations, so each wait is explicit
+// and the registers it guards pass through an empty statement behind it (nothing that uses them can move above the wait).
+// ----------------------------------------------------------------------------------------------------------------
+constexpr int SC_SLOTS = 4;                          // (two would do by the argument above; four is the measured build)
+constexpr int SC_KSTEP_BYTES = 8 * 64 * 8;           // one k-step: 8 column blocks x 64 lanes x 8 bytes
+constexpr int SC_SLOT_BYTES = UG * SC_KSTEP_BYTES;   // one group
+constexpr int SC_RING_DOUBLES = SC_SLOTS * SC_SLOT_BYTES / 8;
+static_assert(UG == 2, "the ring writes of a group sit between its two k-steps");
+static_assert(SC_SLOTS * SC_SLOT_BYTES <= 65536, "every ring address within one immediate offset");
+
+template <int OFF>
+__device__ __forceinline__ void sc_ds_read_b64(double& d, unsigned addr) {
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
+}
+template <int OFF>
+__device__ __forceinline__ void sc_ds_write_b64(unsigned addr, double d) {
+    asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(d), "n"(OFF) : "memory");
+}
+// every LDS operation of this wave has completed; then the workgroup barrier (no wait on the global prefetch)
+__device__ __forceinline__ void sc_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+__device__ __forceinline__ void sc_wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ void sc_guard(double& d) { asm volatile("" : "+v"(d)); }
+
+template <int I> using SCI = std::integral_constant<int, I>;
+template <int N, int I = 0, typename F>
+__device__ __forceinline__ void sc_for(F&& f) {
+    if constexpr (I < N) {
+        f(SCI<I>{});
+        sc_for<N, I + 1>(f);
+    }
+}
+
+// One wave's share of a tile: 2 row blocks x NB column blocks (NB = 8, or 4: the edge shape); DW >= 0: the balanced diagonal
+// shape of cached_block.  `wave` is this wave's index in the workgroup: it fetches column blocks NF wave .. NF wave + NF - 1.
+// Every wave of the workgroup executes the same number of barriers (the trip counts depend on the slice alone).
+template <int NB, int DW>
+__device__ __forceinline__ void cached_block_shared(const float* __restrict__ ublk, const double* __restrict__ P, int64_t n,
+                                                    int64_t n_pad, int64_t n0, int64_t n1, int64_t rb0, int64_t cb0, int wave,
+                                                    unsigned lds0, double* __restrict__ out, int orow0) {
+    constexpr int NA = 2, NF = NB / 4;
+    static_assert((NB == 8 || NB == 4) && (DW < 0 || (NB == 8 && DW < 4)), "2 x 8, 2 x 4 or a diagonal sub-shape of 2 x 8");
+    const int lane = threadIdx.x & 63;
+    const int li = lane & 15, lk = lane >> 4;
+    auto blk_live = [](int a, int b) constexpr { return DW >= 0 ? b >= (a == 0 ? DW : 7 - DW) : b < NB; };
+    auto rblk = [](int a) constexpr { return DW >= 0 ? (a == 0 ? DW : 7 - DW) : a; };
+    constexpr int C0 = DW >= 0 ? DW : 0;  // first column block this wave reads
+
+    constexpr int BUF_RSRC_WORD3 = 0x00020000;  // raw buffer of 32-bit data (gfx9 family), no swizzle
+    __amdgpu_buffer_rsrc_t ra[NA], rc[NF];
+    const int voff = (lk * UB + li) * (int)sizeof(float);
+    const int nbytes = (int)((n1 - n0) * UB * (int64_t)sizeof(float));  // (< 2^31: checked by the host)
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+        ra[a] = __builtin_amdgcn_make_buffer_rsrc((void*)(ublk + ((rb0 + rblk(a)) * n_pad + n0) * UB), (short)0, nbytes, BUF_RSRC_WORD3);
+#pragma unroll
+    for (int j = 0; j < NF; ++j)
+        rc[j] = __builtin_amdgcn_make_buffer_rsrc((void*)(ublk + ((cb0 + NF * wave + j) * n_pad + n0) * UB), (short)0, nbytes,
+                                                  BUF_RSRC_WORD3);
+    // P of this slice through a buffer resource as well: records = the slice's cells that exist, so the padded cells of the
+    // last slice read 0 (their cached rows are zero: any finite P gives the same exact 0) - the clamp of cached_block's tail
+    const int pbytes = (int)(max((int64_t)0, min(n1, n) - n0) * (int64_t)sizeof(double));
+    const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(P + n0), (short)0, pbytes, BUF_RSRC_WORD3);
+    const int pvoff = lk * (int)sizeof(double);
+    typedef int i32x2 __attribute__((ext_vector_type(2)));
+    const unsigned rd_base = lds0 + (unsigned)lane * 8u;              // + ((slot UG + q) 8 + b) 512
+    const unsigned wr_base = rd_base + (unsigned)(NF * wave) * 512u;  // + (slot UG + q) 4096 + j 512
+
+    f64x4 acc[NA][8];
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
+
+    float ua[2][UG][NA], uc[2][UG][NF];  // two register buffers each: row loads run one group ahead, column loads two
+    double pp[2][UG];
+    double op[UG][8];  // column operands as read from the ring
+    const int ngroups = (int)((n1 - n0) / (4 * UG));  // slices are multiples of 256 cells
+    constexpr int SUPER = 4096 / (UG * 4 * UB * (int)sizeof(float));  // groups per unrolled pass (as cached_block)
+    static_assert(SUPER % 2 == 0 && SUPER % SC_SLOTS == 0, "register buffers and ring slots are static inside a pass");
+
+    // Loads of group g (wave-uniform; the caller clamps it to the slice): one scalar offset per group, the k-step immediate.
+    // Every load of the main loop is issued unconditionally - a branch around a prefetch makes the compiler's counted waits
+    // drain it (the count at a join has to hold for both paths).
+    auto load_rows = [&](int g, float(&A)[UG][NA], double(&Pq)[UG]) {
+        const int soff = __builtin_amdgcn_readfirstlane(g * UG * (4 * UB) * (int)sizeof(float));
+        const int psoff = __builtin_amdgcn_readfirstlane(g * UG * 4 * (int)sizeof(double));
+#pragma unroll
+        for (int q = 0; q < UG; ++q) {
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+                A[q][a] = __builtin_bit_cast(float, (int)__builtin_amdgcn_raw_buffer_load_b32(
+                                                        ra[a], voff + q * (4 * UB) * (int)sizeof(float), soff, 0));
+            Pq[q] = __builtin_bit_cast(
+                double, (i32x2)__builtin_amdgcn_raw_buffer_load_b64(rp, pvoff + q * 4 * (int)sizeof(double), psoff, 0));
+        }
+    };
+    auto load_cols = [&](int g, float(&B)[UG][NF]) {
+        const int soff = __builtin_amdgcn_readfirstlane(g * UG * (4 * UB) * (int)sizeof(float));
+#pragma unroll
+        for (int q = 0; q < UG; ++q)
+#pragma unroll
+            for (int j = 0; j < NF; ++j)
+                B[q][j] = __builtin_bit_cast(float, (int)__builtin_amdgcn_raw_buffer_load_b32(
+                                                        rc[j], voff + q * (4 * UB) * (int)sizeof(float), soff, 0));
+    };
+    // widen this wave's column blocks of one group and write them into ring slot `slot`
+    auto write_cols = [&](auto SLOT, const float(&B)[UG][NF]) {
+        constexpr int slot = decltype(SLOT)::value;
+        sc_for<UG * NF>([&](auto QJ) {
+            constexpr int q = decltype(QJ)::value / NF, j = decltype(QJ)::value % NF;
+            sc_ds_write_b64<(slot * UG + q) * SC_KSTEP_BYTES + j * 512>(wr_base, (double)B[q][j]);
+        });
+    };
+    auto read_cols = [&](auto SLOT, double(&O)[UG][8]) {
+        constexpr int slot = decltype(SLOT)::value;
+        sc_for<UG * (NB - C0)>([&](auto QB) {
+            constexpr int q = decltype(QB)::value / (NB - C0), b = C0 + decltype(QB)::value % (NB - C0);
+            sc_ds_read_b64<((slot * UG + q) * 8 + b) * 512>(O[q][b], rd_base);
+        });
+    };
+    auto guard_cols = [&](double(&O)[UG][8]) {
+#pragma unroll
+        for (int q = 0; q < UG; ++q)
+#pragma unroll
+            for (int b = C0; b < NB; ++b) sc_guard(O[q][b]);
+    };
+    auto compute_group = [&](const float(&A)[UG][NA], const double(&Pq)[UG], const double(&O)[UG][8], auto&& mid) {
+#pragma unroll
+        for (int q = 0; q < UG; ++q) {
+            if (q == UG - 1) mid();
+            double fa[NA];
+            const double pd = Pq[q];
+#pragma unroll
+            for (int a = 0; a < NA; ++a) fa[a] = (double)A[q][a] * pd;  // exact in float64
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    if (blk_live(a, b)) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], O[q][b], acc[a][b], 0, 0, 0);
+            __builtin_amdgcn_s_setprio(0);
+        }
+    };
+
+    // main part: whole passes of SUPER groups whose cells all exist
+    const int64_t live = max((int64_t)0, min(n1, n) - n0);
+    const int ng_main = (int)(min((int64_t)ngroups, live / (4 * UG)) / SUPER) * SUPER;
+    const int g_last = ng_main - 1;  // prefetches past the main part read its last group again (never used)
+    if (ng_main > 0) {               // (then at least SUPER >= 2 groups)
+        load_rows(0, ua[0], pp[0]);
+        load_cols(0, uc[0]);
+        write_cols(SCI<0>{}, uc[0]);  // group 0 into the ring, group 1 on its way
+        load_cols(1, uc[1]);
+        sc_barrier();
+    }
+    for (int g0 = 0; g0 < ng_main; g0 += SUPER) {
+        sc_for<SUPER>([&](auto S) {
+            constexpr int s = decltype(S)::value;
+            load_rows(min(g0 + s + 1, g_last), ua[(s + 1) & 1], pp[(s + 1) & 1]);
+            load_cols(min(g0 + s + 2, g_last), uc[s & 1]);
+            // The widening and the ring writes go BETWEEN the MFMAs of the group's two k-steps: float64 VALU work inside a
+            // wave's own MFMA stream costs a third of what it costs beside the partner wave's (the same writes ahead of the
+            // barrier: + 4 % on the tile stage instead of - 1.3 %, profiles/gram_shared_cols_ab.md)
+            auto mid = [&]() {
+                __builtin_amdgcn_sched_barrier(0);
+                write_cols(SCI<(s + 1) % SC_SLOTS>{}, uc[(s + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            sc_barrier();
+            read_cols(SCI<s % SC_SLOTS>{}, op);
+            sc_wait_lds();
+            guard_cols(op);
+            compute_group(ua[s & 1], pp[s & 1], op, mid);
+            __builtin_amdgcn_sched_barrier(0);  // keep the unrolled groups in program order
+        });
+    }
+    // remainder (fewer than SUPER groups, plus the padded cells of the last slice): unpipelined; slot 0, and a second barrier
+    // before it is written again
+    sc_barrier();
+    for (int g = ng_main; g < ngroups; ++g) {
+        load_rows(g, ua[0], pp[0]);
+        load_cols(g, uc[0]);
+        write_cols(SCI<0>{}, uc[0]);
+        sc_barrier();
+        read_cols(SCI<0>{}, op);
+        sc_wait_lds();
+        guard_cols(op);
+        sc_barrier();
+        compute_group(ua[0], pp[0], op, []() {});
+    }
+
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            if (blk_live(a, b)) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = orow0 + rblk(a) * 16 + lk + 4 * r;
+                    const int col = b * 16 + li;
+                    __builtin_nontemporal_store(acc[a][b][r], &out[row * GT + col]);  // read once, by the reduction
+                }
+            }
+}
+
+__global__ __launch_bounds__(256, 2) void gram_cached_kernel_shared_cols(const float* __restrict__ ublk, const double* __restrict__ P,
+                                                                         int64_t n, int64_t n_pad, int64_t m, int nt, int npairs,
+                                                                         int64_t slice_len, int64_t slice0,
+                                                                         double* __restrict__ partial) {
+    // job decode, slices and partial-tile layout of gram_cached_kernel<float>; all LDS of the kernel is this one ring
+    __shared__ double sc_ring[SC_RING_DOUBLES];
+    constexpr int TB = GT / UB;
+    const unsigned lds0 = (unsigned)(uintptr_t)sc_ring;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int pair = blockIdx.x % npairs;
+    const int64_t slice = blockIdx.x / npairs;
+    int ti, tj;
+    decode_pair(pair, nt, ti, tj);
+    const int64_t n0 = (slice0 + slice) * slice_len;
+    const int64_t n1 = min(n_pad, n0 + slice_len);
+    double* out = partial + ((size_t)slice * npairs + pair) * (size_t)(GT * GT);
+    const int64_t rb = (int64_t)ti * TB, cb = (int64_t)tj * TB;
+    if (ti != tj) {
+        const int64_t live_cols = m - (int64_t)tj * GT;  // > 0
+        if (live_cols <= 4 * UB)
+            cached_block_shared<4, -1>(ublk, P, n, n_pad, n0, n1, rb + 2 * wave, cb, wave, lds0, out, 32 * wave);
+        else
+            cached_block_shared<8, -1>(ublk, P, n, n_pad, n0, n1, rb + 2 * wave, cb, wave, lds0, out, 32 * wave);
+    } else {
+        switch (wave) {
+            case 0: cached_block_shared<8, 0>(ublk, P, n, n_pad, n0, n1, rb, cb, 0, lds0, out, 0); break;
+            case 1: cached_block_shared<8, 1>(ublk, P, n, n_pad, n0, n1, rb, cb, 1, lds0, out, 0); break;
+            case 2: cached_block_shared<8, 2>(ublk, P, n, n_pad, n0, n1, rb, cb, 2, lds0, out, 0); break;
+            default: cached_block_shared<8, 3>(ublk, P, n, n_pad, n0, n1, rb, cb, 3, lds0, out, 0); break;
+        }
+    }
+}
+
 // Pd[i - c0] = (double)P[i] for the cells c0 <= i < c1 of a phase (multiples of 256), 0 for the padded cells i >= n (whose
 // cached rows are zero as well)
 __global__ __launch_bounds__(256) void widen_p_kernel(const float* __restrict__ P, int64_t n, int64_t c0, int64_t c1,
@@ -893,14 +1145,21 @@ extern "C" int mvf_gram_cached(int stages, const void* ublk, const void* x4, con
                 const int64_t c0 = s0 * p.slice_len, c1 = std::min(n_pad, c0 + ns * p.slice_len);
                 hipLaunchKernelGGL(widen_p_kernel, dim3((unsigned)((c1 - c0) / 256)), dim3(256), 0, st, (const float*)P, n,
                                    c0, c1, pd);
-                // The kernel indexes P by ABSOLUTE cell, so it gets the buffer's address biased by - c0: for every phase but
-                // the first that address lies BELOW the workspace.  Valid only because the kernel never indexes it outside
-                // [c0, c1): a job's cells are [n0, n1) with c0 <= n0 and n1 <= c1, and the remainder loop's clamp reads cell
-                // n - 1 at the lowest, which is >= c0 (a phase starts at a slice that holds live cells: c0 < n).
+                // Both kernels index P by ABSOLUTE cell, so they get the buffer's address biased by - c0: for every phase but
+                // the first that address lies BELOW the workspace.  Valid only because neither reads it outside [c0, c1): a
+                // job's cells are [n0, n1) with c0 <= n0 and n1 <= c1.  gram_cached_kernel<float> clamps the index of its
+                // remainder loop and reads cell n - 1 at the lowest, which is >= c0 (a phase starts at a slice that holds live
+                // cells: c0 < n); gram_cached_kernel_shared_cols reads P through a buffer resource based at cell n0 whose
+                // records end at min(n1, n): reads behind it return 0 (the same exact 0 in G: those cached rows are zero).
                 const double* Pd = (const double*)((uintptr_t)pd - (uintptr_t)c0 * sizeof(double));
-                hipLaunchKernelGGL(gram_cached_kernel<float>, dim3(njobs), dim3(256), 0, st, (const float*)ublk,
-                                   Pd, n, n_pad, m, p.nt, p.npairs, p.slice_len, s0,
-                                   (double*)workspace, p.npairs, 0);
+                // same grid, jobs and partial tiles either way; "gram_reg_cols" forces the register-operand kernel
+                if (debug_opt(DBG_GRAM_REG_COLS) == 0) {
+                    hipLaunchKernelGGL(gram_cached_kernel_shared_cols, dim3(njobs), dim3(256), 0, st, (const float*)ublk, Pd, n,
+                                       n_pad, m, p.nt, p.npairs, p.slice_len, s0, (double*)workspace);
+                } else {
+                    hipLaunchKernelGGL(gram_cached_kernel<float>, dim3(njobs), dim3(256), 0, st, (const float*)ublk, Pd, n,
+                                       n_pad, m, p.nt, p.npairs, p.slice_len, s0, (double*)workspace, p.npairs, 0);
+                }
             } else
                 hipLaunchKernelGGL(gram_cached_kernel<double>, dim3((unsigned)(ns * p.njobs)), dim3(256), 0, st,
                                    (const double*)ublk, (const double*)P, n, n_pad, m, p.nt, p.npairs, p.slice_len, s0,

@@ -20,7 +20,7 @@ int set_error(const char* fmt, ...) {
 
 static std::atomic<long long> g_debug[DBG_COUNT];
 static const char* const g_debug_names[DBG_COUNT] = {"conk_form", "slice_len", "solve_small_off", "lr_timing", "lr_no_deflate",
-                                                     "defl_block", "defl_apps", "lr_no_direct", "direct_accept"};
+                                                     "defl_block", "defl_apps", "lr_no_direct", "direct_accept", "gram_reg_cols"};
 long long debug_opt(DebugOpt which) { return g_debug[which].load(std::memory_order_relaxed); }
 
 // Looked up per CURRENT device (the host binding makes the launch stream's device current) and remembered per device

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEV_KNOBS = os.environ.get("MVF_DEV_KNOBS") == "1"
 LIB_PATH = (DEV_KNOBS and os.environ.get("MVF_LIB_PATH")) or os.path.join(_HERE, "lib", "libmvf.so")
 DEBUG_OPTIONS = ("conk_form", "slice_len", "solve_small_off", "lr_timing", "lr_no_deflate", "defl_block", "defl_apps", "lr_no_direct",
-                 "direct_accept")
+                 "direct_accept", "gram_reg_cols")
 _LEGACY_ENV = {  # environment name -> (option, value parser)
     "MVF_CONK": ("conk_form", lambda v: {"rows": 1, "flat": 2, "2d": 3}[v]),
     "MVF_SLICE_LEN": ("slice_len", int),
