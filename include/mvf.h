@@ -552,6 +552,25 @@ int mvf_assign_topk(const void* xa4, int64_t na, const void* xb4, int64_t nb, co
                     const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier, int k,
                     double* K_NA, double* K_NB, double* K_NA_spatial, double* K_NA_sigma2, double* PXB, double* scalars,
                     int32_t* rows, double* vals, void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream);
+/* The cell mapping of the reference (`get_optimal_mapping_relationship` / `mapping_aligned_coords`, spateo/alignment/utils.py:
+ * 157-255) without P: the best partner of every A cell (the maximum of its row of P) and of every B cell (of its column).
+ * With v_ij the value mvf_assign_dense stores in P[i][j] and d_ij the clamped squared spatial distance, per row i over j < nb:
+ *   row_val[i]        max_j v_ij;
+ *   row_idx[2 i]      "nearest": the j first in the total order (v descending, d ascending, j ascending) - keep_all=False,
+ *                     where the reference takes the nearest coordinate among equal maxima (an all-zero row: the nearest B cell);
+ *   row_idx[2 i + 1]  "first": the j first in (v descending, j ascending) - what keep_all=True keeps after its sort and
+ *                     drop-duplicates (an all-zero row: 0);
+ * and the same per column j over i < na in col_idx (nb x 2) / col_val (nb).  Both orders are total and the head of a union is
+ * the head of the heads of its parts, so tiles and splits combine in any order: no floating-point atomics, two calls give the
+ * same bits.  Indices always lie in [0, nb) / [0, na): padding is never offered, and a row or column without one comparable
+ * (non-NaN) entry gets index 0 and value 0.  Arguments, checks and the empty-side return are mvf_assign's.  row_idx / row_val
+ * are both NULL or both given, and so are col_idx / col_val; a NULL pair skips that direction's kernel, both pairs NULL is an
+ * error.  Workspace: mvf_assign's with the splits' states behind it.  (An addition behind version 7.) */
+size_t mvf_assign_best_workspace_bytes(int64_t na, int64_t nb); /* 0 for an empty side */
+int mvf_assign_best(const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers, int nlayers,
+                    const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier,
+                    int32_t* row_idx, double* row_val, int32_t* col_idx, double* col_val, void* workspace,
+                    size_t workspace_bytes, mvf_dtype dtype, void* stream);
 
 /* Column statistics of ONE layer's na x nb distance matrix d_ij, which is never written: what the code in front of the
  * reference's loop reduces its matrices to (`_init_guess_sigma2`, utils.py:1339-1354; `_init_probability_parameters`,

@@ -43,6 +43,11 @@
 // distance matrix, on the same tile routine and with pass 1's grid, to per-column minima, per-column lists of the k smallest
 // entries (the lists of mvf_assign_topk with the order turned round) and the sums of d and d^2; the statistics of the rows are
 // the same call with the operands exchanged.
+//
+// mvf_assign_best (the reference's cell mapping, `get_optimal_mapping_relationship` / `mapping_aligned_coords`,
+// spateo/alignment/utils.py:157-255, which takes row and column maxima of the dense P) runs pass 1 and the factors as they are
+// and then one sweep per direction on the same tile routine: per row and per column of P the largest entry and its index
+// under the reference's two tie rules, from states that combine in any order (see struct Best).
 #include <climits>
 
 #include "mvf_common.h"
@@ -1080,6 +1085,241 @@ int run_layer_stats(hipStream_t st, const StatsPlan& t, const DevLayer& ly, int6
     return 0;
 }
 
+// ---- mvf_assign_best: the mapping (`get_optimal_mapping_relationship` / `mapping_aligned_coords`, spateo/alignment/utils.py:
+// 157-255) without P: per row and per column of P the largest entry and its index under the reference's two tie rules.
+// The entry is v_ij = m_i ((e2_ij q_ij) c3_j), the value and the product order of assign_pass2_kernel<T, P2_DENSE>; d_ij is
+// sq_dist's.  A state is the head of its set in two total orders at once:
+//   nearest  (v descending, d ascending, index ascending)     keep_all=False: among equal maxima the nearest partner
+//   first    (v descending, index ascending)                  keep_all=True after the reference's sort and drop-duplicates
+// The empty state (-inf, +inf, INT_MAX, INT_MAX) loses against every entry.  Taking the head of a union from the heads of
+// its parts is associative and commutative: lanes, halves, tiles and splits may be combined in any order, the bits are the
+// same on every call.  Only live rows / columns are ever offered, so an index is in range or INT_MAX (nothing offered, or
+// nothing but NaN), which the merge turns into index 0, value 0.
+struct Best {
+    double v, d;
+    int in, ifirst;
+};
+
+__device__ __forceinline__ Best best_empty() { return Best{-HUGE_VAL, HUGE_VAL, INT_MAX, INT_MAX}; }
+
+__device__ __forceinline__ void best_combine(Best& s, double v, double d, int in, int ifirst) {
+    if (v > s.v) {
+        s.v = v, s.d = d, s.in = in, s.ifirst = ifirst;
+    } else if (v == s.v) {
+        if (d < s.d || (d == s.d && in < s.in)) s.d = d, s.in = in;
+        s.ifirst = min(s.ifirst, ifirst);
+    }
+}
+
+// workspace of mvf_assign_best behind mvf_assign's: K_NB of the factor kernel (not returned), the column splits' row states
+// rv / rd [csplit][na_pad], ri [csplit][na_pad][2] and the row splits' column states cv / cd [rsplit][nb_pad], ci [..][2]
+struct BestPlan {
+    size_t off_knb, off_rv, off_rd, off_ri, off_cv, off_cd, off_ci, total;
+};
+
+BestPlan make_best_plan(const Plan& p) {
+    BestPlan t;
+    size_t o = p.total;
+    const size_t nr = (size_t)p.csplit * p.na_pad, nc = (size_t)p.rsplit * p.nb_pad;
+    t.off_knb = o, o += align_up((size_t)p.nb_pad * sizeof(double), 256);
+    t.off_rv = o, o += align_up(nr * sizeof(double), 256);
+    t.off_rd = o, o += align_up(nr * sizeof(double), 256);
+    t.off_ri = o, o += align_up(nr * 2 * sizeof(int), 256);
+    t.off_cv = o, o += align_up(nc * sizeof(double), 256);
+    t.off_cd = o, o += align_up(nc * sizeof(double), 256);
+    t.off_ci = o, o += align_up(nc * 2 * sizeof(int), 256);
+    t.total = o;
+    return t;
+}
+
+// ---- the rows' best columns.  Pass 2's grid (row tiles, column splits) and tile walk; a lane keeps the states of its 8 rows
+// over the column tiles of its split; bv / bd [split][na_pad], bi [split][na_pad][2]
+template <typename T>
+__global__ __launch_bounds__(256) void assign_best_rows_kernel(const T* __restrict__ xa4, int64_t na, const T* __restrict__ xb4,
+                                                               int64_t nb, DevLayers L, const double* __restrict__ mm, double h2,
+                                                               const double* __restrict__ fac, int64_t ctiles, int64_t na_pad,
+                                                               double* __restrict__ bv, double* __restrict__ bd,
+                                                               int* __restrict__ bi) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, lk = lane >> 4, wi = wave >> 1, wj = wave & 1;
+    const int64_t i0 = (int64_t)blockIdx.x * AT + 32 * wi;
+    const int64_t t_lo = ctiles * blockIdx.y / gridDim.y, t_hi = ctiles * (blockIdx.y + 1) / gridDim.y;
+    Point pa[2][4];
+    double mi[2][4];
+    Best st[2][4];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t i = std::min<int64_t>(i0 + 16 * a + lk + 4 * r, na - 1);
+            pa[a][r] = load_point(xa4, i), mi[a][r] = mm[i], st[a][r] = best_empty();
+        }
+    for (int64_t t = t_lo; t < t_hi; ++t) {
+        const int64_t j0 = t * AT + 32 * wj;
+        f64x4 q[2][2];
+        layer_product<T>(L, i0, j0, na, nb, li, lk, q);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int64_t j = j0 + 16 * b + li;  // < nb_pad
+            if (j >= nb) continue;               // a padded column is never offered
+            const Point cb = load_point(xb4, j);
+            const double c3 = fac[4 * j + 2];
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double d = sq_dist(pa[a][r], cb);
+                    const double v = mi[a][r] * ((exp(d * h2) * q[a][b][r]) * c3);  // P_ij as mvf_assign_dense stores it
+                    best_combine(st[a][r], v, d, (int)j, (int)j);
+                }
+        }
+    }
+    // the 16 column lanes of a row by a butterfly (the combination is commutative: every lane ends with the same state), then
+    // the two column halves of the tile through LDS
+    __shared__ double rv[2][AT], rd[2][AT];
+    __shared__ int ri[2][AT][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            Best s = st[a][r];
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) {
+                const double ov = __shfl_xor(s.v, o, 64), od = __shfl_xor(s.d, o, 64);
+                const int on = __shfl_xor(s.in, o, 64), of = __shfl_xor(s.ifirst, o, 64);
+                best_combine(s, ov, od, on, of);
+            }
+            if (li == 0) {
+                const int row = 32 * wi + 16 * a + lk + 4 * r;
+                rv[wj][row] = s.v, rd[wj][row] = s.d, ri[wj][row][0] = s.in, ri[wj][row][1] = s.ifirst;
+            }
+        }
+    __syncthreads();
+    if (threadIdx.x < AT) {
+        const int row = threadIdx.x;
+        Best s{rv[0][row], rd[0][row], ri[0][row][0], ri[0][row][1]};
+        best_combine(s, rv[1][row], rd[1][row], ri[1][row][0], ri[1][row][1]);
+        const int64_t o = (int64_t)blockIdx.y * na_pad + (int64_t)blockIdx.x * AT + row;
+        bv[o] = s.v, bd[o] = s.d, bi[2 * o] = s.in, bi[2 * o + 1] = s.ifirst;
+    }
+}
+
+// ---- the columns' best rows.  Pass 1's grid (column tiles, row splits) and tile walk; a lane keeps the states of its 2
+// columns over the row tiles of its split; bv / bd [split][nb_pad], bi [split][nb_pad][2]
+template <typename T>
+__global__ __launch_bounds__(256) void assign_best_cols_kernel(const T* __restrict__ xa4, int64_t na, const T* __restrict__ xb4,
+                                                               int64_t nb, DevLayers L, const double* __restrict__ mm, double h2,
+                                                               const double* __restrict__ fac, int64_t rtiles, int64_t nb_pad,
+                                                               double* __restrict__ bv, double* __restrict__ bd,
+                                                               int* __restrict__ bi) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, lk = lane >> 4, wi = wave >> 1, wj = wave & 1;
+    const int64_t j0 = (int64_t)blockIdx.x * AT + 32 * wj;
+    const int64_t t_lo = rtiles * blockIdx.y / gridDim.y, t_hi = rtiles * (blockIdx.y + 1) / gridDim.y;
+    Point cb[2];
+    double c3[2];
+    Best st[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int64_t j = j0 + 16 * b + li;  // < nb_pad: fac is zero for nb <= j (those columns are not merged)
+        cb[b] = load_point(xb4, std::min<int64_t>(j, nb - 1)), c3[b] = fac[4 * j + 2], st[b] = best_empty();
+    }
+    for (int64_t t = t_lo; t < t_hi; ++t) {
+        const int64_t i0 = t * AT + 32 * wi;
+        f64x4 q[2][2];
+        layer_product<T>(L, i0, j0, na, nb, li, lk, q);
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t i = i0 + 16 * a + lk + 4 * r;
+                if (i >= na) continue;  // a padded row is never offered
+                const Point pa = load_point(xa4, i);
+                const double m = mm[i];
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const double d = sq_dist(pa, cb[b]);
+                    const double v = m * ((exp(d * h2) * q[a][b][r]) * c3[b]);  // P_ij as mvf_assign_dense stores it
+                    best_combine(st[b], v, d, (int)i, (int)i);
+                }
+            }
+    }
+    // the 8 (row half, lane group) states of every column through LDS, as pass 1 adds its partial sums
+    __shared__ double rv[8][AT], rd[8][AT];
+    __shared__ int ri[8][AT][2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int g = wi * 4 + lk, c = 32 * wj + 16 * b + li;
+        rv[g][c] = st[b].v, rd[g][c] = st[b].d, ri[g][c][0] = st[b].in, ri[g][c][1] = st[b].ifirst;
+    }
+    __syncthreads();
+    if (threadIdx.x < AT) {
+        const int c = threadIdx.x;
+        Best s{rv[0][c], rd[0][c], ri[0][c][0], ri[0][c][1]};
+#pragma unroll
+        for (int g = 1; g < 8; ++g) best_combine(s, rv[g][c], rd[g][c], ri[g][c][0], ri[g][c][1]);
+        const int64_t o = (int64_t)blockIdx.y * nb_pad + (int64_t)blockIdx.x * AT + c;
+        bv[o] = s.v, bd[o] = s.d, bi[2 * o] = s.in, bi[2 * o + 1] = s.ifirst;
+    }
+}
+
+// ---- the splits' states of one row / column combined: idx[e] = {nearest, first}, val[e] = the maximum.  `limit`: the size
+// of the other side; an index outside [0, limit) - nothing comparable was offered - becomes index 0 with value 0
+__global__ __launch_bounds__(256) void assign_best_merge_kernel(const double* __restrict__ bv, const double* __restrict__ bd,
+                                                                const int* __restrict__ bi, int64_t nsplit, int64_t n,
+                                                                int64_t n_pad, int limit, int* __restrict__ idx,
+                                                                double* __restrict__ val) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    Best s = best_empty();
+    for (int64_t sp = 0; sp < nsplit; ++sp) {
+        const int64_t o = sp * n_pad + e;
+        best_combine(s, bv[o], bd[o], bi[2 * o], bi[2 * o + 1]);
+    }
+    const bool real = s.in >= 0 && s.in < limit && s.ifirst >= 0 && s.ifirst < limit;
+    idx[2 * e] = real ? s.in : 0, idx[2 * e + 1] = real ? s.ifirst : 0;
+    val[e] = real ? s.v : 0.0;
+}
+
+template <typename T>
+int run_assign_best(hipStream_t st, const Plan& p, const BestPlan& bp, const void* xa4, int64_t na, const void* xb4, int64_t nb,
+                    const DevLayers& L, const double* mm, double h1, double h2, double outlier, int* row_idx, double* row_val,
+                    int* col_idx, double* col_val, char* ws) {
+    double* part1 = (double*)(ws + p.off_part1);
+    double* fac = (double*)(ws + p.off_fac);
+    double* K_NB = (double*)(ws + bp.off_knb);
+    const dim3 grid1((unsigned)p.ctiles, (unsigned)p.rsplit), grid2((unsigned)p.rtiles, (unsigned)p.csplit);
+    hipLaunchKernelGGL((assign_pass1_kernel<T>), grid1, dim3(256), 0, st, (const T*)xa4, na, (const T*)xb4, nb, L, mm, h1, h2,
+                       p.rtiles, p.nb_pad, part1);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(assign_factors_kernel, dim3((unsigned)cdiv(p.nb_pad, 256)), dim3(256), 0, st, part1, p.rsplit, nb, p.nb_pad,
+                       outlier, fac, K_NB);
+    MVF_LAUNCH_CHECK();
+    if (row_idx) {
+        double* bv = (double*)(ws + bp.off_rv);
+        double* bd = (double*)(ws + bp.off_rd);
+        int* bi = (int*)(ws + bp.off_ri);
+        hipLaunchKernelGGL((assign_best_rows_kernel<T>), grid2, dim3(256), 0, st, (const T*)xa4, na, (const T*)xb4, nb, L, mm, h2,
+                           fac, p.ctiles, p.na_pad, bv, bd, bi);
+        MVF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(assign_best_merge_kernel, dim3((unsigned)cdiv(na, 256)), dim3(256), 0, st, bv, bd, bi, p.csplit, na,
+                           p.na_pad, (int)nb, row_idx, row_val);
+        MVF_LAUNCH_CHECK();
+    }
+    if (col_idx) {
+        double* bv = (double*)(ws + bp.off_cv);
+        double* bd = (double*)(ws + bp.off_cd);
+        int* bi = (int*)(ws + bp.off_ci);
+        hipLaunchKernelGGL((assign_best_cols_kernel<T>), grid1, dim3(256), 0, st, (const T*)xa4, na, (const T*)xb4, nb, L, mm, h2,
+                           fac, p.rtiles, p.nb_pad, bv, bd, bi);
+        MVF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(assign_best_merge_kernel, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, st, bv, bd, bi, p.rsplit, nb,
+                           p.nb_pad, (int)na, col_idx, col_val);
+        MVF_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
 }  // namespace
 }  // namespace mvf
 
@@ -1229,4 +1469,41 @@ extern "C" int mvf_assign_layer_stats(const mvf_assign_layer* layer, int64_t na,
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MVF_F32) return run_layer_stats<float>(st, t, ly, na, nb, cmin, rows, vals, sums, (char*)workspace);
     return run_layer_stats<double>(st, t, ly, na, nb, cmin, rows, vals, sums, (char*)workspace);
+}
+
+extern "C" size_t mvf_assign_best_workspace_bytes(int64_t na, int64_t nb) {
+    if (na <= 0 || nb <= 0) return 0;
+    return make_best_plan(make_plan(na, nb)).total;
+}
+
+extern "C" int mvf_assign_best(const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers,
+                               int nlayers, const double* model_mul, double sigma2, double sigma2_variance,
+                               double spatial_outlier, int32_t* row_idx, double* row_val, int32_t* col_idx, double* col_val,
+                               void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream) {
+    const char* who = "mvf_assign_best";
+    MVF_REQUIRE((row_idx != nullptr) == (row_val != nullptr), "%s: row_idx and row_val must both be given or both be NULL", who);
+    MVF_REQUIRE((col_idx != nullptr) == (col_val != nullptr), "%s: col_idx and col_val must both be given or both be NULL", who);
+    MVF_REQUIRE(row_idx || col_idx, "%s: nothing to compute: the row pair and the column pair are both NULL", who);
+    if (na == 0 || nb == 0) return 0;
+    MVF_REQUIRE(na > 0 && nb > 0, "%s: negative size", who);
+    MVF_REQUIRE(na < ((int64_t)1 << 31) && nb < ((int64_t)1 << 31), "%s: too many cells", who);
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "%s: bad dtype %d", who, (int)dtype);
+    MVF_REQUIRE(nlayers >= 1 && nlayers <= MAX_LAYERS, "%s: need 1 .. %d layers, got %d", who, MAX_LAYERS, nlayers);
+    MVF_REQUIRE(xa4 && xb4 && layers && model_mul && workspace, "%s: null pointer", who);
+    MVF_REQUIRE(sigma2 > 0.0 && sigma2_variance > 0.0 && spatial_outlier >= 0.0, "%s: need sigma2 > 0, sigma2_variance > 0, outlier >= 0", who);
+    const Plan p = make_plan(na, nb);
+    const BestPlan bp = make_best_plan(p);
+    MVF_REQUIRE(workspace_bytes >= bp.total, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, bp.total);
+    DevLayers L;
+    L.n = nlayers;
+    for (int l = 0; l < nlayers; ++l)
+        if (const int rc = check_layer(who, l, layers[l], true, L.l[l])) return rc;
+    for (int l = nlayers; l < MAX_LAYERS; ++l) L.l[l] = L.l[0];
+    const double h1 = -1.0 / (2.0 * (sigma2 / sigma2_variance)), h2 = -1.0 / (2.0 * sigma2);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MVF_F32)
+        return run_assign_best<float>(st, p, bp, xa4, na, xb4, nb, L, model_mul, h1, h2, spatial_outlier, row_idx, row_val, col_idx,
+                                      col_val, (char*)workspace);
+    return run_assign_best<double>(st, p, bp, xa4, na, xb4, nb, L, model_mul, h1, h2, spatial_outlier, row_idx, row_val, col_idx,
+                                   col_val, (char*)workspace);
 }

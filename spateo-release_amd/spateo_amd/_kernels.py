@@ -727,6 +727,32 @@ class HipKernels:
         return out
 
     @_on_device
+    def assign_best(self, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, spatial_outlier, rows=True, cols=True):
+        """The best partner per cell from the fused assignment (mvf_assign_best): arguments as assign takes them.  Returns
+        device tensors {rows (na, 2) int32 = per A cell the B index under the "nearest" rule (value descending, distance
+        ascending, index ascending) and under the "first" rule (value descending, index ascending), row_values (na,) float64
+        = max_j P_ij, cols (nb, 2) int32 / col_values (nb,) float64: the same per B cell over the A cells}.  ``rows=False``
+        / ``cols=False`` skips that direction (its two entries are absent); one of them must stay."""
+        na, nb = xa4.shape[0], xb4.shape[0]
+        f64 = torch.float64
+        arr = (_lib.AssignLayer * len(layers))()
+        for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, layers):
+            s.Xp, s.Yp, s.a, s.b, s.ld = _ptr(Xp), _ptr(Yp), _ptr(a), _ptr(b), int(ld)
+            s.metric, s.prob, s.param = int(metric), int(prob), float(param)
+        out = {}
+        if rows:
+            out["rows"], out["row_values"] = self.empty(na, 2, dtype=torch.int32), self.empty(na, dtype=f64)
+        if cols:
+            out["cols"], out["col_values"] = self.empty(nb, 2, dtype=torch.int32), self.empty(nb, dtype=f64)
+        need = int(self.lib.mvf_assign_best_workspace_bytes(na, nb))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.mvf_assign_best(_ptr(xa4), na, _ptr(xb4), nb, arr, len(layers), _ptr(model_mul), float(sigma2),
+                                            float(sigma2_variance), float(spatial_outlier), _ptr(out.get("rows")),
+                                            _ptr(out.get("row_values")), _ptr(out.get("cols")), _ptr(out.get("col_values")),
+                                            _ptr(ws), need, self.cdtype, self._stream()), "mvf_assign_best")
+        return out
+
+    @_on_device
     def assign_layer_stats(self, layer, na, nb, k=0):
         """Column statistics of one layer's (na, nb) distance matrix (mvf_assign_layer_stats).  layer: one tuple as assign
         takes them (prob and param are not read).  Returns device tensors {cmin (nb,) float64, sums (2,) float64 = sum d,

@@ -120,6 +120,8 @@ SIGNATURES = {
     "mvf_assign_topk_workspace_bytes": (_sz, [_i64, _i64, _i]),
     "mvf_assign_topk": (_i, [_p, _i64, _p, _i64, C.POINTER(AssignLayer), _i, _p, _d, _d, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                              _sz, _i, _p]),
+    "mvf_assign_best_workspace_bytes": (_sz, [_i64, _i64]),
+    "mvf_assign_best": (_i, [_p, _i64, _p, _i64, C.POINTER(AssignLayer), _i, _p, _d, _d, _d, _p, _p, _p, _p, _p, _sz, _i, _p]),
     "mvf_assign_layer_stats_workspace_bytes": (_sz, [_i64, _i64, _i]),
     "mvf_assign_layer_stats": (_i, [C.POINTER(AssignLayer), _i64, _i64, _i, _p, _p, _p, _p, _p, _sz, _i, _p]),
     "mvf_align_alpha": (_i, [_p, _p, _p, _i64, _d, _d, _p, _p, _p]),

@@ -262,7 +262,10 @@ class Morpho_pairwise:
     The reference draws from ``np.random``; that stream cannot be reproduced here.  Keyword-only and beyond the reference's
     signature, the pinning arguments of the stages: ``seed`` (our own draws), ``inducing_idx`` (rows of the unique
     ``coordsA``), ``subsample_A`` / ``subsample_B`` (the rows of the subsampled stages, the coarse alignment's included) and
-    ``batch_perm`` (the initial SVI permutation).
+    ``batch_perm`` (the initial SVI permutation).  Also keyword-only: ``optimal_mapping=True`` has the loop follow its last
+    assignment with ``mvf_assign_best`` (in SVI mode the closing full assignment runs as with ``return_mapping=True``); after
+    ``run()`` the method ``optimal_mapping(keep_all=False)`` returns the reference's ``mapping_aligned_coords(XAHat, coordsB, P,
+    keep_all)`` - ``(by_A, by_B)``, see ``align.optimal_mapping`` - for slices of any size, with or without a ``P``.
 
     Accepted with no effect: ``use_chunk``, ``chunk_capacity`` and ``pre_compute_dist`` (memory layouts of the reference; the
     fused assignment writes no NA x NB matrix at all), ``save_concrete_iter``, ``graph_knn``, and ``verbose`` beyond logging.
@@ -282,7 +285,7 @@ class Morpho_pairwise:
                  kappa=1.0, partial_robust_level=10, normalize_c=True, normalize_g=False, separate_mean=True,
                  separate_scale=False, dtype="float32", device="cpu", verbose=True, guidance_pair=None, guidance_effect=False,
                  guidance_weight=1.0, use_chunk=False, chunk_capacity=1.0, return_mapping=False, update_R=True, *, seed=0,
-                 inducing_idx=None, subsample_A=None, subsample_B=None, batch_perm=None):
+                 inducing_idx=None, subsample_A=None, subsample_B=None, batch_perm=None, optimal_mapping=False):
         self.verbose = verbose
         self.sampleA, self.sampleB = sampleA, sampleB
         self.rep_layer, self.rep_field, self.genes = rep_layer, rep_field, genes
@@ -303,6 +306,7 @@ class Morpho_pairwise:
         self.guidance_pair, self.guidance_effect, self.guidance_weight = guidance_pair, guidance_effect, guidance_weight
         self.use_chunk, self.chunk_capacity, self.return_mapping, self.update_R = use_chunk, chunk_capacity, return_mapping, update_R
         self.seed, self.inducing_idx, self.subsample_A, self.subsample_B, self.batch_perm = seed, inducing_idx, subsample_A, subsample_B, batch_perm
+        self._optimal_mapping, self.best = bool(optimal_mapping), None   # (the name optimal_mapping is the method's)
         if dtype not in ("float32", "float64"):
             raise ValueError("dtype must be 'float32' or 'float64'")
         self._check()
@@ -437,7 +441,7 @@ class Morpho_pairwise:
     def _P_fits(self):
         """Whether the dense P of the last assignment is within align.RETURN_P_MAX_ENTRIES."""
         columns = self.NB
-        if self.SVI_mode and not self.return_mapping:
+        if self.SVI_mode and not (self.return_mapping or self._optimal_mapping):
             columns = _al._svi_batch_size(self.NB, self.batch_size)
         return self.NA * columns <= _al.RETURN_P_MAX_ENTRIES
 
@@ -468,7 +472,7 @@ class Morpho_pairwise:
                     partial_robust_level=self.partial_robust_level, sigma2_end=self.sigma2_end, nn_init_weight=self.nn_init_weight,
                     update_R=self.update_R, record="arrays" if self.iter_key_added is not None else False,
                     sparse_calculation_mode=bool(self.sparse_calculation_mode), sparse_top_k=self.sparse_top_k, return_P=dense_P,
-                    **common, **start)
+                    optimal_mapping=self._optimal_mapping, **common, **start)
         if self.SVI_mode:
             out = _al.morpho_iterate_svi(start.coordsA, self.coordsB, self.exp_layers_A, self.exp_layers_B, batch_size=self.batch_size,
                                          batch_perm=self.batch_perm, seed=self.seed, return_mapping=bool(self.return_mapping), **loop)
@@ -480,6 +484,17 @@ class Morpho_pairwise:
             lm.main_info(f"Key Parameters: gamma: {self.gamma}; sigma2: {self.sigma2}; probability_parameters: "
                          f"{self.probability_parameters}")
         return self.P
+
+    def optimal_mapping(self, keep_all=False):
+        """``(by_A, by_B)`` of ``align.mapping_from_best`` for the last assignment of ``run()``: ``X`` the de-normalised
+        ``XAHat``, ``Y`` sample B's coordinates as ``check_spatial_coords`` left them.  Needs the constructor's
+        ``optimal_mapping=True`` and a finished ``run()``."""
+        if not self._optimal_mapping:
+            raise ValueError("Morpho_pairwise.optimal_mapping(): construct the model with optimal_mapping=True, so that run() "
+                             "keeps the best partners of its last assignment")
+        if self.best is None:
+            raise ValueError("Morpho_pairwise.optimal_mapping(): call run() first")
+        return _al.mapping_from_best(self.best, self.XAHat, self.raw_coordsB, keep_all)
 
     # ---- _wrap_output (:1471-1528) and _save_iter (:1043-1065) ----
     def _wrap_output(self, start, out):
@@ -498,6 +513,7 @@ class Morpho_pairwise:
         self.RnA = self._denormalize(out["RnA"])
         self.optimal_RnA = self._denormalize(out["optimal_RnA"])
         self.P = out.get("P")
+        self.best = out.get("best")
         self.iter_added = None
         if self.iter_key_added is not None:
             hist = out["history"]

@@ -21,7 +21,7 @@ from .engine import SparseVFCEngine, _consistent_K
 from .vectorfield import vector_field_function
 
 __all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate", "morpho_iterate_svi",
-           "label_transfer_matrix", "init_sigma2", "init_probability_parameters", "coarse_rigid_alignment", "morpho_start",
+           "optimal_mapping", "mapping_from_best", "label_transfer_matrix", "init_sigma2", "init_probability_parameters", "coarse_rigid_alignment", "morpho_start",
            "Morpho_pairwise", "morpho_align"]
 
 RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
@@ -274,6 +274,100 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
         out["topk_rows"], out["topk_values"] = np.array(host["rows"], dtype=np.int32), np.array(host["vals"], dtype=np.float64)
         out["P"] = _coo_from_lists(out["topk_rows"], out["topk_values"], NA)
     return out
+
+
+BEST_KEYS = ("rows", "row_values", "cols", "col_values")
+
+
+def _best_to_host(k, dev):
+    """HipKernels.assign_best's dict of device tensors as host arrays: rows / cols int32 (n, 2), the values float64."""
+    host = dict(zip(BEST_KEYS, _rt._to_host(k, [dev[q] for q in BEST_KEYS])))
+    return {q: np.array(host[q], dtype=np.float64 if q.endswith("values") else np.int32) for q in BEST_KEYS}
+
+
+def _empty_mapping(D):
+    return {"mapping_X": np.zeros((0, D)), "mapping_Y": np.zeros((0, D)), "pi_index": np.zeros((0, 2), dtype=np.int32),
+            "pi_value": np.zeros(0)}
+
+
+def mapping_from_best(best, X, Y, keep_all=False):
+    """The two dicts of the reference's ``mapping_aligned_coords(X, Y, P, keep_all)`` (``spateo/alignment/utils.py:196-255``)
+    from the best partners ``mvf_assign_best`` found, without ``P``.
+
+    ``best``: ``rows`` (NA, 2) / ``cols`` (NB, 2) integer - per cell its partner under the "nearest" rule (column 0: among
+    equal maxima the nearest coordinate, ``keep_all=False``) and under the "first" rule (column 1: the smallest index,
+    ``keep_all=True``) - and ``row_values`` (NA,) / ``col_values`` (NB,), the maxima: the ``best`` of ``morpho_iterate(...,
+    optimal_mapping=True)``, or ``HipKernels.assign_best``'s result brought to the host.  ``X`` (NA, D) and ``Y`` (NB, D): the
+    coordinates the dicts quote (``XAHat`` and ``coordsB``).
+
+    Returns ``(by_A, by_B)``, each ``{"mapping_X", "mapping_Y", "pi_index" (n, 2) int32 = (index_x, index_y), "pi_value" (n,)
+    float64}``: ``by_A`` has one entry per A cell in index order, ``by_B`` one per B cell.  An empty side gives empty dicts."""
+    X, Y = np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+    if X.ndim != 2 or Y.ndim != 2 or X.shape[1] != Y.shape[1]:
+        raise ValueError("mapping_from_best: X (NA, D) and Y (NB, D) must be 2-D with the same D")
+    missing = [q for q in BEST_KEYS if not isinstance(best, dict) or q not in best]
+    if missing:
+        raise ValueError(f"mapping_from_best: best must be a dict with {', '.join(BEST_KEYS)}; missing: {', '.join(missing)}")
+    NA, NB = len(X), len(Y)
+    if NA == 0 or NB == 0:
+        return _empty_mapping(X.shape[1]), _empty_mapping(X.shape[1])
+    col = 1 if keep_all else 0
+    out = []
+    for idx, val, n, limit, own in ((best["rows"], best["row_values"], NA, NB, 0), (best["cols"], best["col_values"], NB, NA, 1)):
+        idx, val = np.asarray(idx), np.asarray(val, dtype=np.float64).reshape(-1)
+        if idx.shape != (n, 2) or idx.dtype.kind not in "iu" or val.shape != (n,):
+            raise ValueError(f"mapping_from_best: the {'rows' if own == 0 else 'cols'} side must be an integer (n, 2) array with "
+                             f"(n,) values, n = {n}; got {idx.shape} {idx.dtype} and {val.shape}")
+        partner = idx[:, col].astype(np.int64)
+        if partner.min() < 0 or partner.max() >= limit:
+            raise ValueError(f"mapping_from_best: a partner index lies outside [0, {limit})")
+        pair = np.empty((n, 2), dtype=np.int32)
+        pair[:, own], pair[:, 1 - own] = np.arange(n), partner
+        out.append({"mapping_X": X[pair[:, 0]], "mapping_Y": Y[pair[:, 1]], "pi_index": pair, "pi_value": val.copy()})
+    return out[0], out[1]
+
+
+def optimal_mapping(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity, probability_type, probability_parameters,
+                    sigma2, alpha, SigmaDiag, gamma, samples_s, sigma2_variance=1.0, dtype: str = "float64", device=None,
+                    label_transfer=None, keep_all=False):
+    """The cell mapping after an alignment - ``mapping_aligned_coords(XAHat, coordsB, P, keep_all)`` of the reference
+    (``spateo/alignment/utils.py:196-255``, on ``get_optimal_mapping_relationship``, ``:157-193``) for the ``P`` that
+    ``update_assignment`` would form from the same arguments - without ``P``: ``mvf_assign_best`` reduces the tiles of the fused
+    assignment to the largest entry of every row and of every column, so two slices of 100 000 cells (a dense ``P`` of 80 GB)
+    get their mapping in about the time of an assignment step and a half.
+
+    Arguments as ``update_assignment`` takes them (``"label"`` layers with ``label_transfer`` included), without ``return_P``
+    and the sparse pair; errors are ``update_assignment``'s.  ``keep_all=False``: among equal maxima the partner with the
+    nearest coordinate - so a cell whose row (column) of ``P`` is all zero, every far or outlying cell, maps to its nearest
+    neighbour, as in the reference; ``keep_all=True``: the smallest index among equal maxima.
+
+    Returns ``(by_A, by_B)``: ``by_A`` maps every A cell to its best B cell (the maximum of its row of ``P``), ``by_B`` every B
+    cell to its best A cell (of its column); each ``{"mapping_X": XAHat[index_x], "mapping_Y": coordsB[index_y], "pi_index"
+    (n, 2) int32 = (index_x, index_y), "pi_value" (n,) float64}``.  ``st.tdr.cell_directions(adataA, adataB, mapping=by_A)``
+    turns ``by_A`` into ``V_mapping``.  Two calls give equal bits.
+
+    Where this differs from ``get_optimal_mapping_relationship`` / ``mapping_aligned_coords``: the entries are sorted by cell
+    index and there is ONE per cell also for ``keep_all=True``.  The reference appends the cells with tied maxima at the end
+    of its index arrays and, with ``keep_all=True``, returns every tied pair; its ``mapping_aligned_coords`` then sorts and
+    drops the duplicates, which is what is returned here."""
+    if dtype not in ("float32", "float64"):
+        raise ValueError("dtype must be 'float32' or 'float64'")
+    XA, XB, LA, LB, codes, table = _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
+                                                         probability_type, probability_parameters, False, label_transfer,
+                                                         who="optimal_mapping")
+    NA, D = XA.shape
+    al, sd = np.asarray(alpha, dtype=np.float64).reshape(-1), np.asarray(SigmaDiag, dtype=np.float64).reshape(-1)
+    if len(al) != NA or len(sd) != NA:
+        raise ValueError("alpha and SigmaDiag must be (NA,)")
+    sigma2, gamma, samples_s, sigma2_variance = float(sigma2), float(gamma), float(samples_s), float(sigma2_variance)
+    if NA == 0 or len(XB) == 0:
+        return _empty_mapping(D), _empty_mapping(D)
+    model_mul = al * np.exp(-sd / sigma2)                                                   # morpho_class.py:1087
+    outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
+    k = _rt._make_kernels(device, dtype)
+    layers = _prepare_layers(k, LA, LB, codes, table)
+    dev = k.assign_best(k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, float(outlier))
+    return mapping_from_best(_best_to_host(k, dev), XA, XB, keep_all)
 
 
 def _nonrigid_solve(k, G, Gamma, reg, R):
@@ -590,7 +684,8 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
                    inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter=0, kappa=1.0, gamma_a=1.0,
                    gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                    update_R=True, dtype: str = "float64", device=None, record=True, origin=None, SVI_mode=False, guidance=None,
-                   sparse_calculation_mode=False, kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False):
+                   sparse_calculation_mode=False, kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False,
+                   optimal_mapping=False):
     """The iteration loop of Spateo's pairwise alignment on the MI355X: the non-SVI, dense-path body of
     ``Morpho_pairwise.run`` (``spateo/alignment/methods/morpho_class.py:280-294``: assignment -> gamma -> alpha -> non-rigid
     -> rigid -> ``XAHat`` -> sigma2) for ``max_iter`` iterations from the state ``_initialize_variational_variables`` sets
@@ -629,6 +724,12 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     ``RETURN_P_MAX_ENTRIES`` entries): the last iteration's assignment runs through ``mvf_assign_dense`` and the result gains
     its ``P`` (NA, NB), the reference's ``self.P`` after ``run()``.  Every other output keeps its bits.
 
+    ``optimal_mapping=True`` (dense and sparse mode, any size): the last iteration's assignment is followed by
+    ``mvf_assign_best`` on the same device operands and state, and the result gains ``best`` - host ``rows`` (NA, 2) / ``cols``
+    (NB, 2) int32 and ``row_values`` / ``col_values`` float64, the best partner of every cell in the last assignment's DENSE
+    ``P`` under both tie rules; ``mapping_from_best(best, XAHat, coordsB, keep_all)`` makes the reference's two mapping dicts
+    of it.  Every other output keeps its bits.
+
     Not supported (``NotImplementedError``): ``SVI_mode`` (``morpho_iterate_svi`` runs it), ``guidance``,
     ``sparse_calculation_mode`` with ``sparse_top_k`` above 64 (the default, 1024, is the reference constructor's,
     ``morpho_class.py:140``), ``kernel_type="geodist"`` (anything but ``"euc"``), and what
@@ -644,7 +745,8 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
                            record, SVI_mode, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer)
     return_P = _return_P_argument(return_P, a["top_k"], len(a["XA"]), len(a["XB"]))
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
-                    partial_robust_level, nn_init_weight, update_R, dtype, device, record, return_P=return_P)
+                    partial_robust_level, nn_init_weight, update_R, dtype, device, record, return_P=return_P,
+                    best=bool(optimal_mapping))
 
 
 def _return_P_argument(return_P, top_k, NA, NB_last):
@@ -662,10 +764,11 @@ def _return_P_argument(return_P, top_k, NA, NB_last):
 
 
 def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b, partial_robust_level,
-             nn_init_weight, update_R, dtype, device, record, svi=None, return_P=False):
+             nn_init_weight, update_R, dtype, device, record, svi=None, return_P=False, best=False):
     """The loop of morpho_iterate and, with ``svi = dict(batch_size=, batch_perm= (int32, validated), return_mapping=)``, of
     morpho_iterate_svi, on validated arguments ``a`` (_iterate_arguments).  ``return_P``: the LAST assignment executed - the
-    last iteration's, or the closing full one - runs through mvf_assign_dense."""
+    last iteration's, or the closing full one - runs through mvf_assign_dense.  ``best``: the same assignment is followed by
+    mvf_assign_best on its operands, before the iteration moves them on."""
     XA, XB, ctrl, org, top_k = a["XA"], a["XB"], a["ctrl"], a["origin"], a["top_k"]
     NA, D = XA.shape
     NB, m = len(XB), len(ctrl)
@@ -731,6 +834,9 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
             dev = _assign_device(k, xa4, xb4_b, layers_b, model_mul, sigma2, sigma2_variance, outlier, dense=dense, top_k=top_k)
         else:
             dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, dense=dense, top_k=top_k)
+        if best and not closing and it == int(max_iter) - 1:   # the last assignment executed: its operands as they are now
+            best_dev = k.assign_best(xa4, xb4 if svi is None else xb4_b, layers if svi is None else layers_b, model_mul, sigma2,
+                                     sigma2_variance, float(outlier))
         ph.mark("assign")
         if (it > nonrigid_start_iter or nonrigid) and svi is not None:
             nonrigid = True
@@ -806,8 +912,10 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
         if a["sigma2_end"] is not None:                        # model_mul of :1087 with the replaced sigma2: once, on the host
             al, sd = k.to_host([alpha, SigmaDiag], own_pinned=False)
             model_mul = k.h2d(np.array(al, dtype=np.float64) * np.exp(-np.array(sd, dtype=np.float64) / sigma2))
-        dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance,
-                             _spatial_outlier(sigma2, gamma, samples_s, NA, D), dense=bool(return_P), top_k=top_k)
+        outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
+        dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, dense=bool(return_P), top_k=top_k)
+        if best:
+            best_dev = k.assign_best(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier))
         k.align_moments(A64, V4, dev["K_NA"], dev["K_NA_spatial"], dev["K_NA_sigma2"], SigmaDiag, dev["PXB"], B64, dev["K_NB"],
                         block, origin=org, extra=dev["scalars"])
         blk = np.array(k.to_host([block])[0], dtype=np.float64)
@@ -833,6 +941,8 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
         out["P"] = _coo_from_lists(rows, vals, NA)
     if return_P:
         out["P"] = np.array(k.to_host([dev["P"]], own_pinned=False)[0], dtype=np.float64)
+    if best:
+        out["best"] = _best_to_host(k, best_dev)
     if record:
         out["history"] = {q: np.array(v) for q, v in history.items()}
     ph.mark("result")
@@ -887,7 +997,7 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
                        gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                        update_R=True, dtype: str = "float64", device=None, record=True, origin=None, batch_size=None,
                        batch_perm=None, seed=None, return_mapping=False, guidance=None, sparse_calculation_mode=False,
-                       kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False):
+                       kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False, optimal_mapping=False):
     """The SVI mode of the same loop - the reference constructor's default, ``SVI_mode=True``
     (``spateo/alignment/methods/morpho_class.py:136, 283-284, 749-760, 894-896``): every iteration sees ``batch_size`` cells
     of the B slice and blends what it learns into running averages with ``step_size = min(1, 10 / (iter + 1))``.
@@ -920,6 +1030,10 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
     ``mvf_assign_dense`` and its ``P`` is returned - the last batch's, (NA, ``batch_size``) with the columns in the batch's
     order, or with ``return_mapping=True`` the closing full one's, (NA, NB).  Every other output keeps its bits.
 
+    ``optimal_mapping=True``: a mapping needs every B cell, so the closing full assignment runs exactly as with
+    ``return_mapping=True`` and is followed by ``mvf_assign_best``; the result gains ``best`` as in ``morpho_iterate`` (``cols``
+    has NB rows).  Every other output has the bits of the same call with ``return_mapping=True``.
+
     Not supported (``NotImplementedError``): what ``morpho_iterate`` refuses but ``SVI_mode``.
 
     Returns ``morpho_iterate``'s dict - ``K_NA``, ``K_NB`` (``batch_size``,), ``K_NA_spatial``, ``K_NA_sigma2`` of the last
@@ -930,10 +1044,12 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
                            record, False, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer)
     bs, perm = _svi_arguments(len(a["XB"]), batch_size, batch_perm, seed)
+    return_mapping = bool(return_mapping) or bool(optimal_mapping)
     return_P = _return_P_argument(return_P, a["top_k"], len(a["XA"]), len(a["XB"]) if return_mapping else bs)
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
                     partial_robust_level, nn_init_weight, update_R, dtype, device, record,
-                    svi=dict(batch_size=bs, batch_perm=perm, return_mapping=bool(return_mapping)), return_P=return_P)
+                    svi=dict(batch_size=bs, batch_perm=perm, return_mapping=bool(return_mapping)), return_P=return_P,
+                    best=bool(optimal_mapping))
 
 
 # ---- the start state: what the reference computes in front of the loop (morpho_class.py:700-747, 771-820, 845-852, 898-1041) ----

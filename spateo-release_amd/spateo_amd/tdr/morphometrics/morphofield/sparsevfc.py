@@ -45,6 +45,7 @@ def cell_directions(
     keep_all: bool = False,
     inplace: bool = True,
     pi: Optional[np.ndarray] = None,
+    mapping=None,
     **kwargs,
 ):
     """Developmental direction of every cell of sample A towards its optimally mapped cell of sample B
@@ -56,7 +57,35 @@ def cell_directions(
     ``paste_pairwise_align`` (PASTE's fused Gromov-Wasserstein optimal transport, POT's solvers): that solve is
     outside this package ("the rest of the alignment module") - pass the coupling obtained from
     ``st.align.paste_pairwise_align`` (or any other aligner) as ``pi=``; the OT arguments are accepted for signature
-    compatibility and ignored."""
+    compatibility and ignored.
+
+    ``mapping`` (instead of ``pi``; both together: ``ValueError``): the mapping of the A cells as
+    ``st.align.optimal_mapping`` / ``Morpho_pairwise.optimal_mapping`` return it - the ``by_A`` dict or the
+    ``(by_A, by_B)`` tuple -, which needs no dense coupling.  The partners are ``pi_index[:, 1]``; ``pi_index[:, 0]`` must be
+    ``arange(n_A)`` and the partners lie in ``[0, n_B)``, otherwise ``ValueError``.  ``keep_all`` is not read then (the
+    mapping was made with its own).  Returns ``(None if inplace else adataA, mapping)`` as given."""
+    if mapping is not None:
+        if pi is not None:
+            raise ValueError("cell_directions: pass the coupling pi= or the mapping=, not both")
+        by_A = mapping[0] if isinstance(mapping, (tuple, list)) else mapping
+        if not isinstance(by_A, dict) or "pi_index" not in by_A:
+            raise ValueError("cell_directions: mapping must be the by_A dict of st.align.optimal_mapping (with 'pi_index') or "
+                             "the (by_A, by_B) tuple")
+        XA = np.asarray(adataA.obsm[spatial_key])
+        XB = np.asarray(adataB.obsm[spatial_key])
+        index = np.asarray(by_A["pi_index"])
+        if index.ndim != 2 or index.shape != (len(XA), 2) or index.dtype.kind not in "iu":
+            raise ValueError(f"cell_directions: mapping['pi_index'] must be an integer array (n_A, 2) = {(len(XA), 2)}, got "
+                             f"{index.shape} {index.dtype}")
+        if not np.array_equal(index[:, 0], np.arange(len(XA))):
+            raise ValueError("cell_directions: mapping['pi_index'][:, 0] must be arange(n_A): one partner per A cell, in order")
+        partner = index[:, 1].astype(np.int64)
+        if len(partner) and (partner.min() < 0 or partner.max() >= len(XB)):
+            raise ValueError(f"cell_directions: the partners mapping['pi_index'][:, 1] must lie in [0, n_B) = [0, {len(XB)})")
+        out = adataA if inplace else adataA.copy()
+        out.obsm[f"X_{key_added}"] = XB[partner]
+        out.obsm[f"V_{key_added}"] = out.obsm[f"X_{key_added}"] - XA
+        return None if inplace else out, mapping
     if pi is None:
         raise NotImplementedError(
             "cell_directions: the PASTE optimal-transport solve (paste_pairwise_align) is outside spateo_amd - compute "
