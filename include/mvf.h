@@ -665,6 +665,44 @@ int mvf_align_alpha_svi(const double* kappa, const double* K_NA_spatial, const d
 int mvf_align_transform_svi(const double* RnA, const double* PXB, const double* K_NA, int64_t na, const double* origin,
                             double step, double* PXB_term, void* Y4, void* Pw, mvf_dtype dtype, void* stream);
 
+/* ---- PCA across slices: the cache of mvf_ublk_build filled from data (mvf_pca.hip) ----------------------------------------
+ * Five additions to the table (mvf_version stays 7 by the rule above).  A PCA of the stacked n_total x g matrix X of several
+ * slices is  means -> cache of Xc = X - mean -> G = Xc^T Xc -> eigenvectors V -> scores Xc V;  the entry points here do the
+ * first two, the rest runs UNCHANGED on the cache: mvf_gram_cached(MVF_GRAM_STAGE_TILES | MVF_GRAM_STAGE_REDUCE) with m = g and
+ * P = 1 (x4 / ctrl4: any non-NULL pointer, neither stage reads them; y4, R: NULL), mvf_apply_cached with C = V (Yd: zeros).
+ * A slice is n rows of the stacked matrix starting at global row `row0`; the slices are handed in by rising row0, from 0, on
+ * one stream, and the call with row0 + n == n_total finishes the job (n_total = n, row0 = 0: one matrix, one call).  Input
+ * matrices are row-major n x g, float32 (x_is_f32 / data_is_f32 != 0) or float64.  Arguments are validated before any HIP call.
+ *
+ * Replaces: `group_pca` (spateo/alignment/utils.py:88-149: `ad.concat` of the slices + `sc.tl.pca`), each of them. */
+/* mvf_colmeans: mean[j] = (sum_i X[i][j]) / n_total, g float64, written by the call that ends at n_total.  The sum runs over
+ * fixed blocks of 1024 global rows, the rows of a block in row order, then the blocks in order - float64, no atomics: the
+ * result depends on the stacked matrix only (not on where it is cut into slices), and two calls give the same bits.
+ * workspace: mvf_colmeans_workspace_bytes(n_total, g), 8-byte aligned, the same buffer for every slice of a matrix.
+ * Replaces: the centring inside `sc.tl.pca(..., zero_center=True)` of alignment/utils.py:88-149. */
+size_t mvf_colmeans_workspace_bytes(int64_t n_total, int64_t g);
+int mvf_colmeans(const void* x, int x_is_f32, int64_t n, int64_t g, int64_t n_total, int64_t row0, double* mean,
+                 void* workspace, size_t workspace_bytes, void* stream);
+/* mvf_ublk_pack: (dtype)((double)X[i][j] - mu[j]) into the cache of mvf_ublk_build - same layout Ublk[g/16][n_total][16], same
+ * size mvf_ublk_bytes(n_total, g, dtype) - at rows row0 .. row0 + n; mu (g float64, device) NULL = no centring.  The columns
+ * g .. roundup(g, 128) of those rows are written as zeros, and the call that ends at n_total zeroes the rows n_total ..
+ * roundup(n_total, 256): after the last slice every element of the cache has been written once.  ublk: 16-byte aligned.
+ * Replaces: the operand of the SVD inside `sc.tl.pca` of alignment/utils.py:88-149 (the centred, concatenated matrix). */
+int mvf_ublk_pack(const void* x, int x_is_f32, int64_t n, int64_t g, const double* mu, int64_t n_total, int64_t row0,
+                  void* ublk, size_t ublk_bytes, mvf_dtype dtype, void* stream);
+/* The same two from CSR: indptr (n + 1 int64), indices (int32), data (float32 / float64), all on the device.  The contract is
+ * mvf_assign_prepare_csr's: distinct column indices within a row; an entry whose column is outside [0, g) is skipped, never
+ * used as an address; indptr is the caller's to validate.  Chunks of rows are expanded into `staging` (>= one row = g elements
+ * of the data's type, 8-byte aligned; as many rows per chunk as it holds) and go through the dense kernels: bit for bit what
+ * the dense entry points give for the densified matrix, whatever the staging size.  No n x g copy of the input is made.
+ * Replaces: `.X` of the concatenated slices as `sc.tl.pca` reads it when it is sparse (alignment/utils.py:88-149). */
+int mvf_colmeans_csr(const int64_t* indptr, const int32_t* indices, const void* data, int data_is_f32, int64_t n, int64_t g,
+                     int64_t n_total, int64_t row0, double* mean, void* workspace, size_t workspace_bytes, void* staging,
+                     size_t staging_bytes, void* stream);
+int mvf_ublk_pack_csr(const int64_t* indptr, const int32_t* indices, const void* data, int data_is_f32, int64_t n, int64_t g,
+                      const double* mu, int64_t n_total, int64_t row0, void* ublk, size_t ublk_bytes, void* staging,
+                      size_t staging_bytes, mvf_dtype dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,34 @@ def csr_arrays(layer):
             np.ascontiguousarray(data), int(n), int(g))
 
 
+def pca_slices(mats):
+    """The per-slice matrices of `align.pca` as the kernels' pca_* methods take them, validated on the host: a dense slice
+    -> ("dense", C-contiguous (n, g) float32 | float64 array; other dtypes become float64), a scipy.sparse slice -> ("csr",
+    indptr, indices, data, n, g) from `csr_arrays`.  Equal column counts and finite values, or ValueError - checked chunk by
+    chunk, without a boolean copy of a whole slice."""
+    out, g = [], None
+    for i, m in enumerate(mats):
+        if is_sparse(m):
+            sl = ("csr",) + csr_arrays(m)
+            shape, values = (sl[4], sl[5]), sl[3][None, :]
+        else:
+            a = np.asarray(m)
+            if a.ndim != 2:
+                raise ValueError(f"slice {i}: expected an (n, g) matrix, got shape {a.shape}")
+            a = np.ascontiguousarray(a, dtype=a.dtype if a.dtype in (np.float32, np.float64) else np.float64)
+            sl, shape, values = ("dense", a), a.shape, a
+        if g is None:
+            g = shape[1]
+        if shape[1] != g:
+            raise ValueError(f"slice {i} has {shape[1]} columns, slice 0 has {g}")
+        step = max(1, (1 << 22) // max(1, values.shape[1]))
+        for lo in range(0, values.shape[0], step):
+            if not np.isfinite(values[lo : lo + step]).all():
+                raise ValueError(f"slice {i} holds non-finite values")
+        out.append(sl)
+    return out, (0 if g is None else int(g))
+
+
 def _on_device(fn):
     """Run a kernel method with the instance's GPU as the thread's current HIP device: libmvf launches on the stream it
     is handed, but hipFuncSetAttribute / hipMemsetAsync / occupancy queries inside it act on the CURRENT device, which
@@ -849,6 +877,126 @@ class HipKernels:
         _lib.check(self.lib.mvf_align_transform_svi(_ptr(RnA), _ptr(PXB), _ptr(K_NA), RnA.shape[0], self._host3(origin, 3),
                                                     float(step), _ptr(PXB_term), _ptr(Y4), _ptr(Pw), self.cdtype, self._stream()),
                    "mvf_align_transform_svi")
+
+    # ---- PCA across slices on the kernel-value cache (mvf_pca.hip + the cached Gram / apply kernels, unchanged) ----
+    PCA_UPLOAD_BYTES = 256 << 20  # rows of a dense slice travel in chunks of at most this much (each chunk is a slice of its own)
+
+    def mem_free(self):
+        """Bytes of device memory free right now."""
+        return int(torch.cuda.mem_get_info(self.device)[0])
+
+    @_on_device
+    def pca_open(self, n_total, g):
+        """The cache (mvf_ublk_bytes(n_total, g) of the cell dtype) and the partial column sums of one PCA."""
+        self.pca_close()
+        self._pca_n, self._pca_g = int(n_total), int(g)
+        need = self.ublk_bytes(self._pca_n, self._pca_g)
+        self._ublk = torch.empty(need // self._ublk_itemsize(), dtype=self.tdtype, device=self.device)
+        self._ublk_key = None  # (no (x4, ctrl4, beta) builds this cache: `gram` must not mistake it for a fit's)
+        self._pca_mu = None
+        self._pca_dev = {}  # slice index -> the device copies of a CSR slice's three arrays (uploaded once, used by both passes)
+
+    def pca_close(self):
+        self.drop_ublk()
+        self._pca_mu = self._pca_dev = None
+
+    def _pca_chunks(self, sl):
+        """A dense slice as (first row, device rows) chunks of at most PCA_UPLOAD_BYTES."""
+        a = sl[1]
+        rows = max(1, self.PCA_UPLOAD_BYTES // max(1, a.shape[1] * a.itemsize))
+        for lo in range(0, a.shape[0], rows):
+            yield lo, self.h2d(a[lo : lo + rows])
+
+    def _pca_csr(self, i, sl):
+        """Device (indptr, indices, data) of CSR slice i and the staging area of expanded rows (bounded like assign_prepare's)."""
+        _, indptr, indices, data, n, g = sl
+        if i not in self._pca_dev:
+            if len(data) == 0:  # an all-zero slice: the arrays still need an address
+                indices, data = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=data.dtype)
+            self._pca_dev[i] = (self.h2d(indptr), self.h2d(indices), self.h2d(data))
+        rows = min(n, CSR_STAGING_MAX_ROWS, max(1, CSR_STAGING_MAX_BYTES // (data.itemsize * g)))
+        stage = self.empty(-(-rows * g * data.itemsize // 8), dtype=torch.float64)
+        return self._pca_dev[i], stage
+
+    @_on_device
+    def pca_means(self, slices):
+        """Column means of the stacked slices (mvf_colmeans / mvf_colmeans_csr): host float64 (g,); kept on the device for
+        pca_pack.  slices: what `pca_slices` made of the caller's matrices."""
+        n_total, g = self._pca_n, self._pca_g
+        need = int(self.lib.mvf_colmeans_workspace_bytes(n_total, g))
+        ws = self.empty(need // 8, dtype=torch.float64)
+        self._pca_mu = self.empty(g, dtype=torch.float64)
+        row0 = 0
+        for i, sl in enumerate(slices):
+            if sl[0] == "csr":
+                (d_indptr, d_indices, d_data), stage = self._pca_csr(i, sl)
+                _lib.check(self.lib.mvf_colmeans_csr(_ptr(d_indptr), _ptr(d_indices), _ptr(d_data), int(sl[3].dtype == np.float32),
+                                                     sl[4], g, n_total, row0, _ptr(self._pca_mu), _ptr(ws), need, _ptr(stage),
+                                                     stage.numel() * 8, self._stream()), "mvf_colmeans_csr")
+                row0 += sl[4]
+                continue
+            for lo, xd in self._pca_chunks(sl):
+                _lib.check(self.lib.mvf_colmeans(_ptr(xd), int(xd.dtype == torch.float32), xd.shape[0], g, n_total, row0 + lo,
+                                                 _ptr(self._pca_mu), _ptr(ws), need, self._stream()), "mvf_colmeans")
+            row0 += sl[1].shape[0]
+        return self.d2h(self._pca_mu)
+
+    @_on_device
+    def pca_pack(self, slices, centred):
+        """The slices, one behind the other, minus pca_means' means (centred) or as they are, into the cache."""
+        n_total, g = self._pca_n, self._pca_g
+        mu = self._pca_mu if centred else None
+        if centred and mu is None:
+            raise RuntimeError("pca_pack(centred=True) needs pca_means first")
+        nbytes = self._ublk.numel() * self._ublk_itemsize()
+        row0 = 0
+        for i, sl in enumerate(slices):
+            if sl[0] == "csr":
+                (d_indptr, d_indices, d_data), stage = self._pca_csr(i, sl)
+                _lib.check(self.lib.mvf_ublk_pack_csr(_ptr(d_indptr), _ptr(d_indices), _ptr(d_data), int(sl[3].dtype == np.float32),
+                                                      sl[4], g, _ptr(mu), n_total, row0, _ptr(self._ublk), nbytes, _ptr(stage),
+                                                      stage.numel() * 8, self.cdtype, self._stream()), "mvf_ublk_pack_csr")
+                row0 += sl[4]
+                continue
+            for lo, xd in self._pca_chunks(sl):
+                _lib.check(self.lib.mvf_ublk_pack(_ptr(xd), int(xd.dtype == torch.float32), xd.shape[0], g, _ptr(mu), n_total,
+                                                  row0 + lo, _ptr(self._ublk), nbytes, self.cdtype, self._stream()), "mvf_ublk_pack")
+            row0 += sl[1].shape[0]
+        self._pca_dev = {}
+
+    @_on_device
+    def pca_gram(self):
+        """G = Xc^T Xc (g x g float64, host) from the packed cache: mvf_gram_cached's tile and reduce stages with P = 1.
+        Neither stage reads x4 / ctrl4 (they must only be non-NULL: P stands in), y4 and R belong to stages not asked for."""
+        n, g = self._pca_n, self._pca_g
+        need = int(self.lib.mvf_gram_workspace_bytes(n, g, self.cdtype))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        P = torch.ones(n, dtype=self.tdtype, device=self.device)
+        G = self.empty(g, g, dtype=torch.float64)
+        _lib.check(self.lib.mvf_gram_cached(_lib.GRAM_TILES | _lib.GRAM_REDUCE, _ptr(self._ublk), _ptr(P), _ptr(P), None, n, _ptr(P),
+                                            g, 0.0, _ptr(G), None, _ptr(ws), ws.numel(), self.cdtype, self._stream()),
+                   "mvf_gram_cached")
+        return self.d2h(G)
+
+    @_on_device
+    def pca_scores(self, V):
+        """Xc V for host V (g, k <= 128 float64): mvf_apply_cached with C = V against Yd = 0; the scores come back in the
+        cell dtype, as the kernel stores them, widened to float64 on the host: (n_total, k)."""
+        n, g = self._pca_n, self._pca_g
+        V = np.asarray(V, dtype=np.float64)
+        k = V.shape[1]
+        n_pad, m_pad = self.wide_pads(n, g)
+        ld = -(-k // 16) * 16
+        Ch = np.zeros((m_pad, ld))
+        Ch[:g, :k] = V
+        Cd = self.h2d(Ch)
+        Yd = self.zeros(n_pad, ld)
+        Vd = self.empty(n, ld)
+        r = self.empty(n)
+        ws = self._wide_ws(n, g)
+        _lib.check(self.lib.mvf_apply_cached(_ptr(self._ublk), n, g, _ptr(Cd), ld, k, _ptr(Yd), ld, None, _ptr(Vd), _ptr(r), None,
+                                             _ptr(ws), ws.numel(), self.cdtype, self._stream()), "mvf_apply_cached")
+        return self.d2h(Vd[:, :k]).astype(np.float64)
 
     @staticmethod
     def _affine_buf(affine):

@@ -37,6 +37,10 @@ ASSIGN_PROBS = {"gauss": 0, "gaussian": 0, "cos": 1, "cosine": 1, "prob": 2}
 ASSIGN_MAX_LAYERS = 4
 ASSIGN_TOPK_MAX = 64  # MVF_ASSIGN_TOPK_MAX: the largest sparse_top_k mvf_assign_topk keeps per column
 ALIGN_MOMENT_DOUBLES = 64
+# align.pca: the Gram stage reduces its partial tiles with one grid row per pair of 128-wide tiles (gram_reduce_kernel's
+# grid.y = nt (nt + 1) / 2 <= 65535  ->  nt <= 361), and mvf_apply_cached projects at most 128 columns per pass over the cache
+PCA_MAX_FEATURES = 361 * 128
+PCA_MAX_COMPS = 128
 EVAL_V, EVAL_JAC, EVAL_DIV, EVAL_CURL, EVAL_ACC, EVAL_CURV, EVAL_TORS, EVAL_JDET = 1, 2, 4, 8, 16, 32, 64, 128
 
 _p, _i64, _i, _d, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_size_t
@@ -133,6 +137,11 @@ SIGNATURES = {
                               _p]),
     "mvf_align_alpha_svi": (_i, [_p, _p, _p, _i64, _d, _d, _d, _p, _p, _p]),
     "mvf_align_transform_svi": (_i, [_p, _p, _p, _i64, C.POINTER(C.c_double), _d, _p, _p, _p, _i, _p]),
+    "mvf_colmeans_workspace_bytes": (_sz, [_i64, _i64]),
+    "mvf_colmeans": (_i, [_p, _i, _i64, _i64, _i64, _i64, _p, _p, _sz, _p]),
+    "mvf_ublk_pack": (_i, [_p, _i, _i64, _i64, _p, _i64, _i64, _p, _sz, _i, _p]),
+    "mvf_colmeans_csr": (_i, [_p, _p, _p, _i, _i64, _i64, _i64, _i64, _p, _p, _sz, _p, _sz, _p]),
+    "mvf_ublk_pack_csr": (_i, [_p, _p, _p, _i, _i64, _i64, _p, _i64, _i64, _p, _sz, _p, _sz, _i, _p]),
 }
 
 _lib = None

@@ -22,7 +22,7 @@ from .vectorfield import vector_field_function
 
 __all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate", "morpho_iterate_svi",
            "optimal_mapping", "mapping_from_best", "label_transfer_matrix", "init_sigma2", "init_probability_parameters", "coarse_rigid_alignment", "morpho_start",
-           "Morpho_pairwise", "morpho_align"]
+           "Morpho_pairwise", "morpho_align", "pca", "group_pca"]
 
 RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
 
@@ -1464,6 +1464,167 @@ def morpho_start(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity,
     out.coordsA, out.init_R, out.init_t = XA, R, t
     out.inducing_rows = np.asarray(uniq_idx[pick], dtype=np.int64)   # the rows of coordsA the inducing variables are
     return out
+
+
+# =====================================================================================================================
+# PCA across slices (`group_pca`, spateo/alignment/utils.py:88-149): from counts to the 50 features the assignment likes
+# =====================================================================================================================
+
+def pca_sign(PCs):
+    """The sign rule of ``pca``: every column of ``PCs`` (G, k) scaled by +-1 so that its loading of largest magnitude is
+    positive, the lowest index on ties.  Returns (PCs flipped, the (k,) signs)."""
+    PCs = np.asarray(PCs, dtype=np.float64)
+    top = np.argmax(np.abs(PCs), axis=0)                      # (np.argmax returns the first of equal maxima)
+    signs = np.where(PCs[top, np.arange(PCs.shape[1])] < 0, -1.0, 1.0)
+    return PCs * signs, signs
+
+
+def pca(mats, n_comps=50, zero_center=True, dtype="float32", device=None):
+    """One PCA over all slices of a series, on the MI355X: what ``group_pca`` (``spateo/alignment/utils.py:88-149``) gets
+    from ``sc.tl.pca`` on the concatenated slices.
+
+    ``mats``: a list of per-slice matrices (n_i, G) with equal G, each dense or ``scipy.sparse`` (a single matrix is a list
+    of one).  With N = sum n_i the stacked matrix is never formed on the host: the slices are packed one behind the other
+    into one device cache of the centred values in ``dtype`` ("float32" | "float64"; the difference ``x - mean`` is taken in
+    float64 and then rounded), laid out as the Gram kernel's operand (``mvf_colmeans`` / ``mvf_ublk_pack`` and their CSR
+    twins).  ``G = Xc^T Xc`` is the cached Gram kernel with unit weights (float64 accumulation in both modes), the G x G
+    symmetric eigenproblem runs ONCE on the host (``scipy.linalg.eigh`` with ``subset_by_index``: the top k pairs,
+    independent of N) and the scores ``Xc V`` are ``mvf_apply_cached`` on the same cache.
+
+    Returns a dict: ``X_pca`` - list of float64 (n_i, k) arrays (computed with float64 accumulation and stored in ``dtype``
+    on the device, so in float32 mode they carry a float32 rounding); ``PCs`` (G, k), orthonormal columns; ``variance`` (k,)
+    = eigenvalues / (N - 1); ``variance_ratio`` (k,) = eigenvalues / trace, the trace taken from the Gram diagonal;
+    ``mean`` (G,) float64.  ``k = min(n_comps, min(N, G) - 1)``, components by decreasing variance.
+
+    Sign rule: in every component the loading of largest magnitude is positive (the lowest index on ties) - sklearn's
+    ``svd_flip(u_based_decision=False)``; with the fixed summation orders of the kernels it makes two calls bit-identical.
+    The column means, and with them every output, depend on the stacked matrix only: a list of slices and their stacked
+    matrix give the same bits.
+
+    ``zero_center=False``: no means are taken (``mean`` is zeros), the raw values are packed and ``variance`` divides by N.
+
+    Refused before anything is launched (``ValueError``): non-finite input, N < 2, G < 2, unequal column counts,
+    ``n_comps < 1``; (``NotImplementedError``): G above ``_lib.PCA_MAX_FEATURES`` (what the Gram stage's reduction covers),
+    k above ``_lib.PCA_MAX_COMPS`` (one pass of ``mvf_apply_cached``); (``_lib.MVFError``): a cache larger than the free
+    device memory."""
+    from ._kernels import pca_slices
+
+    if dtype not in ("float32", "float64"):
+        raise ValueError("dtype must be 'float32' or 'float64'")
+    if is_sparse(mats) or (isinstance(mats, np.ndarray) and mats.ndim == 2):
+        mats = [mats]
+    mats = list(mats)
+    if len(mats) == 0:
+        raise ValueError("pca: no slices")
+    if int(n_comps) < 1:
+        raise ValueError(f"pca: n_comps must be at least 1, got {n_comps}")
+    slices, G = pca_slices(mats)
+    counts = [sl[4] if sl[0] == "csr" else sl[1].shape[0] for sl in slices]
+    N = int(sum(counts))
+    if N < 2:
+        raise ValueError(f"pca: needs at least 2 cells over all slices, got {N}")
+    if G < 2:
+        raise ValueError(f"pca: needs at least 2 features, got {G}")
+    if G > _lib.PCA_MAX_FEATURES:
+        raise NotImplementedError(f"pca: at most {_lib.PCA_MAX_FEATURES} features are supported (_lib.PCA_MAX_FEATURES, the "
+                                  f"extent of the Gram stage's tile reduction), got {G}; select genes first")
+    k_comp = min(int(n_comps), min(N, G) - 1)
+    if k_comp > _lib.PCA_MAX_COMPS:
+        raise NotImplementedError(f"pca: at most {_lib.PCA_MAX_COMPS} components are supported (_lib.PCA_MAX_COMPS, one pass "
+                                  f"of mvf_apply_cached), got {k_comp}")
+    k = _rt._make_kernels(device, dtype)
+    need, free = k.ublk_bytes(N, G), k.mem_free()
+    if need >= free:
+        raise _lib.MVFError(f"pca: the kernel-value cache ({need} bytes of HBM for {N} cells x {G} features in {dtype}) does "
+                            f"not fit the {free} bytes free on the device")
+    live = [sl for sl, c in zip(slices, counts) if c > 0]
+    k.pca_open(N, G)
+    try:
+        mean = np.array(k.pca_means(live), dtype=np.float64) if zero_center else np.zeros(G)
+        k.pca_pack(live, centred=bool(zero_center))
+        gram = k.pca_gram()
+        import scipy.linalg
+
+        # ascending eigenvalues of the top k_comp pairs (the lower triangle is read; the Gram stage writes both, equal)
+        lam, vec = scipy.linalg.eigh(gram, subset_by_index=[G - k_comp, G - 1])
+        lam, vec = lam[::-1], vec[:, ::-1]
+        PCs, _ = pca_sign(vec)
+        scores = k.pca_scores(PCs)
+    finally:
+        k.pca_close()
+    trace = float(np.trace(gram))
+    bounds = np.concatenate([[0], np.cumsum(counts)])
+    return {"X_pca": [np.array(scores[bounds[i] : bounds[i + 1]], dtype=np.float64) for i in range(len(counts))],
+            "PCs": np.ascontiguousarray(PCs), "variance": lam / (N - 1 if zero_center else N),
+            "variance_ratio": lam / trace if trace > 0 else np.zeros_like(lam), "mean": mean}
+
+
+def _pca_genes(adatas, use_hvg, hvg_key, genes):
+    """The genes ``group_pca`` runs on: those every slice carries - with ``use_hvg`` only the ones ``var[hvg_key]`` marks in
+    EVERY slice -, in the first slice's order; restricted to ``genes`` (in its order) when given."""
+    from ._morpho_pairwise import _var_column, var_names
+
+    names = [var_names(a) for a in adatas]
+    if use_hvg:
+        marks = [_var_column(a, hvg_key) for a in adatas]
+        lacking = [i for i, m in enumerate(marks) if m is None]
+        if lacking:
+            raise NotImplementedError(
+                f"group_pca(use_hvg=True): slices {lacking} have no var['{hvg_key}'] column, and scanpy's highly-variable-gene "
+                f"selection (sc.pp.highly_variable_genes, which the reference runs here) is not restated in this package. "
+                f"Remedies: pass genes=[...], pass use_hvg=False, or mark the column yourself.")
+        names = [[g for g, keep in zip(nm, np.asarray(m).astype(bool)) if keep] for nm, m in zip(names, marks)]
+    common = names[0]
+    for nm in names[1:]:
+        have = set(nm)
+        common = [g for g in common if g in have]
+    if genes is not None:
+        allowed, seen, picked = set(common), set(), []
+        for g in np.asarray(genes).tolist():
+            if g in allowed and g not in seen:
+                seen.add(g)
+                picked.append(g)
+        common = picked
+    if len(common) == 0:
+        if use_hvg:
+            raise ValueError("No highly variable genes were found. Please check your data or parameters for highly variable "
+                             "gene selection.")
+        raise ValueError("The number of common gene between all samples is 0.")
+    return common
+
+
+def group_pca(adatas, batch_key="batch", pca_key="X_pca", use_hvg=True, hvg_key="highly_variable", genes=None, **args):
+    """``st.align.group_pca`` (``spateo/alignment/utils.py:88-149``): one PCA over the ``.X`` of all slices, written back as
+    ``adatas[i].obsm[pca_key]`` (float64 (n_i, k)) - the representation ``Morpho_pairwise(rep_layer="X_pca",
+    rep_field="obsm")`` then aligns on.  Returns None, like the reference.
+
+    ``adatas``: ``AnnDataLite`` or, by duck typing, ``anndata.AnnData``.  ``batch_key`` is only checked: the reference's
+    ``ValueError`` when it is already an ``obs`` column (the slices are not concatenated here, so nothing is labelled).
+    The PCA runs on the genes common to all slices, in the first slice's order; ``genes=`` (an extension) restricts them.
+    ``use_hvg=True`` uses the genes ``var[hvg_key]`` marks in EVERY slice (the rule of ``common_genes``); none left: the
+    reference's "No highly variable genes were found" ``ValueError``; a slice without the column: ``NotImplementedError`` -
+    the reference computes the column with scanpy's ``highly_variable_genes`` at this point, which is not restated here.
+    ``**args``: ``n_comps`` (50), ``zero_center`` (True), ``dtype`` ("float32"), ``device`` of ``pca``; anything else
+    (``sc.tl.pca``'s solver options) is a ``TypeError``."""
+    from ._morpho_pairwise import _gene_positions, select_columns
+
+    unknown = set(args) - {"n_comps", "zero_center", "dtype", "device"}
+    if unknown:
+        raise TypeError(f"group_pca: unsupported arguments {sorted(unknown)} (n_comps, zero_center, dtype, device are)")
+    adatas = list(adatas)
+    for i, adata in enumerate(adatas):
+        obs = adata.obs
+        if batch_key in (obs.columns if hasattr(obs, "columns") else obs.keys()):
+            raise ValueError(f"batch_key '{batch_key}' already exists in adata.obs for dataset {i}. Please choose a different key.")
+    use = _pca_genes(adatas, use_hvg, hvg_key, genes)
+    mats = []
+    for a in adatas:
+        idx = _gene_positions(a, use)
+        whole = len(idx) == a.X.shape[1] and np.array_equal(idx, np.arange(len(idx)))
+        mats.append(a.X if whole else select_columns(a.X, idx))  # (all genes in place: the slice's own matrix, no copy)
+    res = pca(mats, **args)
+    for a, s in zip(adatas, res["X_pca"]):
+        a.obsm[pca_key] = s
 
 
 # the reference's top-level API on the stages above (its module reads this one's names at call time)
