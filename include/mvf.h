@@ -571,6 +571,25 @@ int mvf_assign_best(const void* xa4, int64_t na, const void* xb4, int64_t nb, co
                     const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier,
                     int32_t* row_idx, double* row_val, int32_t* col_idx, double* col_val, void* workspace,
                     size_t workspace_bytes, mvf_dtype dtype, void* stream);
+/* P applied to cell features without P: what the reference's users form from `Morpho_pairwise.run()`'s dense result -
+ * `P.T @ onehot(labels_A)` (an annotation carried to the next slice), `P @ X_B` (expression or an embedding carried across),
+ * and with the sums the row-normalised, barycentric forms.  With P[i][j] the value mvf_assign_dense stores, m_i e2_ij q_ij c3_j:
+ *   to_A (na x cb, ld = cb) = P   @ FB,   FB nb x cb (ld ldfb >= cb);
+ *   to_B (nb x ca, ld = ca) = P^T @ FA,   FA na x ca (ld ldfa >= ca);
+ *   K_NA (na) / K_NB (nb)   the row / column sums of P, each may be NULL (K_NB is the factor kernel's, K_NA rides with P @ FB).
+ * Features and outputs are DEVICE float64 row-major whatever `dtype` (the storage of the coordinates and layer operands).  A
+ * direction whose F and output are NULL and whose c is 0 is skipped; any other mix, both directions skipped, and K_NA without
+ * P @ FB are errors.  Any c >= 1: a sweep takes up to 64 columns (in blocks of 16), wider F is worked in 64-column chunks
+ * behind ONE pass 1 and one factor launch.  Pass 1 and the factors as mvf_assign runs them, then per direction and chunk one
+ * sweep of the tiles whose entries feed v_mfma_f64_16x16x4_f64 straight from the accumulator layout the tile routine leaves
+ * them in (P @ FB: the same sweep on the exchanged operands), and a kernel that adds the splits' partial products in split
+ * order: no floating-point atomics, two calls give the same bits.  Arguments, checks and the empty-side return (0, nothing
+ * touched) are mvf_assign's; every error is reported before anything is launched.  (An addition behind version 7.) */
+size_t mvf_assign_apply_workspace_bytes(int64_t na, int64_t nb, int cb, int ca); /* 0 for an empty side */
+int mvf_assign_apply(const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers, int nlayers,
+                     const double* model_mul, double sigma2, double sigma2_variance, double spatial_outlier,
+                     const double* FB, int cb, int64_t ldfb, double* to_A, const double* FA, int ca, int64_t ldfa, double* to_B,
+                     double* K_NA, double* K_NB, void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream);
 
 /* Column statistics of ONE layer's na x nb distance matrix d_ij, which is never written: what the code in front of the
  * reference's loop reduces its matrices to (`_init_guess_sigma2`, utils.py:1339-1354; `_init_probability_parameters`,

@@ -48,6 +48,11 @@
 // spateo/alignment/utils.py:157-255, which takes row and column maxima of the dense P) runs pass 1 and the factors as they are
 // and then one sweep per direction on the same tile routine: per row and per column of P the largest entry and its index
 // under the reference's two tie rules, from states that combine in any order (see struct Best).
+//
+// mvf_assign_apply (what the reference's users form from the dense P of `Morpho_pairwise.run()`: P.T @ onehot(labels), P @ X_B,
+// the row-normalised forms) runs pass 1 and the factors as they are and then, per direction and 64-column chunk of the
+// features, one sweep whose tile entries feed the same MFMA straight from the accumulator layout they are formed in (see
+// assign_apply_kernel); P @ FB is that sweep on the exchanged operands.
 #include <climits>
 
 #include "mvf_common.h"
@@ -177,18 +182,20 @@ __device__ __forceinline__ void product_distances(const DevLayer& ly, int64_t i0
 }
 
 // The same for a label layer: d = T[la_i][lb_j], T = ly.X (float64, row length ly.ld), the labels integers held in ly.a / ly.b.
-// 8 row labels, 2 column labels and 16 table reads per lane; no clamp, no square root.
+// 8 row labels, 2 column labels and 16 table reads per lane; no clamp, no square root.  TR: the caller sweeps the TRANSPOSED
+// problem (rows = B cells, columns = A cells; ly.a / ly.b already exchanged) and the table is read as T[column label][row label].
+template <bool TR = false>
 __device__ __forceinline__ void label_distances(const DevLayer& ly, int64_t i0, int64_t j0, int64_t na, int64_t nb, int li, int lk,
                                                 f64x4 (&acc)[2][2]) {
     const double* tab = (const double*)ly.X;
     int64_t cj[2];
 #pragma unroll
-    for (int b = 0; b < 2; ++b) cj[b] = (int64_t)ly.b[std::min<int64_t>(j0 + 16 * b + li, nb - 1)];
+    for (int b = 0; b < 2; ++b) cj[b] = (int64_t)ly.b[std::min<int64_t>(j0 + 16 * b + li, nb - 1)] * (TR ? ly.ld : 1);
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const double* row = tab + (int64_t)ly.a[std::min<int64_t>(i0 + 16 * a + lk + 4 * r, na - 1)] * ly.ld;
+            const double* row = tab + (int64_t)ly.a[std::min<int64_t>(i0 + 16 * a + lk + 4 * r, na - 1)] * (TR ? 1 : ly.ld);
 #pragma unroll
             for (int b = 0; b < 2; ++b) acc[a][b][r] = row[cj[b]];
         }
@@ -196,8 +203,8 @@ __device__ __forceinline__ void label_distances(const DevLayer& ly, int64_t i0, 
 
 // q[a][b][r] = product over the layers of the probability of d(row i0 + 16 a + lk + 4 r, column j0 + 16 b + li), for the
 // wave's 32 x 32 block at (i0, j0).  The branch between the two kinds of layer is the same on every lane; the probability is
-// formed by one piece of code for both.
-template <typename T>
+// formed by one piece of code for both.  TR: see label_distances.
+template <typename T, bool TR = false>
 __device__ __forceinline__ void layer_product(const DevLayers& L, int64_t i0, int64_t j0, int64_t na, int64_t nb, int li, int lk,
                                               f64x4 (&q)[2][2]) {
 #pragma unroll
@@ -208,7 +215,7 @@ __device__ __forceinline__ void layer_product(const DevLayers& L, int64_t i0, in
         const DevLayer& ly = L.l[l];
         f64x4 acc[2][2];
         if (ly.post == POST_LABEL)
-            label_distances(ly, i0, j0, na, nb, li, lk, acc);
+            label_distances<TR>(ly, i0, j0, na, nb, li, lk, acc);
         else
             product_distances<T>(ly, i0, j0, na, nb, li, lk, acc);
 #pragma unroll
@@ -1320,6 +1327,224 @@ int run_assign_best(hipStream_t st, const Plan& p, const BestPlan& bp, const voi
     return 0;
 }
 
+// ---- mvf_assign_apply: P @ FB and P^T @ FA without P.  One sweep kernel for both directions, on pass 1's tile walk: grid
+// (column tiles, row splits) of a SWEEP problem whose rows carry the features and whose columns receive the product,
+//   SWAP = false  rows = A cells, columns = B cells:  out^T = FA^T P      (to_B = P^T @ FA; pass 1's grid as it is)
+//   SWAP = true   rows = B cells, columns = A cells:  out^T = FB^T P^T    (to_A = P @ FB; the operands exchanged - layers
+//                 Xp <-> Yp and a <-> b, a label layer's table read transposed - as mvf_assign_layer_stats' row statistics are).
+// layer_product and the spatial factor leave p = P[row i0 + 16 a + lk + 4 r][column j0 + 16 b + li] in lane (li, lk), which for
+// fixed (a, r) IS the B operand B[k = lk][n = li] of v_mfma_f64_16x16x4_f64 over the 4 rows i0 + 16 a + 4 r + (0 .. 3); the A
+// operand A[m = li][k = lk] = F[that row][16 c + li] is 16 consecutive doubles per lane group, and the accumulator
+// D[m = lk + 4 r'][n = li] = out^T[feature 16 c + lk + 4 r'][column j0 + 16 b + li]: no shuffle, no transpose of P.  CB column
+// blocks of 16 features (at most 4: 32 accumulator doubles per lane).  The entry is the value mvf_assign_dense stores,
+// m ((e2 q) c3), in that product order under either SWAP.  A padded row has p = 0 and F = 0; a padded column has factor 0.
+// The two row halves of the workgroup meet in LDS, which also turns the tile round: part[split][column][16 CB] is written in
+// whole rows.  ksum (may be NULL): the columns' sums of p, kpart[split][nc_pad] - K_NA under SWAP.
+template <typename T, int CB, bool SWAP>
+__global__ __launch_bounds__(256) void assign_apply_kernel(const T* __restrict__ xr4, int64_t nr, const T* __restrict__ xc4,
+                                                           int64_t nc, DevLayers L, const double* __restrict__ rowfac,
+                                                           int64_t rstride, const double* __restrict__ colfac, int64_t cstride,
+                                                           double h2, const double* __restrict__ F, int64_t ldf, int cw,
+                                                           int64_t rtiles, int64_t nc_pad, double* __restrict__ part,
+                                                           double* __restrict__ kpart) {
+    constexpr int W = 16 * CB;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, lk = lane >> 4, wi = wave >> 1, wj = wave & 1;
+    const int64_t j0 = (int64_t)blockIdx.x * AT + 32 * wj;
+    const int64_t t_lo = rtiles * blockIdx.y / gridDim.y, t_hi = rtiles * (blockIdx.y + 1) / gridDim.y;
+    Point cb[2];
+    double cf[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int64_t j = j0 + 16 * b + li;
+        cb[b] = load_point(xc4, std::min<int64_t>(j, nc - 1));
+        cf[b] = j < nc ? colfac[j * cstride] : 0.0;
+    }
+    f64x4 acc[CB][2];
+#pragma unroll
+    for (int c = 0; c < CB; ++c)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[c][b] = f64x4{0.0, 0.0, 0.0, 0.0};
+    double ks[2] = {0.0, 0.0};
+    for (int64_t t = t_lo; t < t_hi; ++t) {
+        const int64_t i0 = t * AT + 32 * wi;
+        f64x4 q[2][2];
+        if (SWAP)
+            layer_product<T, true>(L, i0, j0, nr, nc, li, lk, q);
+        else
+            layer_product<T, false>(L, i0, j0, nr, nc, li, lk, q);
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t i = i0 + 16 * a + lk + 4 * r;
+                const bool live = i < nr;
+                const int64_t ic = live ? i : nr - 1;
+                const Point pa = load_point(xr4, ic);
+                const double rf = live ? rowfac[ic * rstride] : 0.0;
+                double f[CB];
+#pragma unroll
+                for (int c = 0; c < CB; ++c) f[c] = live && 16 * c + li < cw ? F[ic * ldf + 16 * c + li] : 0.0;
+                double p[2];
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const double d = sq_dist(pa, cb[b]);
+                    const double eq = exp(d * h2) * q[a][b][r];
+                    p[b] = SWAP ? cf[b] * (eq * rf) : rf * (eq * cf[b]);  // P_ij as mvf_assign_dense stores it
+                    ks[b] += p[b];
+                }
+#pragma unroll
+                for (int c = 0; c < CB; ++c)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) acc[c][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[c], p[b], acc[c][b], 0, 0, 0);
+            }
+    }
+    __shared__ double red[AT][W + 1];
+    __shared__ double kred[8][AT];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) kred[wi * 4 + lk][32 * wj + 16 * b + li] = ks[b];
+    if (wi == 1) {
+#pragma unroll
+        for (int c = 0; c < CB; ++c)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) red[32 * wj + 16 * b + li][16 * c + lk + 4 * r] = acc[c][b][r];
+    }
+    __syncthreads();
+    if (wi == 0) {
+#pragma unroll
+        for (int c = 0; c < CB; ++c)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    double& x = red[32 * wj + 16 * b + li][16 * c + lk + 4 * r];
+                    x = acc[c][b][r] + x;
+                }
+    }
+    __syncthreads();
+    double* out = part + ((int64_t)blockIdx.y * nc_pad + (int64_t)blockIdx.x * AT) * W;
+    for (int e = threadIdx.x; e < AT * W; e += 256) out[e] = red[e / W][e % W];
+    if (kpart && threadIdx.x < AT) {
+        double tot = 0.0;
+#pragma unroll
+        for (int g = 0; g < 8; ++g) tot += kred[g][threadIdx.x];
+        kpart[(int64_t)blockIdx.y * nc_pad + (int64_t)blockIdx.x * AT + threadIdx.x] = tot;
+    }
+}
+
+// the splits' partial products added in split order: out[j][c0 + c] for j < n, c < cw (part[split][n_pad][W])
+__global__ __launch_bounds__(256) void assign_apply_reduce_kernel(const double* __restrict__ part, int64_t nsplit, int64_t n,
+                                                                  int64_t n_pad, int W, int cw, double* __restrict__ out,
+                                                                  int64_t ldo) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n * cw) return;
+    const int64_t j = e / cw;
+    const int c = (int)(e % cw);
+    double s = 0.0;
+    for (int64_t sp = 0; sp < nsplit; ++sp) s += part[(sp * n_pad + j) * W + c];
+    out[j * ldo + c] = s;
+}
+
+// the splits' column sums added in split order
+__global__ __launch_bounds__(256) void assign_apply_ksum_kernel(const double* __restrict__ kpart, int64_t nsplit, int64_t n,
+                                                                int64_t n_pad, double* __restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    double s = 0.0;
+    for (int64_t sp = 0; sp < nsplit; ++sp) s += kpart[sp * n_pad + j];
+    out[j] = s;
+}
+
+constexpr int APPLY_CHUNK = 64;  // feature columns per sweep
+
+int apply_width(int c) { return 16 * (int)std::min<int64_t>(APPLY_CHUNK / 16, cdiv(c, 16)); }  // 0 for c == 0
+
+// workspace of mvf_assign_apply: pass 1's partials and the factors (mvf_assign's offsets), K_NB when it is not returned, the
+// sweeps' partial products (one buffer, both directions and every chunk in turn) and the partial K_NA
+struct ApplyPlan {
+    size_t off_knb, off_part, off_kpart, total;
+};
+
+ApplyPlan make_apply_plan(const Plan& p, int cb, int ca) {
+    ApplyPlan t;
+    size_t o = p.off_part2;  // (pass 2's partials are not needed)
+    t.off_knb = o, o += align_up((size_t)p.nb_pad * sizeof(double), 256);
+    const size_t to_a = (size_t)p.csplit * p.na_pad * apply_width(cb), to_b = (size_t)p.rsplit * p.nb_pad * apply_width(ca);
+    t.off_part = o, o += align_up(std::max(to_a, to_b) * sizeof(double), 256);
+    t.off_kpart = o, o += align_up((size_t)p.csplit * p.na_pad * sizeof(double), 256);
+    t.total = o;
+    return t;
+}
+
+// one direction: the chunks of F (n_rows x c, ld ldf) swept one after the other into out (n_cols x c, dense)
+template <typename T, bool SWAP>
+int run_apply_direction(hipStream_t st, const void* xr4, int64_t nr, const void* xc4, int64_t nc, const DevLayers& L,
+                        const double* rowfac, int64_t rstride, const double* colfac, int64_t cstride, double h2, const double* F,
+                        int c, int64_t ldf, double* out, int64_t rtiles, int64_t ctiles, int64_t nsplit, int64_t nc_pad,
+                        double* part, double* kpart, double* ksum) {
+    const dim3 grid((unsigned)ctiles, (unsigned)nsplit);
+    for (int c0 = 0; c0 < c; c0 += APPLY_CHUNK) {
+        const int cw = std::min(APPLY_CHUNK, c - c0), W = apply_width(cw);
+        double* kp = c0 == 0 && ksum ? kpart : nullptr;
+#define MVF_APPLY(CB)                                                                                                          \
+    hipLaunchKernelGGL((assign_apply_kernel<T, CB, SWAP>), grid, dim3(256), 0, st, (const T*)xr4, nr, (const T*)xc4, nc, L, rowfac, \
+                       rstride, colfac, cstride, h2, F + c0, ldf, cw, rtiles, nc_pad, part, kp)
+        if (W == 16)
+            MVF_APPLY(1);
+        else if (W == 32)
+            MVF_APPLY(2);
+        else if (W == 48)
+            MVF_APPLY(3);
+        else
+            MVF_APPLY(4);
+#undef MVF_APPLY
+        MVF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(assign_apply_reduce_kernel, dim3((unsigned)cdiv(nc * cw, 256)), dim3(256), 0, st, part, nsplit, nc, nc_pad,
+                           W, cw, out + c0, (int64_t)c);
+        MVF_LAUNCH_CHECK();
+        if (kp) {
+            hipLaunchKernelGGL(assign_apply_ksum_kernel, dim3((unsigned)cdiv(nc, 256)), dim3(256), 0, st, kp, nsplit, nc, nc_pad, ksum);
+            MVF_LAUNCH_CHECK();
+        }
+    }
+    return 0;
+}
+
+template <typename T>
+int run_assign_apply(hipStream_t st, const Plan& p, const ApplyPlan& ap, const void* xa4, int64_t na, const void* xb4, int64_t nb,
+                     const DevLayers& L, const double* mm, double h1, double h2, double outlier, const double* FB, int cb,
+                     int64_t ldfb, double* to_A, const double* FA, int ca, int64_t ldfa, double* to_B, double* K_NA, double* K_NB,
+                     char* ws) {
+    double* part1 = (double*)(ws + p.off_part1);
+    double* fac = (double*)(ws + p.off_fac);
+    double* part = (double*)(ws + ap.off_part);
+    double* kpart = (double*)(ws + ap.off_kpart);
+    if (!K_NB) K_NB = (double*)(ws + ap.off_knb);
+    hipLaunchKernelGGL((assign_pass1_kernel<T>), dim3((unsigned)p.ctiles, (unsigned)p.rsplit), dim3(256), 0, st, (const T*)xa4, na,
+                       (const T*)xb4, nb, L, mm, h1, h2, p.rtiles, p.nb_pad, part1);
+    MVF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(assign_factors_kernel, dim3((unsigned)cdiv(p.nb_pad, 256)), dim3(256), 0, st, part1, p.rsplit, nb, p.nb_pad,
+                       outlier, fac, K_NB);
+    MVF_LAUNCH_CHECK();
+    if (to_B)  // rows = A cells (factor m_i), columns = B cells (factor c3_j = fac[4 j + 2]; zero for the padded ones)
+        if (const int rc = run_apply_direction<T, false>(st, xa4, na, xb4, nb, L, mm, 1, fac + 2, 4, h2, FA, ca, ldfa, to_B, p.rtiles,
+                                                         p.ctiles, p.rsplit, p.nb_pad, part, kpart, nullptr))
+            return rc;
+    if (to_A) {  // the operands exchanged: rows = B cells (factor c3_j), columns = A cells (factor m_i)
+        DevLayers Ls = L;
+        for (int l = 0; l < MAX_LAYERS; ++l) {
+            if (Ls.l[l].post != POST_LABEL) std::swap(Ls.l[l].X, Ls.l[l].Y);  // (a label layer: X stays the table, read transposed)
+            std::swap(Ls.l[l].a, Ls.l[l].b);
+        }
+        if (const int rc = run_apply_direction<T, true>(st, xb4, nb, xa4, na, Ls, fac + 2, 4, mm, 1, h2, FB, cb, ldfb, to_A, p.ctiles,
+                                                        p.rtiles, p.csplit, p.na_pad, part, kpart, K_NA))
+            return rc;
+    }
+    return 0;
+}
+
 }  // namespace
 }  // namespace mvf
 
@@ -1506,4 +1731,45 @@ extern "C" int mvf_assign_best(const void* xa4, int64_t na, const void* xb4, int
                                       col_val, (char*)workspace);
     return run_assign_best<double>(st, p, bp, xa4, na, xb4, nb, L, model_mul, h1, h2, spatial_outlier, row_idx, row_val, col_idx,
                                    col_val, (char*)workspace);
+}
+
+extern "C" size_t mvf_assign_apply_workspace_bytes(int64_t na, int64_t nb, int cb, int ca) {
+    if (na <= 0 || nb <= 0 || cb < 0 || ca < 0) return 0;
+    return make_apply_plan(make_plan(na, nb), cb, ca).total;
+}
+
+extern "C" int mvf_assign_apply(const void* xa4, int64_t na, const void* xb4, int64_t nb, const mvf_assign_layer* layers,
+                                int nlayers, const double* model_mul, double sigma2, double sigma2_variance,
+                                double spatial_outlier, const double* FB, int cb, int64_t ldfb, double* to_A, const double* FA,
+                                int ca, int64_t ldfa, double* to_B, double* K_NA, double* K_NB, void* workspace,
+                                size_t workspace_bytes, mvf_dtype dtype, void* stream) {
+    const char* who = "mvf_assign_apply";
+    const bool row_dir = FB && to_A && cb >= 1, col_dir = FA && to_B && ca >= 1;
+    MVF_REQUIRE(row_dir || (!FB && !to_A && cb == 0), "%s: FB, cb >= 1 and to_A must all be given, or NULL / 0 to skip P @ FB", who);
+    MVF_REQUIRE(col_dir || (!FA && !to_B && ca == 0), "%s: FA, ca >= 1 and to_B must all be given, or NULL / 0 to skip P^T @ FA", who);
+    MVF_REQUIRE(row_dir || col_dir, "%s: nothing to compute: both directions are skipped", who);
+    MVF_REQUIRE(!K_NA || row_dir, "%s: K_NA rides with P @ FB, which is skipped", who);
+    MVF_REQUIRE((!row_dir || ldfb >= cb) && (!col_dir || ldfa >= ca), "%s: a feature matrix's ld is below its column count", who);
+    if (na == 0 || nb == 0) return 0;
+    MVF_REQUIRE(na > 0 && nb > 0, "%s: negative size", who);
+    MVF_REQUIRE(na < ((int64_t)1 << 31) && nb < ((int64_t)1 << 31), "%s: too many cells", who);
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "%s: bad dtype %d", who, (int)dtype);
+    MVF_REQUIRE(nlayers >= 1 && nlayers <= MAX_LAYERS, "%s: need 1 .. %d layers, got %d", who, MAX_LAYERS, nlayers);
+    MVF_REQUIRE(xa4 && xb4 && layers && model_mul && workspace, "%s: null pointer", who);
+    MVF_REQUIRE(sigma2 > 0.0 && sigma2_variance > 0.0 && spatial_outlier >= 0.0, "%s: need sigma2 > 0, sigma2_variance > 0, outlier >= 0", who);
+    const Plan p = make_plan(na, nb);
+    const ApplyPlan ap = make_apply_plan(p, cb, ca);
+    MVF_REQUIRE(workspace_bytes >= ap.total, "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, ap.total);
+    DevLayers L;
+    L.n = nlayers;
+    for (int l = 0; l < nlayers; ++l)
+        if (const int rc = check_layer(who, l, layers[l], true, L.l[l])) return rc;
+    for (int l = nlayers; l < MAX_LAYERS; ++l) L.l[l] = L.l[0];
+    const double h1 = -1.0 / (2.0 * (sigma2 / sigma2_variance)), h2 = -1.0 / (2.0 * sigma2);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MVF_F32)
+        return run_assign_apply<float>(st, p, ap, xa4, na, xb4, nb, L, model_mul, h1, h2, spatial_outlier, FB, cb, ldfb, to_A, FA, ca,
+                                       ldfa, to_B, K_NA, K_NB, (char*)workspace);
+    return run_assign_apply<double>(st, p, ap, xa4, na, xb4, nb, L, model_mul, h1, h2, spatial_outlier, FB, cb, ldfb, to_A, FA, ca,
+                                    ldfa, to_B, K_NA, K_NB, (char*)workspace);
 }

@@ -781,6 +781,52 @@ class HipKernels:
         return out
 
     @_on_device
+    def assign_apply(self, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, spatial_outlier, features_B=None,
+                     features_A=None, sums=True):
+        """The assignment applied to cell features without P (mvf_assign_apply): arguments as assign takes them, plus
+        features_B (nb, cb) and / or features_A (na, ca), device float64 (rows may be strided: a column slice of a wider
+        row-major tensor).  Returns device float64 tensors {to_A (na, cb) = P @ features_B, to_B (nb, ca) = P^T @ features_A,
+        K_NB (nb,) and - with features_B, which its sweep carries - K_NA (na,)}; a direction without features is absent, one
+        must be given.  ``sums=False`` leaves K_NA / K_NB out."""
+        na, nb = xa4.shape[0], xb4.shape[0]
+        f64 = torch.float64
+        if features_A is None and features_B is None:
+            raise ValueError("assign_apply: features_A or features_B must be given")
+        for F, n, name in ((features_B, nb, "features_B"), (features_A, na, "features_A")):
+            if F is None:
+                continue
+            if F.dtype != f64 or F.dim() != 2 or F.shape[0] != n or F.shape[1] < 1 or (n > 0 and F.stride(1) != 1) \
+                    or (n > 1 and F.stride(0) < F.shape[1]):
+                raise ValueError(f"assign_apply: {name} must be a float64 ({n}, c >= 1) tensor with contiguous rows")
+        arr = (_lib.AssignLayer * len(layers))()
+        for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, layers):
+            s.Xp, s.Yp, s.a, s.b, s.ld = _ptr(Xp), _ptr(Yp), _ptr(a), _ptr(b), int(ld)
+            s.metric, s.prob, s.param = int(metric), int(prob), float(param)
+        out = {}
+        cb = ca = 0
+        ldb = lda = 0
+        if features_B is not None:
+            cb = int(features_B.shape[1])
+            ldb = int(features_B.stride(0)) if nb > 1 else cb
+            out["to_A"] = self.empty(na, cb, dtype=f64)
+            if sums:
+                out["K_NA"] = self.empty(na, dtype=f64)
+        if features_A is not None:
+            ca = int(features_A.shape[1])
+            lda = int(features_A.stride(0)) if na > 1 else ca
+            out["to_B"] = self.empty(nb, ca, dtype=f64)
+        if sums:
+            out["K_NB"] = self.empty(nb, dtype=f64)
+        need = int(self.lib.mvf_assign_apply_workspace_bytes(na, nb, cb, ca))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.mvf_assign_apply(_ptr(xa4), na, _ptr(xb4), nb, arr, len(layers), _ptr(model_mul), float(sigma2),
+                                             float(sigma2_variance), float(spatial_outlier), _ptr(features_B), cb, ldb,
+                                             _ptr(out.get("to_A")), _ptr(features_A), ca, lda, _ptr(out.get("to_B")),
+                                             _ptr(out.get("K_NA")), _ptr(out.get("K_NB")), _ptr(ws), need, self.cdtype,
+                                             self._stream()), "mvf_assign_apply")
+        return out
+
+    @_on_device
     def assign_layer_stats(self, layer, na, nb, k=0):
         """Column statistics of one layer's (na, nb) distance matrix (mvf_assign_layer_stats).  layer: one tuple as assign
         takes them (prob and param are not read).  Returns device tensors {cmin (nb,) float64, sums (2,) float64 = sum d,

@@ -126,6 +126,9 @@ SIGNATURES = {
                              _sz, _i, _p]),
     "mvf_assign_best_workspace_bytes": (_sz, [_i64, _i64]),
     "mvf_assign_best": (_i, [_p, _i64, _p, _i64, C.POINTER(AssignLayer), _i, _p, _d, _d, _d, _p, _p, _p, _p, _p, _sz, _i, _p]),
+    "mvf_assign_apply_workspace_bytes": (_sz, [_i64, _i64, _i, _i]),
+    "mvf_assign_apply": (_i, [_p, _i64, _p, _i64, C.POINTER(AssignLayer), _i, _p, _d, _d, _d, _p, _i, _i64, _p, _p, _i, _i64, _p,
+                              _p, _p, _p, _sz, _i, _p]),
     "mvf_assign_layer_stats_workspace_bytes": (_sz, [_i64, _i64, _i]),
     "mvf_assign_layer_stats": (_i, [C.POINTER(AssignLayer), _i64, _i64, _i, _p, _p, _p, _p, _p, _sz, _i, _p]),
     "mvf_align_alpha": (_i, [_p, _p, _p, _i64, _d, _d, _p, _p, _p]),

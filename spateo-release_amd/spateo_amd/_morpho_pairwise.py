@@ -266,6 +266,11 @@ class Morpho_pairwise:
     assignment with ``mvf_assign_best`` (in SVI mode the closing full assignment runs as with ``return_mapping=True``); after
     ``run()`` the method ``optimal_mapping(keep_all=False)`` returns the reference's ``mapping_aligned_coords(XAHat, coordsB, P,
     keep_all)`` - ``(by_A, by_B)``, see ``align.optimal_mapping`` - for slices of any size, with or without a ``P``.
+    ``apply=dict(features_A=, features_B=, normalize=True)`` is forwarded to the loop (``align.morpho_iterate``'s ``apply``:
+    the last assignment applied to cell features without ``P``; in SVI mode the closing full assignment runs); a string
+    names a categorical ``obs`` column of that sample - expanded to one-hot columns in category order - or an ``obsm`` key.
+    After ``run()`` the result is ``self.applied``, ``align.apply_assignment``'s dict, with ``categories_A`` / ``categories_B``
+    beside it where an ``obs`` column was named.
 
     Accepted with no effect: ``use_chunk``, ``chunk_capacity`` and ``pre_compute_dist`` (memory layouts of the reference; the
     fused assignment writes no NA x NB matrix at all), ``save_concrete_iter``, ``graph_knn``, and ``verbose`` beyond logging.
@@ -285,7 +290,8 @@ class Morpho_pairwise:
                  kappa=1.0, partial_robust_level=10, normalize_c=True, normalize_g=False, separate_mean=True,
                  separate_scale=False, dtype="float32", device="cpu", verbose=True, guidance_pair=None, guidance_effect=False,
                  guidance_weight=1.0, use_chunk=False, chunk_capacity=1.0, return_mapping=False, update_R=True, *, seed=0,
-                 inducing_idx=None, subsample_A=None, subsample_B=None, batch_perm=None, optimal_mapping=False):
+                 inducing_idx=None, subsample_A=None, subsample_B=None, batch_perm=None, optimal_mapping=False,
+                 apply=None):
         self.verbose = verbose
         self.sampleA, self.sampleB = sampleA, sampleB
         self.rep_layer, self.rep_field, self.genes = rep_layer, rep_field, genes
@@ -307,11 +313,13 @@ class Morpho_pairwise:
         self.use_chunk, self.chunk_capacity, self.return_mapping, self.update_R = use_chunk, chunk_capacity, return_mapping, update_R
         self.seed, self.inducing_idx, self.subsample_A, self.subsample_B, self.batch_perm = seed, inducing_idx, subsample_A, subsample_B, batch_perm
         self._optimal_mapping, self.best = bool(optimal_mapping), None   # (the name optimal_mapping is the method's)
+        self._apply_request, self.applied = apply, None
         if dtype not in ("float32", "float64"):
             raise ValueError("dtype must be 'float32' or 'float64'")
         self._check()
         self._refuse()
         self._align_preprocess()
+        self._apply, self._apply_categories = self._resolve_apply()
 
     # ---- _check (:316-441) ----
     def _check(self):
@@ -432,6 +440,34 @@ class Morpho_pairwise:
         if self.verbose:
             lm.main_info("Preprocess finished.", indent_level=1)
 
+    def _resolve_apply(self):
+        """``apply=`` with its strings looked up: (the dict the loops take or None, {"categories_A" / "categories_B": list})."""
+        req = self._apply_request
+        if req is None:
+            return None, {}
+        if not isinstance(req, dict) or not set(req) <= {"features_A", "features_B", "normalize"}:
+            raise ValueError("Morpho_pairwise: apply must be a dict with features_A and / or features_B and, optionally, normalize")
+        out, cats = {"normalize": bool(req.get("normalize", True))}, {}
+        for side, sample, n in (("A", self.sampleA, self.NA), ("B", self.sampleB, self.NB)):
+            F = req.get(f"features_{side}")
+            if isinstance(F, str):
+                if F in sample.obs:
+                    if not _is_categorical(sample.obs[F]):
+                        raise ValueError(f"Morpho_pairwise: apply: obs column '{F}' of sample {side} is not categorical")
+                    cats[f"categories_{side}"], codes = _categorical(sample, F)
+                    if len(codes) and codes.min() < 0:
+                        raise ValueError(f"Morpho_pairwise: apply: obs column '{F}' of sample {side} has missing values")
+                    F = np.zeros((n, max(len(cats[f"categories_{side}"]), 1)))
+                    F[np.arange(n), codes] = 1.0             # one column per category, in category order
+                elif F in sample.obsm:
+                    F = np.asarray(sample.obsm[F])
+                else:
+                    raise KeyError(f"Morpho_pairwise: apply: '{F}' is neither an obs column nor an obsm key of sample {side}")
+            if F is not None:
+                out[f"features_{side}"] = F
+        _al._apply_argument(out, self.NA, self.NB, "Morpho_pairwise")   # the loops' own validation, before anything runs
+        return out, cats
+
     def _denormalize(self, X):
         """``X * normalize_scales[1] + normalize_means[1]`` (``_wrap_output``, ``_save_iter``): back to the fixed slice's frame."""
         if not self.normalize_c:
@@ -441,7 +477,7 @@ class Morpho_pairwise:
     def _P_fits(self):
         """Whether the dense P of the last assignment is within align.RETURN_P_MAX_ENTRIES."""
         columns = self.NB
-        if self.SVI_mode and not (self.return_mapping or self._optimal_mapping):
+        if self.SVI_mode and not (self.return_mapping or self._optimal_mapping or self._apply is not None):
             columns = _al._svi_batch_size(self.NB, self.batch_size)
         return self.NA * columns <= _al.RETURN_P_MAX_ENTRIES
 
@@ -472,7 +508,7 @@ class Morpho_pairwise:
                     partial_robust_level=self.partial_robust_level, sigma2_end=self.sigma2_end, nn_init_weight=self.nn_init_weight,
                     update_R=self.update_R, record="arrays" if self.iter_key_added is not None else False,
                     sparse_calculation_mode=bool(self.sparse_calculation_mode), sparse_top_k=self.sparse_top_k, return_P=dense_P,
-                    optimal_mapping=self._optimal_mapping, **common, **start)
+                    optimal_mapping=self._optimal_mapping, apply=self._apply, **common, **start)
         if self.SVI_mode:
             out = _al.morpho_iterate_svi(start.coordsA, self.coordsB, self.exp_layers_A, self.exp_layers_B, batch_size=self.batch_size,
                                          batch_perm=self.batch_perm, seed=self.seed, return_mapping=bool(self.return_mapping), **loop)
@@ -514,6 +550,7 @@ class Morpho_pairwise:
         self.optimal_RnA = self._denormalize(out["optimal_RnA"])
         self.P = out.get("P")
         self.best = out.get("best")
+        self.applied = dict(out["applied"], **self._apply_categories) if "applied" in out else None
         self.iter_added = None
         if self.iter_key_added is not None:
             hist = out["history"]

@@ -21,7 +21,7 @@ from .engine import SparseVFCEngine, _consistent_K
 from .vectorfield import vector_field_function
 
 __all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate", "morpho_iterate_svi",
-           "optimal_mapping", "mapping_from_best", "label_transfer_matrix", "init_sigma2", "init_probability_parameters", "coarse_rigid_alignment", "morpho_start",
+           "optimal_mapping", "mapping_from_best", "apply_assignment", "label_transfer_matrix", "init_sigma2", "init_probability_parameters", "coarse_rigid_alignment", "morpho_start",
            "Morpho_pairwise", "morpho_align", "pca", "group_pca"]
 
 RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
@@ -228,7 +228,8 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
     Returns host float64: ``K_NA``, ``K_NA_spatial``, ``K_NA_sigma2`` (NA,), ``K_NB`` (NB,), ``Sp``, ``Sp_spatial``,
     ``Sp_sigma2``, ``sigma2_related`` (already divided by ``Dim * Sp_sigma2``, ``:1200``), ``PXB = P @ coordsB`` (NA, D)
     and, with ``return_P=True``, the dense ``P`` (NA, NB) - label transfer and debugging only; ``ValueError`` above
-    ``RETURN_P_MAX_ENTRIES`` entries.  Two calls give bit-identical results.
+    ``RETURN_P_MAX_ENTRIES`` entries (``apply_assignment`` forms ``P @ F`` and ``P.T @ F`` at any size, without ``P``).  Two calls
+    give bit-identical results.
 
     What the other updates take from it:
 
@@ -368,6 +369,142 @@ def optimal_mapping(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity
     layers = _prepare_layers(k, LA, LB, codes, table)
     dev = k.assign_best(k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, float(outlier))
     return mapping_from_best(_best_to_host(k, dev), XA, XB, keep_all)
+
+
+def _transfer_features(features, n, name, who="apply_assignment"):
+    """``features_A`` / ``features_B`` of apply_assignment validated (no device needed): None, or host float64 (n, c >= 1).  A
+    1-D integer array is a label vector and becomes its one-hot matrix (n, max + 1)."""
+    if features is None:
+        return None
+    if is_sparse(features):
+        raise NotImplementedError(f"{who}: scipy.sparse {name} is not supported: the sweep reads dense float64 rows; pass "
+                                  f"{name}.toarray(), a block of columns at a time if it is wide")
+    F = np.asarray(features)
+    if F.ndim == 1 and F.dtype.kind in "iu":
+        if len(F) != n:
+            raise ValueError(f"{who}: {name} must have one entry per cell of its slice ({n}), got {len(F)}")
+        if len(F) and F.min() < 0:
+            raise ValueError(f"{who}: a label vector {name} must be non-negative")
+        out = np.zeros((n, int(F.max()) + 1 if len(F) else 1))
+        out[np.arange(n), F.astype(np.int64)] = 1.0
+        return out
+    if F.dtype.kind not in "fiub":
+        raise ValueError(f"{who}: {name} must be numeric (n, c) or a 1-D integer label vector, got dtype {F.dtype}")
+    F = np.ascontiguousarray(F, dtype=np.float64)
+    if F.ndim != 2 or F.shape[0] != n:
+        raise ValueError(f"{who}: {name} must have one row per cell of its slice ({n}), got shape {F.shape}")
+    if F.shape[1] < 1:
+        raise ValueError(f"{who}: {name} needs at least one column")
+    if not np.isfinite(F).all():
+        raise ValueError(f"{who}: {name} must be finite")
+    return F
+
+
+def _normalized_rows(M, K):
+    """Every row of M divided by its cell's sum K; a cell whose sum is 0 (no partner within reach) keeps a zero row."""
+    K = np.asarray(K, dtype=np.float64)
+    out = np.zeros_like(M)
+    live = K != 0.0
+    out[live] = M[live] / K[live, None]
+    return out
+
+
+def _normalize_applied(out, normalize):
+    if normalize:
+        if "to_A" in out:
+            out["to_A"] = _normalized_rows(out["to_A"], out["K_NA"])
+        if "to_B" in out:
+            out["to_B"] = _normalized_rows(out["to_B"], out["K_NB"])
+    return out
+
+
+def _applied_to_host(k, dev, normalize):
+    """HipKernels.assign_apply's dict of device tensors as apply_assignment's host result."""
+    keys = [q for q in ("to_A", "to_B", "K_NA", "K_NB") if q in dev]
+    out = {q: np.array(v, dtype=np.float64) for q, v in zip(keys, _rt._to_host(k, [dev[q] for q in keys]))}
+    return _normalize_applied(out, normalize)
+
+
+def _applied_from_coo(P, K_NA, K_NB, FA, FB, normalize):
+    """The same from the kept entries of sparse_calculation_mode: the returned coo_matrix times F, on the host."""
+    P = P.tocsr()
+    out = {}
+    if FB is not None:
+        out["to_A"], out["K_NA"] = np.asarray(P @ FB, dtype=np.float64), np.array(K_NA, dtype=np.float64)
+    if FA is not None:
+        out["to_B"] = np.asarray(P.T @ FA, dtype=np.float64)
+    out["K_NB"] = np.array(K_NB, dtype=np.float64)
+    return _normalize_applied(out, normalize)
+
+
+def _apply_argument(apply, NA, NB, who):
+    """``apply=`` of the loops validated (no device needed): None or dict(FA=, FB=, normalize=)."""
+    if apply is None:
+        return None
+    if not isinstance(apply, dict) or not set(apply) <= {"features_A", "features_B", "normalize"}:
+        raise ValueError(f"{who}: apply must be a dict with features_A and / or features_B and, optionally, normalize")
+    FA = _transfer_features(apply.get("features_A"), NA, "features_A", who)
+    FB = _transfer_features(apply.get("features_B"), NB, "features_B", who)
+    if FA is None and FB is None:
+        raise ValueError(f"{who}: apply needs features_A or features_B")
+    return dict(FA=FA, FB=FB, normalize=bool(apply.get("normalize", True)))
+
+
+def apply_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, features_A=None, features_B=None, normalize=True,
+                     dissimilarity, probability_type, probability_parameters, sigma2, alpha, SigmaDiag, gamma, samples_s,
+                     sigma2_variance=1.0, dtype: str = "float64", device=None, label_transfer=None):
+    """The assignment applied to cell features - what the reference's users form from the dense ``P`` that
+    ``Morpho_pairwise.run()`` returns - for the ``P`` that ``update_assignment`` would form from the same arguments, without
+    ``P`` (``mvf_assign_apply``): the tiles of the fused step feed a matrix product as they are formed, so two slices of
+    100 000 cells (a dense ``P`` of 80 GB) are served like any other size.
+
+    * ``features_B`` (NB, CB): ``to_A = P @ features_B`` (NA, CB) - expression or an embedding of slice B carried to the A
+      cells; with ``normalize`` each A cell's barycentre of its partners' rows.
+    * ``features_A`` (NA, CA): ``to_B = P.T @ features_A`` (NB, CA) - an annotation of slice A carried to the B cells.
+
+    A 1-D INTEGER ``features_*`` is a label vector and is expanded on the host to its one-hot matrix (n, max + 1):
+    ``to_B`` of ``features_A=labels_A`` is every B cell's class distribution.  Anything else must be a finite numeric (n, c >= 1)
+    array (``ValueError``); ``scipy.sparse`` features are ``NotImplementedError``.  One of the two must be given.
+
+    ``normalize=True`` divides every output row by its cell's sum of ``P`` - ``K_NA[i]`` for ``to_A``, ``K_NB[j]`` for ``to_B``;
+    a cell whose sum is 0 (a B cell out of reach of every A cell, an A cell whose weight is 0) gets a zero row.
+    ``normalize=False`` returns the raw products.
+
+    The other arguments and their errors are ``update_assignment``'s (``"label"`` layers with ``label_transfer`` included),
+    without ``return_P`` and the sparse pair.  ``dtype`` is the storage of the coordinates and of the prepared layer operands;
+    the features, the products and every sum are float64 in both modes.
+
+    Returns host float64 ``{"to_A", "K_NA"}`` (with ``features_B``), ``{"to_B"}`` (with ``features_A``) and ``"K_NB"``; an empty
+    side gives zeros of the right shape.  Two calls give equal bits."""
+    if dtype not in ("float32", "float64"):
+        raise ValueError("dtype must be 'float32' or 'float64'")
+    XA, XB, LA, LB, codes, table = _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
+                                                         probability_type, probability_parameters, False, label_transfer,
+                                                         who="apply_assignment")
+    NA, D = XA.shape
+    NB = len(XB)
+    FA = _transfer_features(features_A, NA, "features_A")
+    FB = _transfer_features(features_B, NB, "features_B")
+    if FA is None and FB is None:
+        raise ValueError("apply_assignment: features_A or features_B must be given")
+    al, sd = np.asarray(alpha, dtype=np.float64).reshape(-1), np.asarray(SigmaDiag, dtype=np.float64).reshape(-1)
+    if len(al) != NA or len(sd) != NA:
+        raise ValueError("alpha and SigmaDiag must be (NA,)")
+    sigma2, gamma, samples_s, sigma2_variance = float(sigma2), float(gamma), float(samples_s), float(sigma2_variance)
+    if NA == 0 or NB == 0:
+        out = {"K_NB": np.zeros(NB)}
+        if FB is not None:
+            out["to_A"], out["K_NA"] = np.zeros((NA, FB.shape[1])), np.zeros(NA)
+        if FA is not None:
+            out["to_B"] = np.zeros((NB, FA.shape[1]))
+        return out
+    model_mul = al * np.exp(-sd / sigma2)                                                   # morpho_class.py:1087
+    outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
+    k = _rt._make_kernels(device, dtype)
+    layers = _prepare_layers(k, LA, LB, codes, table)
+    dev = k.assign_apply(k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, float(outlier),
+                         features_B=None if FB is None else k.h2d(FB), features_A=None if FA is None else k.h2d(FA))
+    return _applied_to_host(k, dev, bool(normalize))
 
 
 def _nonrigid_solve(k, G, Gamma, reg, R):
@@ -685,7 +822,7 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
                    gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                    update_R=True, dtype: str = "float64", device=None, record=True, origin=None, SVI_mode=False, guidance=None,
                    sparse_calculation_mode=False, kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False,
-                   optimal_mapping=False):
+                   optimal_mapping=False, apply=None):
     """The iteration loop of Spateo's pairwise alignment on the MI355X: the non-SVI, dense-path body of
     ``Morpho_pairwise.run`` (``spateo/alignment/methods/morpho_class.py:280-294``: assignment -> gamma -> alpha -> non-rigid
     -> rigid -> ``XAHat`` -> sigma2) for ``max_iter`` iterations from the state ``_initialize_variational_variables`` sets
@@ -730,6 +867,11 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     ``P`` under both tie rules; ``mapping_from_best(best, XAHat, coordsB, keep_all)`` makes the reference's two mapping dicts
     of it.  Every other output keeps its bits.
 
+    ``apply=dict(features_A=, features_B=, normalize=True)`` (features as ``apply_assignment`` takes them, validated before
+    anything runs): the last iteration's assignment is followed by ``mvf_assign_apply`` on the same device operands and state,
+    and the result gains ``applied``, ``apply_assignment``'s dict for that assignment.  With ``sparse_calculation_mode`` the kept
+    entries are applied instead: the returned ``coo_matrix`` times the features, on the host.  Every other output keeps its bits.
+
     Not supported (``NotImplementedError``): ``SVI_mode`` (``morpho_iterate_svi`` runs it), ``guidance``,
     ``sparse_calculation_mode`` with ``sparse_top_k`` above 64 (the default, 1024, is the reference constructor's,
     ``morpho_class.py:140``), ``kernel_type="geodist"`` (anything but ``"euc"``), and what
@@ -744,9 +886,10 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
                            record, SVI_mode, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer)
     return_P = _return_P_argument(return_P, a["top_k"], len(a["XA"]), len(a["XB"]))
+    apply = _apply_argument(apply, len(a["XA"]), len(a["XB"]), "morpho_iterate")
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
                     partial_robust_level, nn_init_weight, update_R, dtype, device, record, return_P=return_P,
-                    best=bool(optimal_mapping))
+                    best=bool(optimal_mapping), apply=apply)
 
 
 def _return_P_argument(return_P, top_k, NA, NB_last):
@@ -764,11 +907,12 @@ def _return_P_argument(return_P, top_k, NA, NB_last):
 
 
 def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b, partial_robust_level,
-             nn_init_weight, update_R, dtype, device, record, svi=None, return_P=False, best=False):
+             nn_init_weight, update_R, dtype, device, record, svi=None, return_P=False, best=False, apply=None):
     """The loop of morpho_iterate and, with ``svi = dict(batch_size=, batch_perm= (int32, validated), return_mapping=)``, of
     morpho_iterate_svi, on validated arguments ``a`` (_iterate_arguments).  ``return_P``: the LAST assignment executed - the
     last iteration's, or the closing full one - runs through mvf_assign_dense.  ``best``: the same assignment is followed by
-    mvf_assign_best on its operands, before the iteration moves them on."""
+    mvf_assign_best on its operands, before the iteration moves them on.  ``apply`` (_apply_argument): and, on the dense
+    path, by mvf_assign_apply there; in the top-k mode the kept entries are applied on the host."""
     XA, XB, ctrl, org, top_k = a["XA"], a["XB"], a["ctrl"], a["origin"], a["top_k"]
     NA, D = XA.shape
     NB, m = len(XB), len(ctrl)
@@ -823,6 +967,10 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
     R3, t3 = _embed(R, t)
     k.align_transform(A64, V4, None, None, R3, t3, RnA=RnA, XAHat=XAHat)
     dev = blk = None
+    apply_dev = None
+    if apply is not None and top_k is None:                    # the features go up once, with the layers
+        FA_dev = None if apply["FA"] is None else k.h2d(apply["FA"])
+        FB_dev = None if apply["FB"] is None else k.h2d(apply["FB"])
     ph.mark("setup")
     closing = svi is not None and svi["return_mapping"]       # a full assignment follows the loop
     for it in range(int(max_iter)):
@@ -837,6 +985,9 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
         if best and not closing and it == int(max_iter) - 1:   # the last assignment executed: its operands as they are now
             best_dev = k.assign_best(xa4, xb4 if svi is None else xb4_b, layers if svi is None else layers_b, model_mul, sigma2,
                                      sigma2_variance, float(outlier))
+        if apply is not None and top_k is None and not closing and it == int(max_iter) - 1:   # (SVI: the closing one)
+            apply_dev = k.assign_apply(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier),
+                                       features_B=FB_dev, features_A=FA_dev)
         ph.mark("assign")
         if (it > nonrigid_start_iter or nonrigid) and svi is not None:
             nonrigid = True
@@ -916,6 +1067,9 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
         dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, dense=bool(return_P), top_k=top_k)
         if best:
             best_dev = k.assign_best(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier))
+        if apply is not None and top_k is None:
+            apply_dev = k.assign_apply(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier),
+                                       features_B=FB_dev, features_A=FA_dev)
         k.align_moments(A64, V4, dev["K_NA"], dev["K_NA_spatial"], dev["K_NA_sigma2"], SigmaDiag, dev["PXB"], B64, dev["K_NB"],
                         block, origin=org, extra=dev["scalars"])
         blk = np.array(k.to_host([block])[0], dtype=np.float64)
@@ -943,6 +1097,11 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
         out["P"] = np.array(k.to_host([dev["P"]], own_pinned=False)[0], dtype=np.float64)
     if best:
         out["best"] = _best_to_host(k, best_dev)
+    if apply is not None:
+        if top_k is None:
+            out["applied"] = _applied_to_host(k, apply_dev, apply["normalize"])
+        else:
+            out["applied"] = _applied_from_coo(out["P"], out["K_NA"], out["K_NB"], apply["FA"], apply["FB"], apply["normalize"])
     if record:
         out["history"] = {q: np.array(v) for q, v in history.items()}
     ph.mark("result")
@@ -997,7 +1156,7 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
                        gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                        update_R=True, dtype: str = "float64", device=None, record=True, origin=None, batch_size=None,
                        batch_perm=None, seed=None, return_mapping=False, guidance=None, sparse_calculation_mode=False,
-                       kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False, optimal_mapping=False):
+                       kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False, optimal_mapping=False, apply=None):
     """The SVI mode of the same loop - the reference constructor's default, ``SVI_mode=True``
     (``spateo/alignment/methods/morpho_class.py:136, 283-284, 749-760, 894-896``): every iteration sees ``batch_size`` cells
     of the B slice and blends what it learns into running averages with ``step_size = min(1, 10 / (iter + 1))``.
@@ -1034,6 +1193,9 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
     ``return_mapping=True`` and is followed by ``mvf_assign_best``; the result gains ``best`` as in ``morpho_iterate`` (``cols``
     has NB rows).  Every other output has the bits of the same call with ``return_mapping=True``.
 
+    ``apply=dict(...)`` as in ``morpho_iterate``: the closing full assignment runs in the same way and is followed by
+    ``mvf_assign_apply``; the result gains ``applied`` (``to_B`` has NB rows).
+
     Not supported (``NotImplementedError``): what ``morpho_iterate`` refuses but ``SVI_mode``.
 
     Returns ``morpho_iterate``'s dict - ``K_NA``, ``K_NB`` (``batch_size``,), ``K_NA_spatial``, ``K_NA_sigma2`` of the last
@@ -1044,12 +1206,13 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
                            record, False, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer)
     bs, perm = _svi_arguments(len(a["XB"]), batch_size, batch_perm, seed)
-    return_mapping = bool(return_mapping) or bool(optimal_mapping)
+    apply = _apply_argument(apply, len(a["XA"]), len(a["XB"]), "morpho_iterate_svi")
+    return_mapping = bool(return_mapping) or bool(optimal_mapping) or apply is not None
     return_P = _return_P_argument(return_P, a["top_k"], len(a["XA"]), len(a["XB"]) if return_mapping else bs)
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
                     partial_robust_level, nn_init_weight, update_R, dtype, device, record,
                     svi=dict(batch_size=bs, batch_perm=perm, return_mapping=bool(return_mapping)), return_P=return_P,
-                    best=bool(optimal_mapping))
+                    best=bool(optimal_mapping), apply=apply)
 
 
 # ---- the start state: what the reference computes in front of the loop (morpho_class.py:700-747, 771-820, 845-852, 898-1041) ----
