@@ -5,6 +5,8 @@ device tensors.  Nothing here computes on the host and nothing falls back to tor
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 import torch
 
@@ -16,6 +18,44 @@ _NP = {torch.float64: np.float64, torch.float32: np.float32, torch.int32: np.int
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+class Layer(NamedTuple):
+    """One prepared layer of the assignment step, the record every HipKernels method that takes layers reads (a plain
+    8-sequence in this order is accepted too).  A product layer: Xp (na, ld) / Yp (nb, ld) in the cell dtype and a (na,) /
+    b (nb,) float64 from assign_prepare.  A label layer (metric == _lib.ASSIGN_LABEL): Xp the (K, L) float64 table, Yp
+    None, a / b the labels of the A / B cells from assign_label_prepare, ld = L.  prob and param: the probability type
+    and its parameter (include/mvf.h)."""
+    Xp: object
+    Yp: object
+    a: object
+    b: object
+    ld: int
+    metric: int
+    prob: int
+    param: float
+
+    @property
+    def is_label(self):
+        return self.metric == _lib.ASSIGN_LABEL
+
+    def exchanged(self):
+        """The layer whose column statistics are this one's row statistics: Xp <-> Yp, a <-> b (na <-> nb is the caller's)."""
+        return self._replace(Xp=self.Yp, Yp=self.Xp, a=self.b, b=self.a)
+
+    def with_columns(self, Yp, b):
+        """The same layer over another set of B rows (an SVI batch)."""
+        return self._replace(Yp=Yp, b=b)
+
+
+def layer_array(layers):
+    """The layers as the C ABI takes them, (_lib.AssignLayer * max(len(layers), 1)), every field set; a missing Yp is NULL."""
+    arr = (_lib.AssignLayer * max(len(layers), 1))()
+    for s, t in zip(arr, layers):
+        L = Layer(*t)
+        s.Xp, s.Yp, s.a, s.b, s.ld = _ptr(L.Xp), _ptr(L.Yp), _ptr(L.a), _ptr(L.b), int(L.ld)
+        s.metric, s.prob, s.param = int(L.metric), int(L.prob), float(L.param)
+    return arr
 
 
 def is_sparse(layer):
@@ -701,31 +741,36 @@ class HipKernels:
                    "mvf_assign_label_prepare")
         return ab
 
+    def _assign_call(self, name, workspace_bytes, size_args, common, middle):
+        """One call of an assignment entry point: the head its kind shares, built from `common` = (xa4, xb4, layers,
+        model_mul, sigma2, sigma2_variance, spatial_outlier) (None: mvf_assign_layer_stats, which has none), the entry
+        point's own `middle` arguments, and the tail: a fresh workspace of `workspace_bytes(*size_args)`, dtype, stream."""
+        head = ()
+        if common is not None:
+            xa4, xb4, layers, model_mul, sigma2, sigma2_variance, spatial_outlier = common
+            head = (_ptr(xa4), xa4.shape[0], _ptr(xb4), xb4.shape[0], layer_array(layers), len(layers), _ptr(model_mul),
+                    float(sigma2), float(sigma2_variance), float(spatial_outlier))
+        need = int(workspace_bytes(*size_args))
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        _lib.check(getattr(self.lib, name)(*head, *middle, _ptr(ws), need, self.cdtype, self._stream()), name)
+
+    def _assign_outputs(self, na, nb):
+        """The outputs mvf_assign, _dense and _topk share, in the order the C ABI takes them."""
+        shapes = {"K_NA": (na,), "K_NB": (nb,), "K_NA_spatial": (na,), "K_NA_sigma2": (na,), "PXB": (na, 3), "scalars": (1,)}
+        return {q: self.empty(*s, dtype=torch.float64) for q, s in shapes.items()}
+
     @_on_device
     def assign(self, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, spatial_outlier, dense=False):
-        """The fused assignment step (mvf_assign / mvf_assign_dense).  layers: [(Xp, Yp, a, b, ld, metric, prob, param)]
-        of device tensors from assign_prepare; a label layer is (table (K, L) float64, None, labels A, labels B, L,
-        _lib.ASSIGN_LABEL, prob, param) with the labels from assign_label_prepare.  Returns device float64 tensors {K_NA, K_NB, K_NA_spatial, K_NA_sigma2,
-        PXB (na, 3), scalars (1,) = sum P_sigma2 d [, P (na, nb)]}."""
+        """The fused assignment step (mvf_assign / mvf_assign_dense).  layers: a list of `Layer` records (or plain
+        8-sequences in their order) of device tensors from assign_prepare / assign_label_prepare.  Returns device float64
+        tensors {K_NA, K_NB, K_NA_spatial, K_NA_sigma2, PXB (na, 3), scalars (1,) = sum P_sigma2 d [, P (na, nb)]}."""
         na, nb = xa4.shape[0], xb4.shape[0]
-        f64 = torch.float64
-        arr = (_lib.AssignLayer * len(layers))()
-        for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, layers):
-            s.Xp, s.Yp, s.a, s.b, s.ld = _ptr(Xp), _ptr(Yp), _ptr(a), _ptr(b), int(ld)
-            s.metric, s.prob, s.param = int(metric), int(prob), float(param)
-        out = {"K_NA": self.empty(na, dtype=f64), "K_NB": self.empty(nb, dtype=f64), "K_NA_spatial": self.empty(na, dtype=f64),
-               "K_NA_sigma2": self.empty(na, dtype=f64), "PXB": self.empty(na, 3, dtype=f64), "scalars": self.empty(1, dtype=f64)}
-        need = int(self.lib.mvf_assign_workspace_bytes(na, nb))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        head = (_ptr(xa4), na, _ptr(xb4), nb, arr, len(layers), _ptr(model_mul), float(sigma2), float(sigma2_variance),
-                float(spatial_outlier), _ptr(out["K_NA"]), _ptr(out["K_NB"]), _ptr(out["K_NA_spatial"]),
-                _ptr(out["K_NA_sigma2"]), _ptr(out["PXB"]), _ptr(out["scalars"]))
-        tail = (_ptr(ws), need, self.cdtype, self._stream())
+        out = self._assign_outputs(na, nb)
         if dense:
-            out["P"] = self.empty(na, nb, dtype=f64)
-            _lib.check(self.lib.mvf_assign_dense(*head, _ptr(out["P"]), *tail), "mvf_assign_dense")
-        else:
-            _lib.check(self.lib.mvf_assign(*head, *tail), "mvf_assign")
+            out["P"] = self.empty(na, nb, dtype=torch.float64)
+        self._assign_call("mvf_assign_dense" if dense else "mvf_assign", self.lib.mvf_assign_workspace_bytes, (na, nb),
+                          (xa4, xb4, layers, model_mul, sigma2, sigma2_variance, spatial_outlier),
+                          [_ptr(t) for t in out.values()])   # (P comes last in the ABI too)
         return out
 
     @_on_device
@@ -737,21 +782,11 @@ class HipKernels:
         na, nb = xa4.shape[0], xb4.shape[0]
         k = int(k)
         ke = min(k, na)
-        f64 = torch.float64
-        arr = (_lib.AssignLayer * len(layers))()
-        for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, layers):
-            s.Xp, s.Yp, s.a, s.b, s.ld = _ptr(Xp), _ptr(Yp), _ptr(a), _ptr(b), int(ld)
-            s.metric, s.prob, s.param = int(metric), int(prob), float(param)
-        out = {"K_NA": self.empty(na, dtype=f64), "K_NB": self.empty(nb, dtype=f64), "K_NA_spatial": self.empty(na, dtype=f64),
-               "K_NA_sigma2": self.empty(na, dtype=f64), "PXB": self.empty(na, 3, dtype=f64), "scalars": self.empty(1, dtype=f64),
-               "rows": self.empty(nb, ke, dtype=torch.int32), "vals": self.empty(nb, ke, dtype=f64)}
-        need = int(self.lib.mvf_assign_topk_workspace_bytes(na, nb, k))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.mvf_assign_topk(_ptr(xa4), na, _ptr(xb4), nb, arr, len(layers), _ptr(model_mul), float(sigma2),
-                                            float(sigma2_variance), float(spatial_outlier), k, _ptr(out["K_NA"]),
-                                            _ptr(out["K_NB"]), _ptr(out["K_NA_spatial"]), _ptr(out["K_NA_sigma2"]),
-                                            _ptr(out["PXB"]), _ptr(out["scalars"]), _ptr(out["rows"]), _ptr(out["vals"]),
-                                            _ptr(ws), need, self.cdtype, self._stream()), "mvf_assign_topk")
+        out = self._assign_outputs(na, nb)
+        out["rows"], out["vals"] = self.empty(nb, ke, dtype=torch.int32), self.empty(nb, ke, dtype=torch.float64)
+        self._assign_call("mvf_assign_topk", self.lib.mvf_assign_topk_workspace_bytes, (na, nb, k),
+                          (xa4, xb4, layers, model_mul, sigma2, sigma2_variance, spatial_outlier),
+                          [k] + [_ptr(t) for t in out.values()])
         return out
 
     @_on_device
@@ -763,21 +798,14 @@ class HipKernels:
         / ``cols=False`` skips that direction (its two entries are absent); one of them must stay."""
         na, nb = xa4.shape[0], xb4.shape[0]
         f64 = torch.float64
-        arr = (_lib.AssignLayer * len(layers))()
-        for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, layers):
-            s.Xp, s.Yp, s.a, s.b, s.ld = _ptr(Xp), _ptr(Yp), _ptr(a), _ptr(b), int(ld)
-            s.metric, s.prob, s.param = int(metric), int(prob), float(param)
         out = {}
         if rows:
             out["rows"], out["row_values"] = self.empty(na, 2, dtype=torch.int32), self.empty(na, dtype=f64)
         if cols:
             out["cols"], out["col_values"] = self.empty(nb, 2, dtype=torch.int32), self.empty(nb, dtype=f64)
-        need = int(self.lib.mvf_assign_best_workspace_bytes(na, nb))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.mvf_assign_best(_ptr(xa4), na, _ptr(xb4), nb, arr, len(layers), _ptr(model_mul), float(sigma2),
-                                            float(sigma2_variance), float(spatial_outlier), _ptr(out.get("rows")),
-                                            _ptr(out.get("row_values")), _ptr(out.get("cols")), _ptr(out.get("col_values")),
-                                            _ptr(ws), need, self.cdtype, self._stream()), "mvf_assign_best")
+        self._assign_call("mvf_assign_best", self.lib.mvf_assign_best_workspace_bytes, (na, nb),
+                          (xa4, xb4, layers, model_mul, sigma2, sigma2_variance, spatial_outlier),
+                          [_ptr(out.get(q)) for q in ("rows", "row_values", "cols", "col_values")])
         return out
 
     @_on_device
@@ -798,13 +826,8 @@ class HipKernels:
             if F.dtype != f64 or F.dim() != 2 or F.shape[0] != n or F.shape[1] < 1 or (n > 0 and F.stride(1) != 1) \
                     or (n > 1 and F.stride(0) < F.shape[1]):
                 raise ValueError(f"assign_apply: {name} must be a float64 ({n}, c >= 1) tensor with contiguous rows")
-        arr = (_lib.AssignLayer * len(layers))()
-        for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, layers):
-            s.Xp, s.Yp, s.a, s.b, s.ld = _ptr(Xp), _ptr(Yp), _ptr(a), _ptr(b), int(ld)
-            s.metric, s.prob, s.param = int(metric), int(prob), float(param)
         out = {}
-        cb = ca = 0
-        ldb = lda = 0
+        cb = ca = ldb = lda = 0
         if features_B is not None:
             cb = int(features_B.shape[1])
             ldb = int(features_B.stride(0)) if nb > 1 else cb
@@ -817,38 +840,28 @@ class HipKernels:
             out["to_B"] = self.empty(nb, ca, dtype=f64)
         if sums:
             out["K_NB"] = self.empty(nb, dtype=f64)
-        need = int(self.lib.mvf_assign_apply_workspace_bytes(na, nb, cb, ca))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.mvf_assign_apply(_ptr(xa4), na, _ptr(xb4), nb, arr, len(layers), _ptr(model_mul), float(sigma2),
-                                             float(sigma2_variance), float(spatial_outlier), _ptr(features_B), cb, ldb,
-                                             _ptr(out.get("to_A")), _ptr(features_A), ca, lda, _ptr(out.get("to_B")),
-                                             _ptr(out.get("K_NA")), _ptr(out.get("K_NB")), _ptr(ws), need, self.cdtype,
-                                             self._stream()), "mvf_assign_apply")
+        self._assign_call("mvf_assign_apply", self.lib.mvf_assign_apply_workspace_bytes, (na, nb, cb, ca),
+                          (xa4, xb4, layers, model_mul, sigma2, sigma2_variance, spatial_outlier),
+                          (_ptr(features_B), cb, ldb, _ptr(out.get("to_A")), _ptr(features_A), ca, lda, _ptr(out.get("to_B")),
+                           _ptr(out.get("K_NA")), _ptr(out.get("K_NB"))))
         return out
 
     @_on_device
     def assign_layer_stats(self, layer, na, nb, k=0):
-        """Column statistics of one layer's (na, nb) distance matrix (mvf_assign_layer_stats).  layer: one tuple as assign
+        """Column statistics of one layer's (na, nb) distance matrix (mvf_assign_layer_stats).  layer: one `Layer` as assign
         takes them (prob and param are not read).  Returns device tensors {cmin (nb,) float64, sums (2,) float64 = sum d,
         sum d^2} and, for k > 0, rows (nb, k_eff) int32 / vals (nb, k_eff) float64, k_eff = min(k, na): column j's smallest
-        entries, value ascending, row ascending.  The statistics of the rows: the same call on the exchanged layer
-        (Yp, Xp, b, a, ...) with na and nb exchanged."""
+        entries, value ascending, row ascending.  The statistics of the rows: the same call on `layer.exchanged()` with na
+        and nb exchanged."""
         na, nb, k = int(na), int(nb), int(k)
         ke = min(k, na)
         f64 = torch.float64
-        arr = (_lib.AssignLayer * 1)()
-        Xp, Yp, a, b, ld, metric, prob, param = layer
-        s = arr[0]
-        s.Xp, s.Yp, s.a, s.b, s.ld = _ptr(Xp), _ptr(Yp), _ptr(a), _ptr(b), int(ld)
-        s.metric, s.prob, s.param = int(metric), int(prob), float(param)
         out = {"cmin": self.empty(nb, dtype=f64), "sums": self.empty(2, dtype=f64)}
         if k > 0:
             out["rows"], out["vals"] = self.empty(nb, ke, dtype=torch.int32), self.empty(nb, ke, dtype=f64)
-        need = int(self.lib.mvf_assign_layer_stats_workspace_bytes(na, nb, k))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.mvf_assign_layer_stats(arr, na, nb, k, _ptr(out["cmin"]), _ptr(out.get("rows")), _ptr(out.get("vals")),
-                                                   _ptr(out["sums"]), _ptr(ws), need, self.cdtype, self._stream()),
-                   "mvf_assign_layer_stats")
+        self._assign_call("mvf_assign_layer_stats", self.lib.mvf_assign_layer_stats_workspace_bytes, (na, nb, k), None,
+                          (layer_array([layer]), na, nb, k, _ptr(out["cmin"]), _ptr(out.get("rows")), _ptr(out.get("vals")),
+                           _ptr(out["sums"])))
         return out
 
     # ---- the O(N) glue of the alignment loop (mvf_align.hip): device tensors in, device tensors out ----
@@ -895,20 +908,18 @@ class HipKernels:
             raise ValueError("align_gather: perm must be int32 (nb,) and B (nb, 3)")
         if xb4_out.shape[0] < bs or B_out.shape[0] < bs or len(Yp_out) != len(layers) or len(b_out) != len(layers):
             raise ValueError("align_gather: the batch buffers do not fit the batch")
-        arr = (_lib.AssignLayer * max(len(layers), 1))()
-        for s, (_, Yp, _, b, ld, metric, *_), Yo, bo in zip(arr, layers, Yp_out, b_out):
+        for (_, Yp, _, b, ld, metric, *_), Yo, bo in zip(layers, Yp_out, b_out):
             if metric == _lib.ASSIGN_LABEL:     # only the B labels (b) are gathered: the table has no rows per cell
                 if b.shape != (nb,) or bo.shape[0] < bs:
                     raise ValueError("align_gather: a layer's buffers do not fit")
             elif Yp.shape != (nb, ld) or b.shape != (nb,) or Yo.shape[0] < bs or Yo.shape[1] != ld or bo.shape[0] < bs:
                 raise ValueError("align_gather: a layer's buffers do not fit")
-            s.Yp, s.b, s.ld, s.metric = _ptr(Yp), _ptr(b), int(ld), int(metric)
         import ctypes
 
         vp = ctypes.c_void_p * max(len(layers), 1)
         _lib.check(self.lib.mvf_align_gather(_ptr(perm), nb, int(start), int(bs), _ptr(xb4), _ptr(xb4_out), _ptr(B), _ptr(B_out),
-                                             arr, len(layers), vp(*[_ptr(t) for t in Yp_out]), vp(*[_ptr(t) for t in b_out]),
-                                             self.cdtype, self._stream()), "mvf_align_gather")
+                                             layer_array(layers), len(layers), vp(*[_ptr(t) for t in Yp_out]),
+                                             vp(*[_ptr(t) for t in b_out]), self.cdtype, self._stream()), "mvf_align_gather")
 
     @_on_device
     def align_alpha_svi(self, kappa, K_NA_spatial, SigmaDiag, Sp_spatial, sigma2, step, alpha, model_mul):

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from . import _runtime as _rt
-from ._kernels import is_sparse
+from ._kernels import Layer, is_sparse
 from .engine import SparseVFCEngine, _consistent_K
 from .vectorfield import vector_field_function
 
@@ -152,27 +152,51 @@ def _spatial_outlier(sigma2, gamma, samples_s, NA, D):
 
 def _prepare_layers(k, LA, LB, codes, table=None):
     """Upload and prepare both sides of every layer (mvf_assign_prepare; a label layer: mvf_assign_label_prepare and the
-    one float64 table its kind shares): the operands no iteration changes."""
+    one float64 table its kind shares): the operands no iteration changes, one `Layer` record each."""
     layers = []
     T = None
     for A, B, (metric, prob, param) in zip(LA, LB, codes):
         if metric == _lib.ASSIGN_LABEL:
             T = k.h2d(table) if T is None else T
             K, L = table.shape
-            layers.append((T, None, k.assign_label_prepare(A, K), k.assign_label_prepare(B, L), L, metric, prob, param))
+            layers.append(Layer(T, None, k.assign_label_prepare(A, K), k.assign_label_prepare(B, L), L, metric, prob, param))
             continue
-        Xp, a, ld = k.assign_prepare(A, metric, 0)
-        Yp, b, _ = k.assign_prepare(B, metric, 1)
-        layers.append((Xp, Yp, a, b, ld, metric, prob, param))
+        layers.append(_product_layer(k, A, B, metric, prob, param))
     return layers
 
 
-def _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, dense=False, top_k=None):
-    """The device-resident body of update_assignment (and of every iteration of morpho_iterate): device tensors in, the
-    dict of device tensors of HipKernels.assign - with ``top_k`` (sparse_calculation_mode) of HipKernels.assign_topk - out."""
-    if top_k is not None:
-        return k.assign_topk(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier), top_k)
-    return k.assign(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier), dense=dense)
+def _assignment_stage(who, XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type, probability_parameters,
+                      sigma2, alpha, SigmaDiag, gamma, samples_s, sigma2_variance, dtype, label_transfer, return_P=False,
+                      features=None):
+    """The prelude update_assignment, optimal_mapping and apply_assignment share, on the host: ``dtype``, the arrays and layers
+    (_assignment_arguments, refusals under the name ``who``), ``features`` = (features_A, features_B) where the stage takes
+    them, ``alpha`` / ``SigmaDiag``, the scalars.  Returns (XA, XB, FA, FB, upload); nothing touches the device before
+    ``upload(device)``: the layers prepared, then XAHat, coordsB and model_mul uploaded, it returns (k, the seven arguments
+    every assignment entry point of HipKernels takes)."""
+    if dtype not in ("float32", "float64"):
+        raise ValueError("dtype must be 'float32' or 'float64'")
+    XA, XB, LA, LB, codes, table = _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
+                                                         probability_type, probability_parameters, return_P, label_transfer,
+                                                         who=who)
+    NA, D = XA.shape
+    FA = FB = None
+    if features is not None:
+        FA, FB = _transfer_features(features[0], NA, "features_A"), _transfer_features(features[1], len(XB), "features_B")
+        if FA is None and FB is None:
+            raise ValueError(f"{who}: features_A or features_B must be given")
+    al, sd = np.asarray(alpha, dtype=np.float64).reshape(-1), np.asarray(SigmaDiag, dtype=np.float64).reshape(-1)
+    if len(al) != NA or len(sd) != NA:
+        raise ValueError("alpha and SigmaDiag must be (NA,)")
+    sigma2, gamma, samples_s, sigma2_variance = float(sigma2), float(gamma), float(samples_s), float(sigma2_variance)
+
+    def upload(device):
+        model_mul = al * np.exp(-sd / sigma2)                                               # morpho_class.py:1087
+        outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
+        k = _rt._make_kernels(device, dtype)
+        layers = _prepare_layers(k, LA, LB, codes, table)
+        return k, (k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, outlier)
+
+    return XA, XB, FA, FB, upload
 
 
 def _coo_from_lists(rows, vals, NA):
@@ -236,33 +260,26 @@ def update_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilari
     * ``update_nonrigid``'s ``PXB_term`` is ``PXB - RnA * K_NA[:, None]``;
     * ``_update_rigid``'s ``XA_hat^T P XB_hat`` (``:1300-1408``) is ``XA_hat^T PXB - (XA_hat^T K_NA) mu_XB``, from
       ``PXB`` and ``K_NA``."""
-    if dtype not in ("float32", "float64"):
+    if dtype not in ("float32", "float64"):                   # (before the stage's own check: dtype is refused first)
         raise ValueError("dtype must be 'float32' or 'float64'")
     top_k = _sparse_top_k(sparse_calculation_mode, sparse_top_k, return_P)
-    XA, XB, LA, LB, codes, table = _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
-                                                         probability_type, probability_parameters, return_P, label_transfer)
-    NA, D = XA.shape
-    al, sd = np.asarray(alpha, dtype=np.float64).reshape(-1), np.asarray(SigmaDiag, dtype=np.float64).reshape(-1)
-    if len(al) != NA or len(sd) != NA:
-        raise ValueError("alpha and SigmaDiag must be (NA,)")
-    sigma2, gamma, samples_s, sigma2_variance = float(sigma2), float(gamma), float(samples_s), float(sigma2_variance)
+    XA, XB, _, _, upload = _assignment_stage("update_assignment", XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
+                                             probability_type, probability_parameters, sigma2, alpha, SigmaDiag, gamma,
+                                             samples_s, sigma2_variance, dtype, label_transfer, return_P=return_P)
+    (NA, D), NB = XA.shape, len(XB)
     names = ("K_NA", "K_NB", "K_NA_spatial", "K_NA_sigma2")
-    if NA == 0 or len(XB) == 0:
-        out = {q: np.zeros(len(XB) if q == "K_NB" else NA) for q in names}
+    if NA == 0 or NB == 0:
+        out = {q: np.zeros(NB if q == "K_NB" else NA) for q in names}
         out.update(Sp=0.0, Sp_spatial=0.0, Sp_sigma2=0.0, sigma2_related=float("nan"), PXB=np.zeros((NA, D)))
         if return_P:
-            out["P"] = np.zeros((NA, len(XB)))
+            out["P"] = np.zeros((NA, NB))
         if top_k is not None:
             ke = min(top_k, NA)
-            out["topk_rows"], out["topk_values"] = np.zeros((len(XB), ke), dtype=np.int32), np.zeros((len(XB), ke))
+            out["topk_rows"], out["topk_values"] = np.zeros((NB, ke), dtype=np.int32), np.zeros((NB, ke))
             out["P"] = _coo_from_lists(out["topk_rows"], out["topk_values"], NA)
         return out
-    model_mul = al * np.exp(-sd / sigma2)                                                   # morpho_class.py:1087
-    outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
-    k = _rt._make_kernels(device, dtype)
-    layers = _prepare_layers(k, LA, LB, codes, table)
-    dev = _assign_device(k, k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, outlier,
-                         dense=bool(return_P), top_k=top_k)
+    k, common = upload(device)
+    dev = k.assign_topk(*common, top_k) if top_k is not None else k.assign(*common, dense=bool(return_P))
     keys = list(names) + ["PXB", "scalars"] + (["P"] if return_P else []) + (["rows", "vals"] if top_k is not None else [])
     host = dict(zip(keys, _rt._to_host(k, [dev[q] for q in keys])))
     out = {q: np.array(host[q], dtype=np.float64) for q in names}
@@ -351,24 +368,13 @@ def optimal_mapping(XAHat, coordsB, exp_layers_A, exp_layers_B, *, dissimilarity
     index and there is ONE per cell also for ``keep_all=True``.  The reference appends the cells with tied maxima at the end
     of its index arrays and, with ``keep_all=True``, returns every tied pair; its ``mapping_aligned_coords`` then sorts and
     drops the duplicates, which is what is returned here."""
-    if dtype not in ("float32", "float64"):
-        raise ValueError("dtype must be 'float32' or 'float64'")
-    XA, XB, LA, LB, codes, table = _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
-                                                         probability_type, probability_parameters, False, label_transfer,
-                                                         who="optimal_mapping")
-    NA, D = XA.shape
-    al, sd = np.asarray(alpha, dtype=np.float64).reshape(-1), np.asarray(SigmaDiag, dtype=np.float64).reshape(-1)
-    if len(al) != NA or len(sd) != NA:
-        raise ValueError("alpha and SigmaDiag must be (NA,)")
-    sigma2, gamma, samples_s, sigma2_variance = float(sigma2), float(gamma), float(samples_s), float(sigma2_variance)
-    if NA == 0 or len(XB) == 0:
-        return _empty_mapping(D), _empty_mapping(D)
-    model_mul = al * np.exp(-sd / sigma2)                                                   # morpho_class.py:1087
-    outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
-    k = _rt._make_kernels(device, dtype)
-    layers = _prepare_layers(k, LA, LB, codes, table)
-    dev = k.assign_best(k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, float(outlier))
-    return mapping_from_best(_best_to_host(k, dev), XA, XB, keep_all)
+    XA, XB, _, _, upload = _assignment_stage("optimal_mapping", XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
+                                             probability_type, probability_parameters, sigma2, alpha, SigmaDiag, gamma,
+                                             samples_s, sigma2_variance, dtype, label_transfer)
+    if len(XA) == 0 or len(XB) == 0:
+        return _empty_mapping(XA.shape[1]), _empty_mapping(XA.shape[1])
+    k, common = upload(device)
+    return mapping_from_best(_best_to_host(k, k.assign_best(*common)), XA, XB, keep_all)
 
 
 def _transfer_features(features, n, name, who="apply_assignment"):
@@ -476,21 +482,11 @@ def apply_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, features_A=N
 
     Returns host float64 ``{"to_A", "K_NA"}`` (with ``features_B``), ``{"to_B"}`` (with ``features_A``) and ``"K_NB"``; an empty
     side gives zeros of the right shape.  Two calls give equal bits."""
-    if dtype not in ("float32", "float64"):
-        raise ValueError("dtype must be 'float32' or 'float64'")
-    XA, XB, LA, LB, codes, table = _assignment_arguments(XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
-                                                         probability_type, probability_parameters, False, label_transfer,
-                                                         who="apply_assignment")
-    NA, D = XA.shape
-    NB = len(XB)
-    FA = _transfer_features(features_A, NA, "features_A")
-    FB = _transfer_features(features_B, NB, "features_B")
-    if FA is None and FB is None:
-        raise ValueError("apply_assignment: features_A or features_B must be given")
-    al, sd = np.asarray(alpha, dtype=np.float64).reshape(-1), np.asarray(SigmaDiag, dtype=np.float64).reshape(-1)
-    if len(al) != NA or len(sd) != NA:
-        raise ValueError("alpha and SigmaDiag must be (NA,)")
-    sigma2, gamma, samples_s, sigma2_variance = float(sigma2), float(gamma), float(samples_s), float(sigma2_variance)
+    XA, XB, FA, FB, upload = _assignment_stage("apply_assignment", XAHat, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
+                                               probability_type, probability_parameters, sigma2, alpha, SigmaDiag, gamma,
+                                               samples_s, sigma2_variance, dtype, label_transfer,
+                                               features=(features_A, features_B))
+    NA, NB = len(XA), len(XB)
     if NA == 0 or NB == 0:
         out = {"K_NB": np.zeros(NB)}
         if FB is not None:
@@ -498,12 +494,8 @@ def apply_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, features_A=N
         if FA is not None:
             out["to_B"] = np.zeros((NB, FA.shape[1]))
         return out
-    model_mul = al * np.exp(-sd / sigma2)                                                   # morpho_class.py:1087
-    outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
-    k = _rt._make_kernels(device, dtype)
-    layers = _prepare_layers(k, LA, LB, codes, table)
-    dev = k.assign_apply(k.to_x4(XA), k.to_x4(XB), layers, k.h2d(model_mul), sigma2, sigma2_variance, float(outlier),
-                         features_B=None if FB is None else k.h2d(FB), features_A=None if FA is None else k.h2d(FA))
+    k, common = upload(device)
+    dev = k.assign_apply(*common, features_B=None if FB is None else k.h2d(FB), features_A=None if FA is None else k.h2d(FA))
     return _applied_to_host(k, dev, bool(normalize))
 
 
@@ -944,16 +936,18 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
         perm = k.h2d(svi["batch_perm"])
         xb4_b, B64_b = k.empty(bs, 4), k.empty(bs, 3, dtype=f64)
         # (a label layer has no rows per B cell: its batch is the gathered labels b alone)
-        Yp_b = [None if L[5] == _lib.ASSIGN_LABEL else k.empty(bs, L[4]) for L in layers]
+        Yp_b = [None if L.is_label else k.empty(bs, L.ld) for L in layers]
         b_b = [k.empty(bs, dtype=f64) for L in layers]
-        layers_b = [(L[0], Yb, L[2], bb) + tuple(L[4:]) for L, Yb, bb in zip(layers, Yp_b, b_b)]
+        layers_b = [L.with_columns(Yb, bb) for L, Yb, bb in zip(layers, Yp_b, b_b)]
         PXB_term.zero_()                                       # the running PXB_term and SigmaInv start at 0 (:759-760)
         S_run = k.zeros(m, m, dtype=f64)
         ones = torch.ones(NA, dtype=Pw_dtype, device=k.device)
         Sp_run = Sp_spatial_run = Sp_sigma2_run = 0.0
-        step = 1.0
+        xb_cur, layers_cur, B_cur = xb4_b, layers_b, B64_b     # the B operands of every iteration: the batch buffers
     else:
         NB_eff = NB
+        xb_cur, layers_cur, B_cur = xb4, layers, B64
+    step = 1.0
     G, Rhs = k.zeros(m, m, dtype=f64), k.zeros(m, 3, dtype=f64)
     Coff = k.zeros(m, 3, dtype=f64)
     block = k.empty(_lib.ALIGN_MOMENT_DOUBLES, dtype=f64)
@@ -967,58 +961,64 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
     R3, t3 = _embed(R, t)
     k.align_transform(A64, V4, None, None, R3, t3, RnA=RnA, XAHat=XAHat)
     dev = blk = None
-    apply_dev = None
+    extras = {}                                                # best / applied of the last assignment executed
     if apply is not None and top_k is None:                    # the features go up once, with the layers
         FA_dev = None if apply["FA"] is None else k.h2d(apply["FA"])
         FB_dev = None if apply["FB"] is None else k.h2d(apply["FB"])
+
+    def assignment(xb, lay, last):
+        """One assignment on the B operands given, at the state as it is now; the ``last`` one executed carries the extras."""
+        common = (xa4, xb, lay, model_mul, sigma2, sigma2_variance, _spatial_outlier(sigma2, gamma, samples_s, NA, D))
+        dev = k.assign_topk(*common, top_k) if top_k is not None else k.assign(*common, dense=last and bool(return_P))
+        if last and best:                                      # on the operands of the assignment itself
+            extras["best"] = k.assign_best(*common)
+        if last and apply is not None and top_k is None:
+            # the features cover the WHOLE B slice, never a batch: the SVI loop applies after its closing full assignment
+            extras["applied"] = k.assign_apply(xa4, xb4, layers, *common[3:], features_B=FB_dev, features_A=FA_dev)
+        return dev
+
+    def moments(dev, B):
+        """The block of reductions of an assignment over the B rows it saw: the one host read, 64 float64, page-locked."""
+        k.align_moments(A64, V4, dev["K_NA"], dev["K_NA_spatial"], dev["K_NA_sigma2"], SigmaDiag, dev["PXB"], B, dev["K_NB"],
+                        block, origin=org, extra=dev["scalars"])
+        return np.array(k.to_host([block])[0], dtype=np.float64)
+
+    def field_and_variance(Coff, rcond, lowrank):
+        """After the solve, in both modes: V4 = U Coff, SigmaDiag = sigma2 diag(U pinv(SigmaInv) U^T)  (:1296).  (Coff, V4)."""
+        V4, _ = k.apply(x4c, c4, beta, Coff)
+        diag = k.pinv_diag(x4c, c4, beta, rcond=rcond, lowrank=lowrank)
+        k.lincomb3(SigmaDiag, sigma2, diag)
+        return Coff, V4
+
     ph.mark("setup")
     closing = svi is not None and svi["return_mapping"]       # a full assignment follows the loop
     for it in range(int(max_iter)):
-        outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
-        dense = bool(return_P) and not closing and it == int(max_iter) - 1
         if svi is not None:
             step = min(1.0, 10.0 / (it + 1.0))                 # :894, SVI_deacy = 10
             k.align_gather(perm, (-it * bs) % NB, bs, xb4, B64, layers, xb4_b, B64_b, Yp_b, b_b)
-            dev = _assign_device(k, xa4, xb4_b, layers_b, model_mul, sigma2, sigma2_variance, outlier, dense=dense, top_k=top_k)
-        else:
-            dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, dense=dense, top_k=top_k)
-        if best and not closing and it == int(max_iter) - 1:   # the last assignment executed: its operands as they are now
-            best_dev = k.assign_best(xa4, xb4 if svi is None else xb4_b, layers if svi is None else layers_b, model_mul, sigma2,
-                                     sigma2_variance, float(outlier))
-        if apply is not None and top_k is None and not closing and it == int(max_iter) - 1:   # (SVI: the closing one)
-            apply_dev = k.assign_apply(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier),
-                                       features_B=FB_dev, features_A=FA_dev)
+        dev = assignment(xb_cur, layers_cur, last=not closing and it == int(max_iter) - 1)
         ph.mark("assign")
-        if (it > nonrigid_start_iter or nonrigid) and svi is not None:
+        if it > nonrigid_start_iter or nonrigid:               # morpho_class.py:289
             nonrigid = True
-            # PXB_term <- step (P coordsB[batch] - RnA K_NA) + (1 - step) PXB_term; rows without a partner in THIS batch keep the
-            # earlier batches' share, so the right-hand side is U^T PXB_term with unit weights (:1270-1279)
-            k.align_transform_svi(RnA, dev["PXB"], dev["K_NA"], step, PXB_term, Y4, Pw, origin=org)
-            k.gram(x4c, Pw, Y4, c4, beta, G, Rhs, tiles_only=True)
-            k.gram(x4c, ones, Y4, c4, beta, G, Rhs, rhs_only=True)
-            # SigmaInv <- step (sigma2 lambdaVF Gamma + U^T diag(K_NA) U) + (1 - step) SigmaInv (:1273): G takes the blend
-            # without the regulariser, which enters the solve as (step sigma2 lambdaVF) Gamma and the stored value after it
-            k.lincomb3(G, step, G, 1.0 - step, S_run)
-            Coff, rcond, lowrank = _nonrigid_solve(k, G, Gamma, step * sigma2 * lambdaVF, Rhs)
-            k.lincomb3(S_run, 1.0, G, step * sigma2 * lambdaVF, Gamma)
-            V4, _ = k.apply(x4c, c4, beta, Coff)
-            diag = k.pinv_diag(x4c, c4, beta, rcond=rcond, lowrank=lowrank)
-            k.lincomb3(SigmaDiag, sigma2, diag)
+            if svi is not None:
+                # PXB_term <- step (P coordsB[batch] - RnA K_NA) + (1 - step) PXB_term; rows without a partner in THIS batch keep
+                # the earlier batches' share, so the right-hand side is U^T PXB_term with unit weights (:1270-1279)
+                k.align_transform_svi(RnA, dev["PXB"], dev["K_NA"], step, PXB_term, Y4, Pw, origin=org)
+                k.gram(x4c, Pw, Y4, c4, beta, G, Rhs, tiles_only=True)
+                k.gram(x4c, ones, Y4, c4, beta, G, Rhs, rhs_only=True)
+                # SigmaInv <- step (sigma2 lambdaVF Gamma + U^T diag(K_NA) U) + (1 - step) SigmaInv (:1273): G takes the blend
+                # without the regulariser, which enters the solve as (step sigma2 lambdaVF) Gamma and the stored value after it
+                k.lincomb3(G, step, G, 1.0 - step, S_run)
+                solved = _nonrigid_solve(k, G, Gamma, step * sigma2 * lambdaVF, Rhs)
+                k.lincomb3(S_run, 1.0, G, step * sigma2 * lambdaVF, Gamma)
+            else:
+                # PXB_term = P coordsB - RnA K_NA with the RnA of the previous iteration's R, t; Y = PXB_term / K_NA; Pw = K_NA
+                k.align_transform(A64, V4, dev["PXB"], dev["K_NA"], R3, t3, origin=org, PXB_term=PXB_term, Y4=Y4, Pw=Pw)
+                k.gram(x4c, Pw, Y4, c4, beta, G, Rhs)
+                solved = _nonrigid_solve(k, G, Gamma, sigma2 * lambdaVF, Rhs)
+            Coff, V4 = field_and_variance(*solved)
             ph.mark("nonrigid")
-        elif it > nonrigid_start_iter or nonrigid:             # morpho_class.py:289
-            nonrigid = True
-            # PXB_term = P coordsB - RnA K_NA with the RnA of the previous iteration's R, t; Y = PXB_term / K_NA; Pw = K_NA
-            k.align_transform(A64, V4, dev["PXB"], dev["K_NA"], R3, t3, origin=org, PXB_term=PXB_term, Y4=Y4, Pw=Pw)
-            k.gram(x4c, Pw, Y4, c4, beta, G, Rhs)
-            Coff, rcond, lowrank = _nonrigid_solve(k, G, Gamma, sigma2 * lambdaVF, Rhs)
-            V4, _ = k.apply(x4c, c4, beta, Coff)
-            diag = k.pinv_diag(x4c, c4, beta, rcond=rcond, lowrank=lowrank)
-            k.lincomb3(SigmaDiag, sigma2, diag)                # SigmaDiag = sigma2 diag(U pinv(SigmaInv) U^T)  (:1296)
-            ph.mark("nonrigid")
-        k.align_moments(A64, V4, dev["K_NA"], dev["K_NA_spatial"], dev["K_NA_sigma2"], SigmaDiag, dev["PXB"],
-                        B64 if svi is None else B64_b, dev["K_NB"], block, origin=org, extra=dev["scalars"])
-        (blk,) = k.to_host([block])                            # the iteration's one read: 64 float64, page-locked
-        blk = np.array(blk, dtype=np.float64)
+        blk = moments(dev, B_cur)
         Sp, Sp_spatial, Sp_sigma2 = float(blk[9]), float(blk[11]), float(blk[12])
         if svi is not None:                                    # :1178-1181
             Sp_run = Sp = step * Sp + (1 - step) * Sp_run
@@ -1029,11 +1029,8 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
                                 f"{Sp_sigma2}): no B cell lies within reach of the A slice at sigma2 = {sigma2}")
         gamma = float(np.exp(_digamma(gamma_a + Sp_spatial) - _digamma(gamma_a + gamma_b + NB_eff)))   # :1214-1222
         gamma = max(min(gamma, 0.99), 0.01)
-        if svi is None:
-            R, t = _rigid_from_block(blk, D, sigma2, a["inliers"], float(nn_init_weight), R, update_R)
-        else:
-            R, t = _rigid_from_block(blk, D, sigma2, a["inliers"], float(nn_init_weight), R, update_R, Sp_blend=Sp, step=step,
-                                     t_prev=t)
+        R, t = _rigid_from_block(blk, D, sigma2, a["inliers"], float(nn_init_weight), R, update_R,
+                                 Sp_blend=None if svi is None else Sp, step=step, t_prev=t)
         R3, t3 = _embed(R, t)
         k.align_transform(A64, V4, None, None, R3, t3, origin=org, RnA=RnA, XAHat=XAHat, xa4=xa4)
         sigma2_related = float(blk[50]) / (D * Sp_sigma2)     # :1200
@@ -1063,16 +1060,8 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
         if a["sigma2_end"] is not None:                        # model_mul of :1087 with the replaced sigma2: once, on the host
             al, sd = k.to_host([alpha, SigmaDiag], own_pinned=False)
             model_mul = k.h2d(np.array(al, dtype=np.float64) * np.exp(-np.array(sd, dtype=np.float64) / sigma2))
-        outlier = _spatial_outlier(sigma2, gamma, samples_s, NA, D)
-        dev = _assign_device(k, xa4, xb4, layers, model_mul, sigma2, sigma2_variance, outlier, dense=bool(return_P), top_k=top_k)
-        if best:
-            best_dev = k.assign_best(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier))
-        if apply is not None and top_k is None:
-            apply_dev = k.assign_apply(xa4, xb4, layers, model_mul, sigma2, sigma2_variance, float(outlier),
-                                       features_B=FB_dev, features_A=FA_dev)
-        k.align_moments(A64, V4, dev["K_NA"], dev["K_NA_spatial"], dev["K_NA_sigma2"], SigmaDiag, dev["PXB"], B64, dev["K_NB"],
-                        block, origin=org, extra=dev["scalars"])
-        blk = np.array(k.to_host([block])[0], dtype=np.float64)
+        dev = assignment(xb4, layers, last=True)
+        blk = moments(dev, B64)
         Sp_run, Sp_spatial_run, Sp_sigma2_run = float(blk[9]), float(blk[11]), float(blk[12])
         if not (Sp_run > 0.0 and np.isfinite(blk).all()):
             raise _lib.MVFError(f"morpho_iterate_svi: the final full assignment is empty or not finite (Sp = {Sp_run})")
@@ -1096,10 +1085,10 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
     if return_P:
         out["P"] = np.array(k.to_host([dev["P"]], own_pinned=False)[0], dtype=np.float64)
     if best:
-        out["best"] = _best_to_host(k, best_dev)
+        out["best"] = _best_to_host(k, extras["best"])
     if apply is not None:
         if top_k is None:
-            out["applied"] = _applied_to_host(k, apply_dev, apply["normalize"])
+            out["applied"] = _applied_to_host(k, extras["applied"], apply["normalize"])
         else:
             out["applied"] = _applied_from_coo(out["P"], out["K_NA"], out["K_NB"], apply["FA"], apply["FB"], apply["normalize"])
     if record:
@@ -1244,17 +1233,11 @@ def _coords_pair(coordsA, coordsB, who):
     return XA, XB
 
 
-def _product_layer(k, A, B, metric):
-    """Both sides of one product layer prepared for mvf_assign_layer_stats: the tuple HipKernels.assign_layer_stats takes."""
+def _product_layer(k, A, B, metric, prob=_lib.ASSIGN_PROBS["prob"], param=0.0):
+    """Both sides of one product layer prepared (mvf_assign_prepare): a `Layer` (mvf_assign_layer_stats reads no prob / param)."""
     Xp, a, ld = k.assign_prepare(A, metric, 0)
     Yp, b, _ = k.assign_prepare(B, metric, 1)
-    return (Xp, Yp, a, b, ld, metric, _lib.ASSIGN_PROBS["prob"], 0.0)
-
-
-def _exchanged(layer):
-    """The layer whose column statistics are `layer`'s row statistics: Xp <-> Yp, a <-> b (the caller exchanges na and nb)."""
-    Xp, Yp, a, b, ld, metric, prob, param = layer
-    return (Yp, Xp, b, a, ld, metric, prob, param)
+    return Layer(Xp, Yp, a, b, ld, metric, prob, param)
 
 
 def init_sigma2(coordsA, coordsB, *, sigma2_init_scale=1.0, subsample=20000, subsample_A=None, subsample_B=None, seed=0,
@@ -1315,7 +1298,7 @@ def _estimate_parameters(k, LA, LB, codes, estimate, iA, iB):
     for l in estimate:
         layer = _product_layer(k, LA[l][iA], LB[l][iB], codes[l][0])
         # the minima over B for every A cell: the column minima of the exchanged call
-        stats = k.assign_layer_stats(_exchanged(layer), len(iB), len(iA))
+        stats = k.assign_layer_stats(layer.exchanged(), len(iB), len(iA))
         row_min = np.sort(np.asarray(_rt._to_host(k, [stats["cmin"]])[0], dtype=np.float64))
         found[l] = max(float(row_min[int(len(iA) * 0.05)]) / 5, 0.01)
     return found
@@ -1510,7 +1493,7 @@ def coarse_rigid_alignment(coordsA, coordsB, init_A, init_B, *, metric, nn_init_
     k = _rt._shared_kernels(device, dtype)
     layer = _product_layer(k, gA, gB, _lib.ASSIGN_METRICS[metric])
     cols = k.assign_layer_stats(layer, N, M, top_K)                  # per B voxel: its top_K A voxels
-    rows = k.assign_layer_stats(_exchanged(layer), M, N, top_K)      # per A voxel: its top_K B voxels
+    rows = k.assign_layer_stats(layer.exchanged(), M, N, top_K)      # per A voxel: its top_K B voxels
     c_rows, c_vals, r_rows, r_vals = _rt._to_host(k, [cols["rows"], cols["vals"], rows["rows"], rows["vals"]])
     # the pair list (B voxel, A voxel) in the reference's order (:976-998): every B voxel's neighbours, then every A voxel's
     NN1 = np.stack([np.repeat(np.arange(M), top_K), np.asarray(c_rows, dtype=np.int64).reshape(-1)], axis=1)

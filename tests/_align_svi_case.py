@@ -214,6 +214,7 @@ def transform_svi_reference(RnA, PXB, K, origin, step, PXB_term, npdt):
 import torch  # noqa: E402
 
 import _cpu_kernels as ck  # noqa: E402
+from spateo_amd._kernels import Layer  # noqa: E402
 
 
 class CpuLoopKernels(ck.CpuKernels):
@@ -238,26 +239,36 @@ class CpuLoopKernels(ck.CpuKernels):
         L = torch.from_numpy(np.ascontiguousarray(layer, dtype=np.float64))
         return L, torch.zeros(len(L), dtype=torch.float64), L.shape[1]
 
-    def assign(self, xa4, xb4, layers, model_mul, sigma2, s2v, outlier, dense=False):
+    def restated(self, xa4, xb4, layers, model_mul, sigma2, s2v, outlier, restatement=ac.restatement, **extra):
+        """`restatement` (the assignment's, or a variant with `extra` keywords) on the arguments of an assignment kernel:
+        (its result, XA, XB).  The layers are `Layer` records or plain 8-sequences."""
         inv = {0: "euc", 1: "square_euc", 2: "kl", 3: "sym_kl", 4: "cos"}
         invp = {0: "gauss", 1: "cos", 2: "prob"}
+        layers = [Layer(*L) for L in layers]
         D = self.D
         XA, XB = ck._np(xa4)[:, :D], ck._np(xb4)[:, :D]
         NA = len(XA)
         # the assignment's restatement takes alpha, SigmaDiag, gamma, samples_s: model_mul goes in as alpha with SigmaDiag = 0,
         # and the outlier term o = (2 pi sigma2)^(D/2) (1 - g) / (g samples_s NA) is met with samples_s = 1 and g solved from it
         c = np.power(2 * np.pi * sigma2, D / 2) / NA
-        g = c / (outlier + c)
-        a = ac.restatement(XA, XB, [ck._np(L[0]) for L in layers], [ck._np(L[1]) for L in layers],
-                           dissimilarity=[inv[L[5]] for L in layers], probability_type=[invp[L[6]] for L in layers],
-                           probability_parameters=[L[7] for L in layers], sigma2=sigma2, alpha=ck._np(model_mul),
-                           SigmaDiag=np.zeros(NA), gamma=g, samples_s=1.0, sigma2_variance=s2v)
-        pxb = np.zeros((NA, 3))
+        a = restatement(XA, XB, [ck._np(L.Xp) for L in layers], [ck._np(L.Yp) for L in layers],
+                        dissimilarity=[inv[L.metric] for L in layers], probability_type=[invp[L.prob] for L in layers],
+                        probability_parameters=[L.param for L in layers], sigma2=sigma2, alpha=ck._np(model_mul),
+                        SigmaDiag=np.zeros(NA), gamma=c / (outlier + c), samples_s=1.0, sigma2_variance=s2v, **extra)
+        return a, XA, XB
+
+    def assign_result(self, a, more=()):
+        """A restatement's result as the dict of tensors HipKernels.assign returns, plus the keys `more`."""
+        D = self.D
+        pxb = np.zeros((len(a["K_NA"]), 3))
         pxb[:, :D] = a["PXB"]
         raw = a["sigma2_related"] * D * a["Sp_sigma2"]
-        t = torch.from_numpy
-        return {"K_NA": t(a["K_NA"]), "K_NB": t(a["K_NB"]), "K_NA_spatial": t(a["K_NA_spatial"]), "K_NA_sigma2": t(a["K_NA_sigma2"]),
-                "PXB": t(pxb), "scalars": torch.tensor([raw], dtype=torch.float64)}
+        out = {q: torch.from_numpy(np.ascontiguousarray(a[q])) for q in ("K_NA", "K_NB", "K_NA_spatial", "K_NA_sigma2") + tuple(more)}
+        out.update(PXB=torch.from_numpy(pxb), scalars=torch.tensor([raw], dtype=torch.float64))
+        return out
+
+    def assign(self, xa4, xb4, layers, model_mul, sigma2, s2v, outlier, dense=False):
+        return self.assign_result(self.restated(xa4, xb4, layers, model_mul, sigma2, s2v, outlier)[0])
 
     def align_alpha(self, kappa, Ks, sd, Sp_spatial, sigma2, alpha, model_mul):
         a, m = lc.alpha_reference(ck._np(kappa), ck._np(Ks), ck._np(sd), Sp_spatial, sigma2)
@@ -301,8 +312,8 @@ class CpuLoopKernels(ck.CpuKernels):
         xb4_out.copy_(xb4[idx])
         B_out.copy_(B[idx])
         for L, yo, bo in zip(layers, Yp_out, b_out):
-            yo.copy_(L[1][idx])
-            bo.copy_(L[3][idx])
+            yo.copy_(Layer(*L).Yp[idx])
+            bo.copy_(Layer(*L).b[idx])
 
 
 def cpu_loop_kernels(monkeypatch, D):

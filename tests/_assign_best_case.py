@@ -21,6 +21,7 @@ import torch
 import _assign_case as ac
 import _assign_topk_case as tk
 import _cpu_kernels as ck
+from spateo_amd._kernels import Layer
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "ref_assign_best.npz")
@@ -141,7 +142,7 @@ class CpuBestKernels(tk.CpuTopkKernels):
 
     @staticmethod
     def _state(xa4, xb4, layers, model_mul, sigma2, s2v, outlier):
-        return dict(xa4=ck._np(xa4).copy(), xb4=ck._np(xb4).copy(), b=[ck._np(L[3]).copy() for L in layers],
+        return dict(xa4=ck._np(xa4).copy(), xb4=ck._np(xb4).copy(), b=[ck._np(Layer(*L).b).copy() for L in layers],
                     model_mul=ck._np(model_mul).copy(), sigma2=float(sigma2), s2v=float(s2v), outlier=float(outlier))
 
     def assign(self, xa4, xb4, layers, model_mul, sigma2, s2v, outlier, dense=False):
@@ -153,16 +154,7 @@ class CpuBestKernels(tk.CpuTopkKernels):
         return super().assign_topk(xa4, xb4, layers, model_mul, sigma2, s2v, outlier, k)
 
     def assign_best(self, xa4, xb4, layers, model_mul, sigma2, s2v, outlier, rows=True, cols=True):
-        inv = {0: "euc", 1: "square_euc", 2: "kl", 3: "sym_kl", 4: "cos"}
-        invp = {0: "gauss", 1: "cos", 2: "prob"}
-        D = self.D
-        XA, XB = ck._np(xa4)[:, :D], ck._np(xb4)[:, :D]
-        NA = len(XA)
-        c = np.power(2 * np.pi * sigma2, D / 2) / NA       # (CpuLoopKernels.assign: the outlier term met through gamma)
-        a = ac.restatement(XA, XB, [ck._np(L[0]) for L in layers], [ck._np(L[1]) for L in layers], return_P=True,
-                           dissimilarity=[inv[L[5]] for L in layers], probability_type=[invp[L[6]] for L in layers],
-                           probability_parameters=[L[7] for L in layers], sigma2=sigma2, alpha=ck._np(model_mul),
-                           SigmaDiag=np.zeros(NA), gamma=c / (outlier + c), samples_s=1.0, sigma2_variance=s2v)
+        a, XA, XB = self.restated(xa4, xb4, layers, model_mul, sigma2, s2v, outlier, return_P=True)
         b = best_of(a["P"], XA, XB)
         self.CALLS.append(("assign_best", dict(self._state(xa4, xb4, layers, model_mul, sigma2, s2v, outlier), P=a["P"])))
         keep = (("rows", "row_values") if rows else ()) + (("cols", "col_values") if cols else ())

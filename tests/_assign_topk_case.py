@@ -15,11 +15,9 @@ near-tie that flips an entry cannot fail a sum it did not corrupt."""
 import os
 
 import numpy as np
-import torch
 
 import _align_svi_case as sc
 import _assign_case as ac
-import _cpu_kernels as ck
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "ref_assign_topk.npz")
@@ -114,22 +112,8 @@ class CpuTopkKernels(sc.CpuLoopKernels):
     """CpuLoopKernels plus a NumPy `assign_topk`: the dense stand-in's P, masked."""
 
     def assign_topk(self, xa4, xb4, layers, model_mul, sigma2, s2v, outlier, k):
-        inv = {0: "euc", 1: "square_euc", 2: "kl", 3: "sym_kl", 4: "cos"}
-        invp = {0: "gauss", 1: "cos", 2: "prob"}
-        D = self.D
-        XA, XB = ck._np(xa4)[:, :D], ck._np(xb4)[:, :D]
-        NA = len(XA)
-        c = np.power(2 * np.pi * sigma2, D / 2) / NA       # (CpuLoopKernels.assign: the outlier term met through gamma)
-        a = restatement(XA, XB, [ck._np(L[0]) for L in layers], [ck._np(L[1]) for L in layers], k=k,
-                        dissimilarity=[inv[L[5]] for L in layers], probability_type=[invp[L[6]] for L in layers],
-                        probability_parameters=[L[7] for L in layers], sigma2=sigma2, alpha=ck._np(model_mul),
-                        SigmaDiag=np.zeros(NA), gamma=c / (outlier + c), samples_s=1.0, sigma2_variance=s2v)
-        pxb = np.zeros((NA, 3))
-        pxb[:, :D] = a["PXB"]
-        raw = a["sigma2_related"] * D * a["Sp_sigma2"]
-        t = lambda v: torch.from_numpy(np.ascontiguousarray(v))  # noqa: E731
-        return {"K_NA": t(a["K_NA"]), "K_NB": t(a["K_NB"]), "K_NA_spatial": t(a["K_NA_spatial"]), "K_NA_sigma2": t(a["K_NA_sigma2"]),
-                "PXB": t(pxb), "scalars": torch.tensor([raw], dtype=torch.float64), "rows": t(a["rows"]), "vals": t(a["vals"])}
+        a, _, _ = self.restated(xa4, xb4, layers, model_mul, sigma2, s2v, outlier, restatement=restatement, k=k)
+        return self.assign_result(a, more=("rows", "vals"))
 
 
 def cpu_topk_kernels(monkeypatch, D):

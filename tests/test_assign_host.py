@@ -164,3 +164,35 @@ def test_c_abi_symbols_and_no_launch_paths():
     assert lib.mvf_assign_prepare(p, 10, 5, 2, 0, p, 24, p, _lib.MVF_F64, None) != 0 and b"ld must be" in lib.mvf_last_error()
     assert lib.mvf_assign_prepare(p, 10, 5, 7, 0, p, 16, p, _lib.MVF_F64, None) != 0 and b"bad metric" in lib.mvf_last_error()
     assert lib.mvf_assign_prepare(p, 10, 5, 2, 2, p, 16, p, _lib.MVF_F64, None) != 0 and b"side" in lib.mvf_last_error()
+
+
+def test_layer_record_and_layer_array():
+    """`Layer` and `layer_array` (spateo_amd._kernels) on host tensors: every field of mvf_assign_layer set from a record and
+    from a plain 8-sequence, NULL for a label layer's Yp, max(n, 1) entries; exchanged() and with_columns() against the tuple
+    expressions they replace, field by field on objects with distinct identities."""
+    import torch
+
+    from spateo_amd import _lib
+    from spateo_amd._kernels import Layer, layer_array
+
+    Xp, Yp, a, b, T, la, lb, Y2, b2 = (torch.zeros(4, dtype=torch.float64) for _ in range(9))
+    assert len({t.data_ptr() for t in (Xp, Yp, a, b, T, la, lb, Y2, b2)}) == 9
+    product = Layer(Xp, Yp, a, b, 16, _lib.ASSIGN_METRICS["kl"], _lib.ASSIGN_PROBS["gauss"], 0.25)
+    label = Layer(T, None, la, lb, 3, _lib.ASSIGN_LABEL, _lib.ASSIGN_PROBS["prob"], 0.0)
+    assert Layer._fields == ("Xp", "Yp", "a", "b", "ld", "metric", "prob", "param")
+    assert label.is_label and not product.is_label
+    for layers in ([product, label], [tuple(product), tuple(label)]):
+        arr = layer_array(layers)
+        assert len(arr) == 2 and isinstance(arr[0], _lib.AssignLayer)
+        for s, L in zip(arr, (product, label)):
+            assert (s.Xp, s.a, s.b) == (L.Xp.data_ptr(), L.a.data_ptr(), L.b.data_ptr())
+            assert s.Yp == (None if L.Yp is None else L.Yp.data_ptr())
+            assert (s.ld, s.metric, s.prob, s.param) == (L.ld, L.metric, L.prob, L.param)
+    assert len(layer_array([])) == 1 and len(layer_array([product])) == 1
+    p0, p1, p2, p3, ld, metric, prob, param = product
+    for got, want in ((product.exchanged(), (p1, p0, p3, p2, ld, metric, prob, param)),
+                      (product.with_columns(Y2, b2), (product[0], Y2, product[2], b2) + tuple(product[4:])),
+                      (label.with_columns(None, b2), (label[0], None, label[2], b2) + tuple(label[4:]))):
+        assert isinstance(got, Layer) and len(got) == len(want) == 8
+        for x, y in zip(got, want):
+            assert x is y if torch.is_tensor(y) or y is None else x == y

@@ -19,58 +19,14 @@ import pytest
 import torch
 
 import _align_loop_case as lc
+from _align_kernel_scaffold import (DEV, DTYPES, GUARD, SENTINEL, deviation_table, dev as _dev, guarded as _guarded,
+                                    intact as _intact, kernels as _k, same_bits as _same_bits)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-DTYPES = ["float64", "float32"]
 SIZES = [1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 70001]
 VARIANTS = ["zero_K", "one_K", "denormal_K", "kappa_small", "kappa_large", "zero_Ks", "offset", "reflection"]
-SENTINEL = {torch.float64: -1.2345e300, torch.float32: -1.2345e30, torch.uint8: 0xA5}
-GUARD = 1024
-_KERNELS, _WORST = {}, {}
-
-
-def _k(dtype):
-    if dtype not in _KERNELS:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _KERNELS[dtype] = HipKernels(DEV, dtype)
-    return _KERNELS[dtype]
-
-
-def _note(family, dtype, value):
-    _WORST[(family, dtype)] = max(_WORST.get((family, dtype), 0.0), float(value))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _deviation_table():
-    yield
-    print("\n| family | dtype | largest deviation / bound |\n|---|---|---|")
-    for (fam, dtype), v in sorted(_WORST.items()):
-        print(f"| {fam} | {dtype} | {v:.3g} |")
-
-
-def _dev(a, tdtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(tdtype).to(DEV)
-
-
-def _guarded(n, tdtype=torch.float64):
-    return torch.full((n + GUARD,), SENTINEL[tdtype], dtype=tdtype, device=DEV)
-
-
-def _intact(buf, n):
-    return bool((buf[n:] == SENTINEL[buf.dtype]).all())
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.int64, 4: np.int32, 1: np.uint8}[a.dtype.itemsize])
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
+_note, _deviation_table = deviation_table("| family | dtype | largest deviation / bound |")
 
 
 def make_inputs(n, variant, seed=0):

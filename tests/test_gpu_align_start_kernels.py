@@ -19,12 +19,11 @@ import torch
 import _align_start_case as sc
 import _assign_case as ac
 import _assign_edge_cases as ec
-import test_gpu_assign_kernels as base
+from _align_kernel_scaffold import (DEV, DTYPES, GUARD, dev as _dev, guarded as _guarded, intact as _intact, kernels as _k,
+                                    nan_workspace as _nan_workspace, prepare as _prepare, written as _written)
 
 pytestmark = pytest.mark.gpu
 
-DEV = base.DEV
-DTYPES = base.DTYPES
 KS = (0, 1, 10, 64)
 # (na, nb, the k's): a list of 64 is asked for where the columns are few - the more entries the lists of a case hold, the
 # closer the closest two of them lie, and the generated cases keep GAP between neighbours
@@ -67,7 +66,7 @@ class _Layer:
     distance matrix (na, nb) from the stored operands; `swapped` the same for the exchanged call."""
 
     def __init__(self, na, nb, g, metric, dtype, k=64):
-        kk = base._k(dtype)
+        kk = _k(dtype)
         self.k, self.na, self.nb, self.metric, self.dtype = kk, na, nb, metric, dtype
         self.name = f"{metric} {na}x{nb} G {g} {dtype}"
         if metric == "label":   # g: (K, L) of the table
@@ -75,7 +74,7 @@ class _Layer:
             rng = np.random.default_rng(na + 3 * nb + K + L)
             table = rng.uniform(0.1, 2.0, (K, L))
             la, lb = rng.integers(0, K, na), rng.integers(0, L, nb)
-            T, Tt = base._dev(table), base._dev(table.T.copy())
+            T, Tt = _dev(table), _dev(table.T.copy())
             a, b = kk.assign_label_prepare(la, K), kk.assign_label_prepare(lb, L)
             self.fields = (T, None, a, b, L, LABEL)
             self.swapped = (Tt, None, b, a, K, LABEL)
@@ -83,8 +82,8 @@ class _Layer:
             self.keep = (T, Tt, a, b)
         else:
             A, B = _product_inputs(na, nb, g, metric, dtype, k)
-            Xp, a, ld = base._prepare(kk, A, metric, 0)
-            Yp, b, _ = base._prepare(kk, B, metric, 1)
+            Xp, a, ld = _prepare(kk, A, metric, 0)
+            Yp, b, _ = _prepare(kk, B, metric, 1)
             self.fields = (Xp, Yp, a, b, ld, ec.METRICS[metric])
             self.swapped = (Yp, Xp, b, a, ld, ec.METRICS[metric])
             self.d = sc.stored_distance(Xp.double().cpu().numpy(), Yp.double().cpu().numpy(), a.cpu().numpy(), b.cpu().numpy(), metric)
@@ -102,31 +101,29 @@ def _stats(ly, fields, na, nb, k, ws=None, ws_bytes=None):
     """mvf_assign_layer_stats through the raw ABI; guards behind every output and the workspace (exactly
     mvf_assign_layer_stats_workspace_bytes, NaN-filled).  Returns host arrays."""
     from spateo_amd import _lib
+    from spateo_amd._kernels import layer_array
 
     kk = ly.k
     ke = min(k, na)
     Xp, Yp, a, b, ld, metric = fields
-    arr = (_lib.AssignLayer * 1)()
-    s = arr[0]
-    s.Xp, s.Yp, s.a, s.b, s.ld = Xp.data_ptr(), None if Yp is None else Yp.data_ptr(), a.data_ptr(), b.data_ptr(), int(ld)
-    s.metric, s.prob, s.param = int(metric), 0, -1.0   # prob / param are not read: a gauss layer without a parameter passes
+    arr = layer_array([(Xp, Yp, a, b, ld, metric, 0, -1.0)])   # prob / param are not read: a gauss layer without a parameter passes
     sizes = {"cmin": nb, "sums": 2, "vals": nb * ke}
-    bufs = {q: base._guarded(n) for q, n in sizes.items()}
-    rows = torch.full((nb * ke + base.GUARD,), -7, dtype=torch.int32, device=DEV)
+    bufs = {q: _guarded(n) for q, n in sizes.items()}
+    rows = torch.full((nb * ke + GUARD,), -7, dtype=torch.int32, device=DEV)
     need = int(kk.lib.mvf_assign_layer_stats_workspace_bytes(na, nb, k))
     assert need > 0 and need % 8 == 0
     if ws is None:
-        ws, ws_bytes = base._nan_workspace(need), need
+        ws, ws_bytes = _nan_workspace(need), need
     _lib.check(kk.lib.mvf_assign_layer_stats(arr, na, nb, k, bufs["cmin"].data_ptr(), rows.data_ptr() if k else None,
                                              bufs["vals"].data_ptr() if k else None, bufs["sums"].data_ptr(), ws.data_ptr(),
                                              int(ws_bytes), kk.cdtype, kk._stream()), "mvf_assign_layer_stats")
     torch.cuda.synchronize()
     for q, n in sizes.items():
-        assert base._intact(bufs[q], n), f"{ly.name}: wrote behind {q}[{n}]"
-        assert base._written(bufs[q], n), f"{ly.name}: left an element of {q} unwritten"
+        assert _intact(bufs[q], n), f"{ly.name}: wrote behind {q}[{n}]"
+        assert _written(bufs[q], n), f"{ly.name}: left an element of {q} unwritten"
     assert bool((rows[nb * ke:] == -7).all()), f"{ly.name}: wrote behind rows"
     assert bool((rows[: nb * ke] != -7).all()), f"{ly.name}: left an element of rows unwritten"
-    assert base._intact(ws, ws_bytes // 8), f"{ly.name}: wrote behind the workspace"
+    assert _intact(ws, ws_bytes // 8), f"{ly.name}: wrote behind the workspace"
     out = {q: bufs[q][:n].cpu().numpy() for q, n in sizes.items()}
     out["vals"], out["rows"] = out["vals"].reshape(nb, ke), rows[: nb * ke].cpu().numpy().reshape(nb, ke)
     return out
@@ -210,7 +207,7 @@ def test_workspace_contents_size_and_stream_do_not_matter(dtype):
     kk = ly.k
     size = max(int(kk.lib.mvf_assign_layer_stats_workspace_bytes(65, 129, 10)),
                int(kk.lib.mvf_assign_layer_stats_workspace_bytes(4097, 10, 10))) + 4096
-    ws = base._guarded(size // 8)
+    ws = _guarded(size // 8)
     ws[: size // 8] = 0.0
     zero = _stats(ly, ly.fields, 65, 129, 10, ws=ws, ws_bytes=size)
     _stats(big, big.fields, 4097, 10, 10, ws=ws, ws_bytes=size)

@@ -16,46 +16,12 @@ import pytest
 import torch
 
 import _align_svi_case as sc
+from _align_kernel_scaffold import (DEV, DTYPES, dev as _dev, guarded as _guarded, intact as _intact, kernels as _k,
+                                    same_bits as _same_bits)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-DTYPES = ["float64", "float32"]
 SIZES = [1, 255, 256, 257, 70001]
-SENTINEL = {torch.float64: -1.2345e300, torch.float32: -1.2345e30}
-GUARD = 1024
-_KERNELS = {}
-
-
-def _k(dtype):
-    if dtype not in _KERNELS:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _KERNELS[dtype] = HipKernels(DEV, dtype)
-    return _KERNELS[dtype]
-
-
-def _dev(a, tdtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if tdtype is None else t.to(tdtype)).to(DEV)
-
-
-def _guarded(n, tdtype=torch.float64):
-    return torch.full((n + GUARD,), SENTINEL[tdtype], dtype=tdtype, device=DEV)
-
-
-def _intact(buf, n):
-    return bool((buf[n:] == SENTINEL[buf.dtype]).all())
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.int64, 4: np.int32}[a.dtype.itemsize])
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 # ---- gather ----------------------------------------------------------------------------------------------------------
@@ -79,11 +45,9 @@ def _slice(nb, lds, dtype):
 
 
 def _gather(lib, k, perm, nb, start, bs, xb4, B, Yp, b, lds, outs):
-    from spateo_amd import _lib
+    from spateo_amd._kernels import layer_array
 
-    arr = (_lib.AssignLayer * max(len(lds), 1))()
-    for s, y, c, ld in zip(arr, Yp, b, lds):
-        s.Yp, s.b, s.ld = y.data_ptr(), c.data_ptr(), ld
+    arr = layer_array([(None, y, None, c, ld, 0, 0, 0.0) for y, c, ld in zip(Yp, b, lds)])   # (Yp, b, ld are what it reads)
     vp = ctypes.c_void_p * max(len(lds), 1)
     return lib.mvf_align_gather(perm.data_ptr(), nb, start, bs, xb4.data_ptr(), outs["xb4"].data_ptr(), B.data_ptr(),
                                 outs["B"].data_ptr(), arr, len(lds), vp(*[o.data_ptr() for o in outs["Yp"]]),
@@ -128,6 +92,8 @@ def test_gather(bs, lds, dtype):
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_gather_through_the_binding_and_empty_batch(dtype):
     """HipKernels.align_gather (what the loop calls) on layers as assign_prepare returns them; bs = 0 is a no-op."""
+    from spateo_amd._kernels import Layer
+
     k, lib = _k(dtype), _k(dtype).lib
     rng = np.random.default_rng(3)
     nb, bs = 457, 150
@@ -135,19 +101,19 @@ def test_gather_through_the_binding_and_empty_batch(dtype):
     layers = []
     for g, metric in ((40, 2), (24, 4)):
         Yp, b, ld = k.assign_prepare(rng.random((nb, g)) + 0.1, metric, 1)
-        layers.append((None, Yp, None, b, ld, metric, 0, 0.1))
+        layers.append((None, Yp, None, b, ld, metric, 0, 0.1))   # plain 8-sequences: the binding takes them
     xb4, B = k.to_x4(XB), k.h2d_padded(XB, 3, torch.float64)
     perm = rng.permutation(nb).astype(np.int32)
-    outs = (k.empty(bs, 4), k.empty(bs, 3, dtype=torch.float64), [k.empty(bs, L[4]) for L in layers],
+    outs = (k.empty(bs, 4), k.empty(bs, 3, dtype=torch.float64), [k.empty(bs, Layer(*L).ld) for L in layers],
             [k.empty(bs, dtype=torch.float64) for L in layers])
     for it in (0, 3, 4):
-        k.align_gather(_dev(perm), (-it * bs) % nb, bs, xb4, B, layers, *outs)
+        k.align_gather(_dev(perm, None), (-it * bs) % nb, bs, xb4, B, layers, *outs)
         idx = torch.from_numpy(sc.schedule(perm, bs, it).astype(np.int64)).to(DEV)
         assert torch.equal(outs[0], xb4[idx]) and torch.equal(outs[1], B[idx])
         for l, L in enumerate(layers):
-            assert torch.equal(outs[2][l], L[1][idx]) and torch.equal(outs[3][l], L[3][idx])
+            assert torch.equal(outs[2][l], Layer(*L).Yp[idx]) and torch.equal(outs[3][l], Layer(*L).b[idx])
     with pytest.raises(ValueError):
-        k.align_gather(_dev(perm.astype(np.int64)), 0, bs, xb4, B, layers, *outs)
+        k.align_gather(_dev(perm.astype(np.int64), None), 0, bs, xb4, B, layers, *outs)
     # bs == 0: nothing is launched, whatever the pointers
     assert lib.mvf_align_gather(None, nb, 0, 0, None, None, None, None, None, 0, None, None, k.cdtype, None) == 0
     p = xb4.data_ptr()

@@ -19,14 +19,12 @@ import torch
 import _assign_best_case as bc
 import _assign_case as ac
 import _assign_edge_cases as ec
-import test_gpu_assign_kernels as base
-import test_gpu_assign_label_kernels as labk
-import test_gpu_assign_topk_kernels as tkk
+from _align_kernel_scaffold import (DEV, DTYPES, GUARD, SENTINEL, LabelCase as _LabelCase, device_case as _case,
+                                    guarded as _guarded, intact as _intact, kernels as _k, layer_struct as _layer_array,
+                                    nan_workspace as _nan_workspace, written as _written)
 
 pytestmark = pytest.mark.gpu
 
-DEV = base.DEV
-DTYPES = base.DTYPES
 EDGE_SHAPES = [(na, nb) for na in (63, 64, 65, 129) for nb in (1, 65, 200)]
 SPLIT_SHAPES = [(4417, 50), (50, 4417)]
 SHAPES = list(ec.DENSE_SHAPES) + EDGE_SHAPES + SPLIT_SHAPES
@@ -48,15 +46,15 @@ def _best(dc, rows=True, cols=True, ws=None, ws_bytes=None, struct=None, nlayers
     need = int(kk.lib.mvf_assign_best_workspace_bytes(na, nb))
     assert need > int(kk.lib.mvf_assign_workspace_bytes(na, nb)) and need % 8 == 0
     if ws is None:
-        ws, ws_bytes = base._nan_workspace(need), need
+        ws, ws_bytes = _nan_workspace(need), need
     bufs = {}
     for on, name, n in ((rows, "row", na), (cols, "col", nb)):
         if on:
-            bufs[f"{name}_idx"] = torch.full((2 * n + base.GUARD,), UNSET, dtype=torch.int32, device=DEV)
-            bufs[f"{name}_val"] = base._guarded(n)
+            bufs[f"{name}_idx"] = torch.full((2 * n + GUARD,), UNSET, dtype=torch.int32, device=DEV)
+            bufs[f"{name}_val"] = _guarded(n)
     ptr = lambda q: bufs[q].data_ptr() if q in bufs else None  # noqa: E731
     c = dc.case if hasattr(dc, "case") else dc.c
-    arr = tkk._layer_array(dc) if struct is None else struct
+    arr = _layer_array(dc) if struct is None else struct
     _lib.check(kk.lib.mvf_assign_best(dc.xa4.data_ptr(), na, dc.xb4.data_ptr(), nb, arr, len(dc.layers) if nlayers is None else nlayers,
                                       dc.mm.data_ptr(), float(c["sigma2"]), float(c["sigma2_variance"]), float(dc.outlier),
                                       ptr("row_idx"), ptr("row_val"), ptr("col_idx"), ptr("col_val"), ws.data_ptr(), int(ws_bytes),
@@ -69,10 +67,10 @@ def _best(dc, rows=True, cols=True, ws=None, ws_bytes=None, struct=None, nlayers
         idx, val = bufs[f"{name}_idx"], bufs[f"{name}_val"]
         assert bool((idx[2 * n:] == UNSET).all()), f"wrote behind {name}_idx"
         assert bool((idx[: 2 * n] != UNSET).all()), f"left an element of {name}_idx unwritten"
-        assert base._intact(val, n), f"wrote behind {name}_val"
-        assert base._written(val, n), f"left an element of {name}_val unwritten"
+        assert _intact(val, n), f"wrote behind {name}_val"
+        assert _written(val, n), f"left an element of {name}_val unwritten"
         out[key], out[vkey] = idx[: 2 * n].cpu().numpy().reshape(n, 2), val[:n].cpu().numpy()
-    assert base._intact(ws, ws_bytes // 8), "wrote behind the workspace"
+    assert _intact(ws, ws_bytes // 8), "wrote behind the workspace"
     return out
 
 
@@ -91,7 +89,7 @@ def _check(dc, got, what):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("na,nb", SHAPES)
 def test_shapes_on_the_kernels_edges(dtype, na, nb):
-    dc = tkk._case(("best", na, nb), lambda: _shape_case(na, nb), dtype)
+    dc = _case(("best", na, nb), lambda: _shape_case(na, nb), dtype)
     got = _best(dc)
     _check(dc, got, f"{na}x{nb}")
     _same(got, _best(dc))
@@ -104,7 +102,7 @@ def test_shapes_on_the_kernels_edges(dtype, na, nb):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("g", [1, 16, 17])
 def test_the_k_step(dtype, g):
-    dc = tkk._case(("best-g", g), lambda: ec.make_case(f"best-g{g}", 70, 66, [("kl", "gauss", None, g)]), dtype)
+    dc = _case(("best-g", g), lambda: ec.make_case(f"best-g{g}", 70, 66, [("kl", "gauss", None, g)]), dtype)
     got = _best(dc)
     _check(dc, got, f"g {g}")
     _same(got, _best(dc))
@@ -115,7 +113,7 @@ def test_the_k_step(dtype, g):
 def test_layers_and_dimensions(dtype, kind):
     make = {"four-layers": lambda: ec.make_case("best-4-layers", 140, 101, list(ec.LAYER_SET)),
             "2d": lambda: ec.make_case("best-2d", 70, 66, [("euc", "gauss", None, 24)], D=2, sigma2_variance=2.5)}[kind]
-    dc = tkk._case(("best", kind), make, dtype)
+    dc = _case(("best", kind), make, dtype)
     got = _best(dc)
     _check(dc, got, kind)
     _same(got, _best(dc))
@@ -125,7 +123,7 @@ def test_layers_and_dimensions(dtype, kind):
 def test_a_label_layer(dtype):
     """The label branch of the tile routine (65 x 129, a 7 x 9 table, an expression layer beside it) against the restatement
     of tests/_assign_label_case.py on the coordinates as stored."""
-    lc = labk._Case((65, 129, 7, 9), dtype)
+    lc = _LabelCase((65, 129, 7, 9), dtype)
     lc.dtype = dtype
     got = _best(lc, struct=lc.struct())
     bc.check(got, lc.ref["P"], lc.XA, lc.XB, ac.F64_TOL, what=f"label 65x129 {dtype}")
@@ -134,7 +132,7 @@ def test_a_label_layer(dtype):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_planted_ties_are_decided_by_the_rules(dtype):
-    dc = tkk._case("best-ties", bc.tie_case, dtype)
+    dc = _case("best-ties", bc.tie_case, dtype)
     c = dc.case
     na, nb = TIE_SHAPE
     rt, ct, rs, cs = ec.plan(na, nb)
@@ -181,7 +179,7 @@ def test_planted_ties_are_decided_by_the_rules(dtype):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_a_null_pair_skips_its_direction(dtype):
-    dc = tkk._case(("best", 129, 200), lambda: _shape_case(129, 200), dtype)
+    dc = _case(("best", 129, 200), lambda: _shape_case(129, 200), dtype)
     both = _best(dc)
     only_rows, only_cols = _best(dc, cols=False), _best(dc, rows=False)
     assert sorted(only_rows) == ["row_values", "rows"] and sorted(only_cols) == ["col_values", "cols"]
@@ -192,11 +190,11 @@ def test_a_null_pair_skips_its_direction(dtype):
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_workspace_contents_and_size_do_not_matter(dtype):
     """A larger workspace, zero-filled, NaN-filled and holding a larger call's states: the same bits."""
-    ds = tkk._case(("best", 129, 200), lambda: _shape_case(129, 200), dtype)
-    dl = tkk._case(("best", 50, 4417), lambda: _shape_case(50, 4417), dtype)
+    ds = _case(("best", 129, 200), lambda: _shape_case(129, 200), dtype)
+    dl = _case(("best", 50, 4417), lambda: _shape_case(50, 4417), dtype)
     kk = ds.k
     size = max(int(kk.lib.mvf_assign_best_workspace_bytes(ds.na, ds.nb)), int(kk.lib.mvf_assign_best_workspace_bytes(dl.na, dl.nb))) + 4096
-    ws = base._guarded(size // 8)
+    ws = _guarded(size // 8)
     ws[: size // 8] = 0.0
     zero = _best(ds, ws=ws, ws_bytes=size)
     ws[: size // 8] = float("nan")
@@ -218,7 +216,7 @@ def _expected_workspace(na, nb):
 
 
 def test_workspace_size_function():
-    lib = base._k("float64").lib
+    lib = _k("float64").lib
     for na, nb in SHAPES + [TIE_SHAPE, (100000, 100000)]:
         assert int(lib.mvf_assign_best_workspace_bytes(na, nb)) == _expected_workspace(na, nb), (na, nb)
     for na, nb in ((0, 5), (5, 0), (0, 0), (-1, 5)):
@@ -226,17 +224,17 @@ def test_workspace_size_function():
 
 
 def test_argument_errors_are_reported_before_anything_is_launched():
-    dc = tkk._case(("best", 65, 63), lambda: _shape_case(65, 63), "float64")
+    dc = _case(("best", 65, 63), lambda: _shape_case(65, 63), "float64")
     lib, na, nb, c = dc.k.lib, dc.na, dc.nb, dc.case
     need = int(lib.mvf_assign_best_workspace_bytes(na, nb))
-    ws = base._nan_workspace(need)
+    ws = _nan_workspace(need)
     ri = torch.full((2 * na,), UNSET, dtype=torch.int32, device=DEV)
     ci = torch.full((2 * nb,), UNSET, dtype=torch.int32, device=DEV)
-    rv, cv = base._guarded(na), base._guarded(nb)
+    rv, cv = _guarded(na), _guarded(nb)
 
     def call(mm=dc.mm.data_ptr(), outs=None, ws_bytes=need, na_=na, nb_=nb):
         outs = (ri.data_ptr(), rv.data_ptr(), ci.data_ptr(), cv.data_ptr()) if outs is None else outs
-        rc = lib.mvf_assign_best(dc.xa4.data_ptr(), na_, dc.xb4.data_ptr(), nb_, tkk._layer_array(dc), len(dc.layers), mm,
+        rc = lib.mvf_assign_best(dc.xa4.data_ptr(), na_, dc.xb4.data_ptr(), nb_, _layer_array(dc), len(dc.layers), mm,
                                  float(c["sigma2"]), float(c["sigma2_variance"]), float(dc.outlier), *outs, ws.data_ptr(),
                                  int(ws_bytes), dc.k.cdtype, dc.k._stream())
         return rc, lib.mvf_last_error().decode("utf-8", "replace")
@@ -253,8 +251,8 @@ def test_argument_errors_are_reported_before_anything_is_launched():
     assert rc != 0 and "col_idx and col_val" in msg
     torch.cuda.synchronize()
     assert bool((ri == UNSET).all()) and bool((ci == UNSET).all())
-    assert bool((rv == base.SENTINEL[torch.float64]).all()) and bool((cv == base.SENTINEL[torch.float64]).all())
-    assert base._intact(ws, need // 8) and bool(torch.isnan(ws[: need // 8]).all())       # nothing was launched
+    assert bool((rv == SENTINEL[torch.float64]).all()) and bool((cv == SENTINEL[torch.float64]).all())
+    assert _intact(ws, need // 8) and bool(torch.isnan(ws[: need // 8]).all())       # nothing was launched
     assert call(na_=0)[0] == 0 and call(nb_=0)[0] == 0                                     # an empty side: nothing to do
     assert call()[0] == 0
     torch.cuda.synchronize()

@@ -25,170 +25,17 @@ import torch
 
 import _assign_case as ac
 import _assign_edge_cases as ec
+from _align_kernel_scaffold import (DEV, DTYPES, assign as _assign, deviation_table, device_case, guarded as _guarded,
+                                    kernels as _k, nan_workspace as _nan_workspace, prepare as _prepare,
+                                    same_bits as _same_bits)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-DTYPES = ["float64", "float32"]
-SENTINEL = {torch.float64: -1.2345e300, torch.float32: -1.2345e30}
-GUARD = 4096  # elements behind every buffer
-_KERNELS = {}
-_WORST = {}
-
-
-def _k(dtype):
-    if dtype not in _KERNELS:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _KERNELS[dtype] = HipKernels(DEV, dtype)
-    return _KERNELS[dtype]
-
-
-def _note(family, dtype, value):
-    key = (family, dtype)
-    _WORST[key] = max(_WORST.get(key, 0.0), float(value))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _deviation_table():
-    yield
-    print("\n| case family | dtype | largest deviation |\n|---|---|---|")
-    for (fam, dtype), v in sorted(_WORST.items()):
-        print(f"| {fam} | {dtype} | {v:.3g} |")
-
-
-def _dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(DEV)
-
-
-def _guarded(n, tdtype=torch.float64):
-    """n live elements and GUARD more, all holding the sentinel."""
-    return torch.full((n + GUARD,), SENTINEL[tdtype], dtype=tdtype, device=DEV)
-
-
-def _intact(buf, n):
-    return bool((buf[n:] == SENTINEL[buf.dtype]).all())
-
-
-def _written(buf, n):
-    return bool((buf[:n] != SENTINEL[buf.dtype]).all())
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
-# ------------------------------------------------------------------------------------------------------ raw calls
-def _prepare(k, layer, metric, side):
-    """mvf_assign_prepare into guarded buffers: (X' / Y' (n, ld) device view, a / b (n,) device view, ld)."""
-    from spateo_amd import _lib
-
-    L = _dev(np.asarray(layer, dtype=np.float64))
-    n, g = L.shape
-    ld = int(k.lib.mvf_assign_padded_features(g, ec.METRICS[metric]))
-    assert ld == ec.padded_features(g, metric)
-    Lp, ab = _guarded(n * ld, k.tdtype), _guarded(n)
-    _lib.check(k.lib.mvf_assign_prepare(L.data_ptr(), n, g, ec.METRICS[metric], side, Lp.data_ptr(), ld, ab.data_ptr(), k.cdtype,
-                                        k._stream()), "mvf_assign_prepare")
-    torch.cuda.synchronize()
-    assert _intact(Lp, n * ld) and _intact(ab, n), "mvf_assign_prepare wrote behind a buffer"
-    assert _written(Lp, n * ld) and _written(ab, n), "mvf_assign_prepare left an element unwritten"
-    return Lp[: n * ld].view(n, ld), ab[:n], ld
-
-
-class _DeviceCase:
-    """A case on the device: coordinates and model_mul uploaded, every layer prepared BY THE DEVICE, and all of it read back."""
-
-    def __init__(self, name, dtype):
-        c, k = ec.case(name), _k(dtype)
-        self.name, self.dtype, self.case, self.k = name, dtype, c, k
-        self.na, self.nb = len(c["XA"]), len(c["XB"])
-        self.xa4, self.xb4 = k.to_x4(c["XA"]), k.to_x4(c["XB"])
-        mm, self.outlier = ec.raw_scalars(c)
-        self.mm = _dev(mm)
-        self.layers, self.host_layers = [], []
-        for A, B, met, kind, par in zip(c["layers_A"], c["layers_B"], c["dissimilarity"], c["probability_type"],
-                                        c["probability_parameters"]):
-            Xp, a, ld = _prepare(k, A, met, 0)
-            Yp, b, _ = _prepare(k, B, met, 1)
-            self.layers.append((Xp, Yp, a, b, ld, ec.METRICS[met], ec.PROBS[kind], 0.0 if par is None else float(par)))
-            self.host_layers.append((Xp.double().cpu().numpy(), Yp.double().cpu().numpy(), a.cpu().numpy(), b.cpu().numpy(),
-                                     met, kind, par))
-        self.xa, self.xb = self.xa4.double().cpu().numpy(), self.xb4.double().cpu().numpy()
-        assert not self.xa[:, 3].any() and not self.xb[:, 3].any() and not self.xa[:, c["XA"].shape[1]:].any()
-        self.mm_host = mm
-        self._ref = None
-
-    def reference(self):
-        """pair_reference on exactly what the device holds."""
-        if self._ref is None:
-            c = self.case
-            self._ref = ec.pair_reference(self.xa, self.xb, self.host_layers, self.mm_host, c["sigma2"], c["sigma2_variance"],
-                                          self.outlier)
-        return self._ref
-
-
-_CASES = {}
+_note, _deviation_table = deviation_table("| case family | dtype | largest deviation |")
 
 
 def _device_case(name, dtype):
-    if (name, dtype) not in _CASES:
-        if len(_CASES) >= 4:
-            _CASES.pop(next(iter(_CASES)))
-        _CASES[(name, dtype)] = _DeviceCase(name, dtype)
-    return _CASES[(name, dtype)]
-
-
-def _nan_workspace(nbytes):
-    """A guarded workspace whose live bytes are NaN bit patterns: a kernel that reads workspace it did not write returns NaN."""
-    assert nbytes % 8 == 0
-    ws = _guarded(nbytes // 8)
-    ws[: nbytes // 8] = float("nan")
-    return ws
-
-
-def _assign(dc, dense=False, ws=None, ws_bytes=None):
-    """mvf_assign / mvf_assign_dense through the raw ABI on the current stream.  Every output sits in front of a guard; the
-    workspace (default: exactly mvf_assign_workspace_bytes, NaN-filled, guarded) likewise.  Returns host arrays."""
-    from spateo_amd import _lib
-
-    k, na, nb = dc.k, dc.na, dc.nb
-    sizes = {"K_NA": na, "K_NB": nb, "K_NA_spatial": na, "K_NA_sigma2": na, "PXB": 3 * na, "scalar": 1}
-    if dense:
-        sizes["P"] = na * nb
-    bufs = {q: _guarded(n) for q, n in sizes.items()}
-    need = int(k.lib.mvf_assign_workspace_bytes(na, nb))
-    assert need == ec.workspace_bytes(na, nb)
-    if ws is None:
-        ws, ws_bytes = _nan_workspace(need), need
-    arr = (_lib.AssignLayer * len(dc.layers))()
-    for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, dc.layers):
-        s.Xp, s.Yp, s.a, s.b, s.ld = Xp.data_ptr(), Yp.data_ptr(), a.data_ptr(), b.data_ptr(), int(ld)
-        s.metric, s.prob, s.param = int(metric), int(prob), float(param)
-    c = dc.case
-    head = (dc.xa4.data_ptr(), na, dc.xb4.data_ptr(), nb, arr, len(dc.layers), dc.mm.data_ptr(), float(c["sigma2"]),
-            float(c["sigma2_variance"]), float(dc.outlier)) + tuple(bufs[q].data_ptr() for q in
-                                                                   ("K_NA", "K_NB", "K_NA_spatial", "K_NA_sigma2", "PXB", "scalar"))
-    tail = (ws.data_ptr(), int(ws_bytes), k.cdtype, k._stream())
-    if dense:
-        _lib.check(k.lib.mvf_assign_dense(*head, bufs["P"].data_ptr(), *tail), "mvf_assign_dense")
-    else:
-        _lib.check(k.lib.mvf_assign(*head, *tail), "mvf_assign")
-    torch.cuda.synchronize()
-    for q, n in sizes.items():
-        assert _intact(bufs[q], n), f"{dc.name}: wrote behind {q}[{n}]"
-        assert _written(bufs[q], n), f"{dc.name}: left an element of {q} unwritten"
-    assert _intact(ws, ws_bytes // 8), f"{dc.name}: wrote behind the workspace"
-    out = {q: bufs[q][:n].cpu().numpy() for q, n in sizes.items()}
-    out["PXB"] = out["PXB"].reshape(na, 3)
-    out["scalar"] = out["scalar"].reshape(())
-    if dense:
-        out["P"] = out["P"].reshape(na, nb)
-    for q, v in out.items():
-        assert np.isfinite(v).all(), f"{dc.name}: {q} is not finite"
-    return out
+    return device_case(name, lambda: ec.case(name), dtype)
 
 
 # ------------------------------------------------------------------------------------------------------ A: prepare

@@ -17,137 +17,10 @@ import _assign_case as ac
 import _assign_edge_cases as ec
 import _assign_label_case as lab
 import _assign_topk_case as tk
+from _align_kernel_scaffold import (DTYPES, LABEL, PROBS, LabelCase as _Case, dev as _dev, guarded as _guarded,
+                                    intact as _intact, label_prepare as _label_prepare)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-DTYPES = ["float64", "float32"]
-SENTINEL = -1.2345e300
-GUARD = 4096
-LABEL, PROBS = 5, {"gauss": 0, "cos": 1, "prob": 2}
-_KERNELS = {}
-
-
-def _k(dtype):
-    if dtype not in _KERNELS:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _KERNELS[dtype] = HipKernels(DEV, dtype)
-    return _KERNELS[dtype]
-
-
-def _dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(DEV)
-
-
-def _guarded(n, tdtype=torch.float64):
-    return torch.full((n + GUARD,), SENTINEL if tdtype == torch.float64 else -12345, dtype=tdtype, device=DEV)
-
-
-def _intact(buf, n):
-    return bool((buf[n:] == (SENTINEL if buf.dtype == torch.float64 else -12345)).all())
-
-
-def _label_prepare(k, labels, classes):
-    """mvf_assign_label_prepare into a guarded buffer."""
-    from spateo_amd import _lib
-
-    lab32 = _dev(np.asarray(labels), torch.int32)
-    out = _guarded(len(labels))
-    _lib.check(k.lib.mvf_assign_label_prepare(lab32.data_ptr(), len(labels), int(classes), out.data_ptr(), k._stream()),
-               "mvf_assign_label_prepare")
-    torch.cuda.synchronize()
-    assert _intact(out, len(labels))
-    return out[: len(labels)]
-
-
-class _Case:
-    """An edge case on the device: the label layer prepared through the raw entry point, an expression layer (if any)
-    through HipKernels.assign_prepare, and the restatement on the coordinates as stored."""
-
-    def __init__(self, shape, dtype, expression=True):
-        NA, NB, K, L = shape
-        c, k = lab.edge_case(NA, NB, K, L, expression=expression), _k(dtype)
-        self.c, self.k, self.na, self.nb = c, k, NA, NB
-        self.xa4, self.xb4 = k.to_x4(c["XA"]), k.to_x4(c["XB"])
-        self.mm_host, self.outlier = ec.raw_scalars(c)
-        self.mm = _dev(self.mm_host)
-        self.T = _dev(c["label_transfer"])
-        self.layers, host_A, host_B = [], [], []
-        for A, B, met, kind, par in zip(c["layers_A"], c["layers_B"], c["dissimilarity"], c["probability_type"],
-                                        c["probability_parameters"]):
-            if met == "label":
-                a, b = _label_prepare(k, A, K), _label_prepare(k, B, L)
-                assert np.array_equal(a.cpu().numpy(), A.astype(np.float64)) and np.array_equal(b.cpu().numpy(), B.astype(np.float64))
-                self.layers.append((self.T, None, a, b, L, LABEL, PROBS[kind], 0.0))
-                host_A.append(A), host_B.append(B)
-            else:
-                Xp, a, ld = k.assign_prepare(A, ec.METRICS[met], 0)
-                Yp, b, _ = k.assign_prepare(B, ec.METRICS[met], 1)
-                self.layers.append((Xp, Yp, a, b, ld, ec.METRICS[met], PROBS[kind], float(par)))
-                g = A.shape[1]      # the operands as stored ("euc": the features themselves)
-                host_A.append(Xp.double().cpu().numpy()[:, :g]), host_B.append(Yp.double().cpu().numpy()[:, :g])
-        D = c["XA"].shape[1]
-        self.XA, self.XB = self.xa4.double().cpu().numpy()[:, :D], self.xb4.double().cpu().numpy()[:, :D]
-        self.ref = lab.restatement(self.XA, self.XB, host_A, host_B, dissimilarity=c["dissimilarity"],
-                                   probability_type=c["probability_type"], probability_parameters=c["probability_parameters"],
-                                   sigma2=c["sigma2"], alpha=None, SigmaDiag=None, gamma=None, samples_s=None,
-                                   sigma2_variance=c["sigma2_variance"], label_transfer=c["label_transfer"], return_P=True,
-                                   model_mul=self.mm_host, outlier=self.outlier)
-
-    def struct(self, layers=None):
-        from spateo_amd import _lib
-
-        layers = self.layers if layers is None else layers
-        arr = (_lib.AssignLayer * len(layers))()
-        for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, layers):
-            s.Xp, s.Yp, s.a, s.b = (None if t is None else t.data_ptr() for t in (Xp, Yp, a, b))
-            s.ld = int(ld)
-            s.metric, s.prob, s.param = int(metric), int(prob), float(param)
-        return arr
-
-    def call(self, mode="plain", k=0, layers=None, check=True):
-        """mvf_assign ("plain"), mvf_assign_dense ("dense") or mvf_assign_topk ("topk") on guarded buffers and a NaN-filled,
-        guarded workspace of exactly the size the library asks for.  Returns (status, host arrays)."""
-        lib, na, nb, c = self.k.lib, self.na, self.nb, self.c
-        ke = min(k, na)
-        sizes = {"K_NA": na, "K_NB": nb, "K_NA_spatial": na, "K_NA_sigma2": na, "PXB": 3 * na, "scalar": 1}
-        if mode == "dense":
-            sizes["P"] = na * nb
-        if mode == "topk":
-            sizes["vals"] = nb * ke
-        bufs = {q: _guarded(n) for q, n in sizes.items()}
-        rows = _guarded(nb * ke, torch.int32) if mode == "topk" else None
-        need = int(lib.mvf_assign_topk_workspace_bytes(na, nb, k) if mode == "topk" else lib.mvf_assign_workspace_bytes(na, nb))
-        ws = _guarded(need // 8)
-        ws[: need // 8] = float("nan")
-        head = (self.xa4.data_ptr(), na, self.xb4.data_ptr(), nb, self.struct(layers), len(self.layers if layers is None else layers),
-                self.mm.data_ptr(), float(c["sigma2"]), float(c["sigma2_variance"]), float(self.outlier))
-        outs = tuple(bufs[q].data_ptr() for q in ("K_NA", "K_NB", "K_NA_spatial", "K_NA_sigma2", "PXB", "scalar"))
-        tail = (ws.data_ptr(), need, self.k.cdtype, self.k._stream())
-        if mode == "dense":
-            status = lib.mvf_assign_dense(*head, *outs, bufs["P"].data_ptr(), *tail)
-        elif mode == "topk":
-            status = lib.mvf_assign_topk(*head, k, *outs, rows.data_ptr(), bufs["vals"].data_ptr(), *tail)
-        else:
-            status = lib.mvf_assign(*head, *outs, *tail)
-        torch.cuda.synchronize()
-        if status != 0 or not check:
-            return status, None
-        for q, n in sizes.items():
-            assert _intact(bufs[q], n), f"wrote behind {q}[{n}]"
-        assert _intact(ws, need // 8), "wrote behind the workspace"
-        out = {q: bufs[q][:n].cpu().numpy() for q, n in sizes.items()}
-        out["PXB"] = out["PXB"].reshape(na, 3)
-        if mode == "dense":
-            out["P"] = out["P"].reshape(na, nb)
-        if mode == "topk":
-            assert _intact(rows, nb * ke)
-            out["rows"], out["vals"] = rows[: nb * ke].cpu().numpy().reshape(nb, ke), out["vals"].reshape(nb, ke)
-        for q, v in out.items():
-            assert np.isfinite(v).all(), f"{q} is not finite"
-        return status, out
 
 
 def _compare(case, out, what):

@@ -18,16 +18,15 @@ import torch
 import _assign_case as ac
 import _assign_edge_cases as ec
 import _assign_topk_case as tk
-import test_gpu_assign_kernels as base
+from _align_kernel_scaffold import (DEV, DTYPES, GUARD, assign as _assign, device_case as _case, guarded as _guarded,
+                                    intact as _intact, layer_struct as _layer_array, nan_workspace as _nan_workspace,
+                                    same_bits as _same_bits, written as _written)
 
 pytestmark = pytest.mark.gpu
 
-DEV = base.DEV
-DTYPES = base.DTYPES
 SHAPES = [(1, 1, 1), (5, 3, 64), (63, 65, 1), (64, 64, 64), (65, 63, 8), (129, 1, 16), (200, 50, 8), (4097, 10, 4), (300, 1100, 8)]
 ORDERINGS = ("rising", "falling", "last_tile", "duplicates", "far_block")
 OUT = ("K_NA", "K_NB", "K_NA_spatial", "K_NA_sigma2", "PXB", "scalar", "rows", "vals")
-_CASES = {}
 
 
 def _shape_case(na, nb):
@@ -75,55 +74,6 @@ def _ordering_case(kind, na, nb):
     return c
 
 
-class _Case:
-    """A case on the device, every layer prepared BY THE DEVICE, all of it read back (test_gpu_assign_kernels._DeviceCase on a
-    case that is given, not named)."""
-
-    def __init__(self, name, c, dtype):
-        k = base._k(dtype)
-        self.name, self.dtype, self.case, self.k = name, dtype, c, k
-        self.na, self.nb = len(c["XA"]), len(c["XB"])
-        self.xa4, self.xb4 = k.to_x4(c["XA"]), k.to_x4(c["XB"])
-        mm, self.outlier = ec.raw_scalars(c)
-        self.mm, self.mm_host = base._dev(mm), mm
-        self.layers, self.host_layers = [], []
-        for A, B, met, kind, par in zip(c["layers_A"], c["layers_B"], c["dissimilarity"], c["probability_type"],
-                                        c["probability_parameters"]):
-            Xp, a, ld = base._prepare(k, A, met, 0)
-            Yp, b, _ = base._prepare(k, B, met, 1)
-            self.layers.append((Xp, Yp, a, b, ld, ec.METRICS[met], ec.PROBS[kind], 0.0 if par is None else float(par)))
-            self.host_layers.append((Xp.double().cpu().numpy(), Yp.double().cpu().numpy(), a.cpu().numpy(), b.cpu().numpy(),
-                                     met, kind, par))
-        self.xa, self.xb = self.xa4.double().cpu().numpy(), self.xb4.double().cpu().numpy()
-        self._ref = None
-
-    def reference(self):
-        if self._ref is None:
-            c = self.case
-            self._ref = ec.pair_reference(self.xa, self.xb, self.host_layers, self.mm_host, c["sigma2"], c["sigma2_variance"],
-                                          self.outlier)
-            assert "P" in self._ref
-        return self._ref
-
-
-def _case(key, make, dtype):
-    if (key, dtype) not in _CASES:
-        if len(_CASES) >= 4:
-            _CASES.pop(next(iter(_CASES)))
-        _CASES[(key, dtype)] = _Case(str(key), make(), dtype)
-    return _CASES[(key, dtype)]
-
-
-def _layer_array(dc):
-    from spateo_amd import _lib
-
-    arr = (_lib.AssignLayer * len(dc.layers))()
-    for s, (Xp, Yp, a, b, ld, metric, prob, param) in zip(arr, dc.layers):
-        s.Xp, s.Yp, s.a, s.b, s.ld = Xp.data_ptr(), Yp.data_ptr(), a.data_ptr(), b.data_ptr(), int(ld)
-        s.metric, s.prob, s.param = int(metric), int(prob), float(param)
-    return arr
-
-
 def _topk(dc, k, ws=None, ws_bytes=None):
     """mvf_assign_topk through the raw ABI on the current stream; guards behind every output and the workspace (default:
     exactly mvf_assign_topk_workspace_bytes, NaN-filled).  Returns host arrays."""
@@ -132,12 +82,12 @@ def _topk(dc, k, ws=None, ws_bytes=None):
     kk, na, nb = dc.k, dc.na, dc.nb
     ke = min(k, na)
     sizes = {"K_NA": na, "K_NB": nb, "K_NA_spatial": na, "K_NA_sigma2": na, "PXB": 3 * na, "scalar": 1, "vals": nb * ke}
-    bufs = {q: base._guarded(n) for q, n in sizes.items()}
-    rows = torch.full((nb * ke + base.GUARD,), -7, dtype=torch.int32, device=DEV)
+    bufs = {q: _guarded(n) for q, n in sizes.items()}
+    rows = torch.full((nb * ke + GUARD,), -7, dtype=torch.int32, device=DEV)
     need = int(kk.lib.mvf_assign_topk_workspace_bytes(na, nb, k))
     assert need > int(kk.lib.mvf_assign_workspace_bytes(na, nb)) and need % 8 == 0
     if ws is None:
-        ws, ws_bytes = base._nan_workspace(need), need
+        ws, ws_bytes = _nan_workspace(need), need
     c = dc.case
     _lib.check(kk.lib.mvf_assign_topk(dc.xa4.data_ptr(), na, dc.xb4.data_ptr(), nb, _layer_array(dc), len(dc.layers),
                                       dc.mm.data_ptr(), float(c["sigma2"]), float(c["sigma2_variance"]), float(dc.outlier), k,
@@ -146,11 +96,11 @@ def _topk(dc, k, ws=None, ws_bytes=None):
                                       kk._stream()), "mvf_assign_topk")
     torch.cuda.synchronize()
     for q, n in sizes.items():
-        assert base._intact(bufs[q], n), f"{dc.name}: wrote behind {q}[{n}]"
-        assert base._written(bufs[q], n), f"{dc.name}: left an element of {q} unwritten"
+        assert _intact(bufs[q], n), f"{dc.name}: wrote behind {q}[{n}]"
+        assert _written(bufs[q], n), f"{dc.name}: left an element of {q} unwritten"
     assert bool((rows[nb * ke:] == -7).all()), f"{dc.name}: wrote behind rows"
     assert bool((rows[: nb * ke] != -7).all()), f"{dc.name}: left an element of rows unwritten"
-    assert base._intact(ws, ws_bytes // 8), f"{dc.name}: wrote behind the workspace"
+    assert _intact(ws, ws_bytes // 8), f"{dc.name}: wrote behind the workspace"
     out = {q: bufs[q][:n].cpu().numpy() for q, n in sizes.items()}
     out["PXB"], out["scalar"] = out["PXB"].reshape(na, 3), out["scalar"].reshape(())
     out["vals"], out["rows"] = out["vals"].reshape(nb, ke), rows[: nb * ke].cpu().numpy().reshape(nb, ke)
@@ -169,6 +119,7 @@ def _check(dc, got, k):
     """The checker against pair_reference on the device's own operands at the float64 bound, the dense quantities against
     the reference, the far columns."""
     ref = dc.reference()
+    assert "P" in ref
     tk.check(got, ref["P"], dc.xb[:, :3], k, ac.F64_TOL, what=f"{dc.name} {dc.dtype} k {k} plan {ec.plan(dc.na, dc.nb)}")
     for q in ("K_NA_spatial", "K_NA_sigma2", "scalar"):
         top = float(np.abs(ref[q]).max())
@@ -241,7 +192,7 @@ def test_workspace_contents_and_size_do_not_matter(dtype):
     kk = ds.k
     size = max(int(kk.lib.mvf_assign_topk_workspace_bytes(ds.na, ds.nb, 8)),
                int(kk.lib.mvf_assign_topk_workspace_bytes(dl.na, dl.nb, 64))) + 4096
-    ws = base._guarded(size // 8)
+    ws = _guarded(size // 8)
     ws[: size // 8] = 0.0
     zero = _topk(ds, 8, ws=ws, ws_bytes=size)
     ws[: size // 8] = float("nan")
@@ -274,11 +225,11 @@ def test_the_dense_quantities_are_mvf_assigns(dtype, na, nb, k):
     dc = _case((na, nb), lambda: _shape_case(na, nb), dtype)
     got = _topk(dc, k)
     dc.name = f"topk-{na}x{nb}"
-    plain = base._assign(_Plain(dc))
+    plain = _assign(_Plain(dc))
     for q in ("K_NA_spatial", "K_NA_sigma2", "scalar"):
         top = float(np.abs(plain[q]).max())
         dev = float(np.abs(got[q] - plain[q]).max() / top)
-        print(f"  {na}x{nb} k {k} {dtype}: {q} against mvf_assign {dev:.1e}, equal bits: {base._same_bits(got[q], plain[q])}")
+        print(f"  {na}x{nb} k {k} {dtype}: {q} against mvf_assign {dev:.1e}, equal bits: {_same_bits(got[q], plain[q])}")
         assert dev <= ec.REF_TOL, (q, dev)
     assert np.all(got["K_NA"] <= plain["K_NA"] * (1 + 1e-12)) and np.all(got["K_NB"] <= plain["K_NB"] * (1 + 1e-12))
 

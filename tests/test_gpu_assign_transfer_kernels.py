@@ -19,14 +19,12 @@ import torch
 import _assign_case as ac
 import _assign_edge_cases as ec
 import _assign_transfer_case as tc
-import test_gpu_assign_kernels as base
-import test_gpu_assign_label_kernels as labk
-import test_gpu_assign_topk_kernels as tkk
+from _align_kernel_scaffold import (DEV, DTYPES, SENTINEL, LabelCase as _LabelCase, assign as _assign, dev as _dev,
+                                    device_case as _case, guarded as _guarded, intact as _intact,
+                                    layer_struct as _layer_array, nan_workspace as _nan_workspace, written as _written)
 
 pytestmark = pytest.mark.gpu
 
-DEV = base.DEV
-DTYPES = base.DTYPES
 EDGE_SHAPES = [(na, nb) for na in (63, 64, 65, 129) for nb in (1, 65, 200)]
 SPLIT_SHAPES = [(4417, 50), (50, 4417)]
 SHAPES = list(ec.DENSE_SHAPES) + EDGE_SHAPES + SPLIT_SHAPES
@@ -54,7 +52,7 @@ def _strided(F, ld):
     """F on the device in rows of ld >= c doubles, the padding NaN: a kernel that reads it returns NaN."""
     n, c = F.shape
     buf = torch.full((n, ld), float("nan"), dtype=torch.float64, device=DEV)
-    buf[:, :c] = base._dev(F)
+    buf[:, :c] = _dev(F)
     return buf
 
 
@@ -69,7 +67,7 @@ def _apply(dc, FB=None, FA=None, ldfb=None, ldfa=None, k_na=True, k_nb=True, ws=
     need = int(kk.lib.mvf_assign_apply_workspace_bytes(na, nb, cb, ca))
     assert need == tc.workspace_bytes(na, nb, cb, ca) and need % 8 == 0
     if ws is None:
-        ws, ws_bytes = base._nan_workspace(need), need
+        ws, ws_bytes = _nan_workspace(need), need
     sizes = {}
     if FB is not None:
         sizes["to_A"] = na * cb
@@ -79,12 +77,12 @@ def _apply(dc, FB=None, FA=None, ldfb=None, ldfa=None, k_na=True, k_nb=True, ws=
         sizes["to_B"] = nb * ca
     if k_nb:
         sizes["K_NB"] = nb
-    bufs = {q: base._guarded(n) for q, n in sizes.items()}
+    bufs = {q: _guarded(n) for q, n in sizes.items()}
     dFB = None if FB is None else _strided(FB, ldfb)
     dFA = None if FA is None else _strided(FA, ldfa)
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     c = dc.case if hasattr(dc, "case") else dc.c
-    arr = tkk._layer_array(dc) if struct is None else struct
+    arr = _layer_array(dc) if struct is None else struct
     _lib.check(kk.lib.mvf_assign_apply(dc.xa4.data_ptr(), na, dc.xb4.data_ptr(), nb, arr, len(dc.layers), dc.mm.data_ptr(),
                                        float(c["sigma2"]), float(c["sigma2_variance"]), float(dc.outlier), ptr(dFB), cb, ldfb,
                                        ptr(bufs.get("to_A")), ptr(dFA), ca, ldfa, ptr(bufs.get("to_B")), ptr(bufs.get("K_NA")),
@@ -92,9 +90,9 @@ def _apply(dc, FB=None, FA=None, ldfb=None, ldfa=None, k_na=True, k_nb=True, ws=
                "mvf_assign_apply")
     torch.cuda.synchronize()
     for q, n in sizes.items():
-        assert base._intact(bufs[q], n), f"wrote behind {q}[{n}]"
-        assert base._written(bufs[q], n), f"left an element of {q} unwritten"
-    assert base._intact(ws, ws_bytes // 8), "wrote behind the workspace"
+        assert _intact(bufs[q], n), f"wrote behind {q}[{n}]"
+        assert _written(bufs[q], n), f"left an element of {q} unwritten"
+    assert _intact(ws, ws_bytes // 8), "wrote behind the workspace"
     out = {q: bufs[q][:n].cpu().numpy() for q, n in sizes.items()}
     if "to_A" in out:
         out["to_A"] = out["to_A"].reshape(na, cb)
@@ -126,7 +124,7 @@ def _check(got, P, FB, FA, what):
 
 
 def _sums_are_mvf_assigns(dc, got):
-    plain = base._assign(dc)
+    plain = _assign(dc)
     for q in ("K_NA", "K_NB"):
         top = np.abs(plain[q]).max()
         assert np.abs(got[q] - plain[q]).max() <= ac.F64_TOL * top if top > 0 else not got[q].any(), q
@@ -135,7 +133,7 @@ def _sums_are_mvf_assigns(dc, got):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("na,nb", SHAPES)
 def test_shapes_on_the_kernels_edges(dtype, na, nb):
-    dc = tkk._case(("transfer", na, nb), lambda: _shape_case(na, nb), dtype)
+    dc = _case(("transfer", na, nb), lambda: _shape_case(na, nb), dtype)
     cb, ca = (17, 5) if (na + nb) % 2 else (5, 17)
     FB, FA = _features(nb, cb, 1), _features(na, ca, 2)
     got = _apply(dc, FB, FA)
@@ -152,7 +150,7 @@ def test_shapes_on_the_kernels_edges(dtype, na, nb):
 @pytest.mark.parametrize("c", WIDTHS)
 def test_feature_widths_at_the_block_and_chunk_edges(dtype, c):
     na, nb = WIDTH_SHAPE
-    dc = tkk._case(("transfer", na, nb), lambda: _shape_case(na, nb), dtype)
+    dc = _case(("transfer", na, nb), lambda: _shape_case(na, nb), dtype)
     FB, FA = _features(nb, c, 3), _features(na, c, 4)
     ld = c + 7 if c == 17 else None             # once with rows longer than c, NaN behind the columns
     got = _apply(dc, FB, FA, ldfb=ld, ldfa=ld)
@@ -165,7 +163,7 @@ def test_feature_widths_at_the_block_and_chunk_edges(dtype, c):
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_one_direction_only_and_null_sums(dtype):
     na, nb = WIDTH_SHAPE
-    dc = tkk._case(("transfer", na, nb), lambda: _shape_case(na, nb), dtype)
+    dc = _case(("transfer", na, nb), lambda: _shape_case(na, nb), dtype)
     FB, FA = _features(nb, 70, 5), _features(na, 33, 6)
     both = _apply(dc, FB, FA)
     only_A, only_B = _apply(dc, FB=FB), _apply(dc, FA=FA)
@@ -181,7 +179,7 @@ def test_one_direction_only_and_null_sums(dtype):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("g", [1, 16, 17])
 def test_the_k_step(dtype, g):
-    dc = tkk._case(("transfer-g", g), lambda: ec.make_case(f"transfer-g{g}", 70, 66, [("kl", "gauss", None, g)]), dtype)
+    dc = _case(("transfer-g", g), lambda: ec.make_case(f"transfer-g{g}", 70, 66, [("kl", "gauss", None, g)]), dtype)
     FB, FA = _features(66, 9, 7), _features(70, 20, 8)
     got = _apply(dc, FB, FA)
     _check(got, dc.reference()["P"], FB, FA, f"g {g} {dtype}")
@@ -200,7 +198,7 @@ def test_layers_dimensions_and_cells_without_partners(dtype, kind):
     make = {"four-layers": lambda: ec.make_case("transfer-4-layers", 140, 101, list(ec.LAYER_SET)),
             "2d": lambda: ec.make_case("transfer-2d", 70, 66, [("euc", "gauss", None, 24)], D=2, sigma2_variance=2.5),
             "weightless": _weightless_cell}[kind]
-    dc = tkk._case(("transfer", kind), make, dtype)
+    dc = _case(("transfer", kind), make, dtype)
     FB, FA = _features(dc.nb, 6, 9), _features(dc.na, 65, 10)
     got = _apply(dc, FB, FA)
     _check(got, dc.reference()["P"], FB, FA, f"{kind} {dtype}")
@@ -216,13 +214,13 @@ def test_a_label_layer_with_a_non_square_table(dtype):
     """65 x 129 cells, a 7 x 9 table and an expression layer beside it: P @ FB runs on the exchanged operands and must read
     the table as T[label of the A cell][label of the B cell] all the same (a missed transpose reads other entries, or - 7 x 9
     against 9 x 7 - rows that do not exist)."""
-    lc = labk._Case((65, 129, 7, 9), dtype)
+    lc = _LabelCase((65, 129, 7, 9), dtype)
     FB, FA = _features(129, 20, 11), _features(65, 7, 12)
     got = _apply(lc, FB, FA, struct=lc.struct())
     _check(got, lc.ref["P"], FB, FA, f"label 65x129 {dtype}")
     _same(got, _apply(lc, FB, FA, struct=lc.struct()))
     # the label layer alone (no expression layer to mask a slip), the other rectangle
-    lo = labk._Case((65, 129, 4, 1), dtype, expression=False)
+    lo = _LabelCase((65, 129, 4, 1), dtype, expression=False)
     got = _apply(lo, FB, FA, struct=lo.struct())
     _check(got, lo.ref["P"], FB, FA, f"label alone 65x129 {dtype}")
 
@@ -230,13 +228,13 @@ def test_a_label_layer_with_a_non_square_table(dtype):
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_workspace_contents_and_size_do_not_matter(dtype):
     """A larger workspace, zero-filled, NaN-filled and holding a larger call's partials: the same bits."""
-    ds = tkk._case(("transfer", 129, 200), lambda: _shape_case(129, 200), dtype)
-    dl = tkk._case(("transfer", 50, 4417), lambda: _shape_case(50, 4417), dtype)
+    ds = _case(("transfer", 129, 200), lambda: _shape_case(129, 200), dtype)
+    dl = _case(("transfer", 50, 4417), lambda: _shape_case(50, 4417), dtype)
     FB, FA = _features(200, 70, 13), _features(129, 5, 14)
     FBl, FAl = _features(4417, 64, 15), _features(50, 64, 16)
     lib = ds.k.lib
     size = max(int(lib.mvf_assign_apply_workspace_bytes(129, 200, 70, 5)), int(lib.mvf_assign_apply_workspace_bytes(50, 4417, 64, 64))) + 4096
-    ws = base._guarded(size // 8)
+    ws = _guarded(size // 8)
     ws[: size // 8] = 0.0
     zero = _apply(ds, FB, FA, ws=ws, ws_bytes=size)
     ws[: size // 8] = float("nan")
@@ -249,19 +247,19 @@ def test_workspace_contents_and_size_do_not_matter(dtype):
 
 
 def test_argument_errors_are_reported_before_anything_is_launched():
-    dc = tkk._case(("transfer", 65, 63), lambda: _shape_case(65, 63), "float64")
+    dc = _case(("transfer", 65, 63), lambda: _shape_case(65, 63), "float64")
     lib, na, nb, c = dc.k.lib, dc.na, dc.nb, dc.case
     cb, ca = 5, 70
     need = int(lib.mvf_assign_apply_workspace_bytes(na, nb, cb, ca))
-    ws = base._nan_workspace(need)
-    FB, FA = base._dev(_features(nb, cb, 17)), base._dev(_features(na, ca, 18))
-    outs = {"to_A": base._guarded(na * cb), "to_B": base._guarded(nb * ca), "K_NA": base._guarded(na), "K_NB": base._guarded(nb)}
+    ws = _nan_workspace(need)
+    FB, FA = _dev(_features(nb, cb, 17)), _dev(_features(na, ca, 18))
+    outs = {"to_A": _guarded(na * cb), "to_B": _guarded(nb * ca), "K_NA": _guarded(na), "K_NB": _guarded(nb)}
 
     def call(ws_bytes=need, na_=na, nb_=nb, **over):
         a = dict(FB=FB.data_ptr(), cb=cb, ldfb=cb, to_A=outs["to_A"].data_ptr(), FA=FA.data_ptr(), ca=ca, ldfa=ca,
                  to_B=outs["to_B"].data_ptr(), K_NA=outs["K_NA"].data_ptr(), K_NB=outs["K_NB"].data_ptr(), mm=dc.mm.data_ptr())
         a.update(over)
-        rc = lib.mvf_assign_apply(dc.xa4.data_ptr(), na_, dc.xb4.data_ptr(), nb_, tkk._layer_array(dc), len(dc.layers), a["mm"],
+        rc = lib.mvf_assign_apply(dc.xa4.data_ptr(), na_, dc.xb4.data_ptr(), nb_, _layer_array(dc), len(dc.layers), a["mm"],
                                   float(c["sigma2"]), float(c["sigma2_variance"]), float(dc.outlier), a["FB"], a["cb"], a["ldfb"],
                                   a["to_A"], a["FA"], a["ca"], a["ldfa"], a["to_B"], a["K_NA"], a["K_NB"], ws.data_ptr(),
                                   int(ws_bytes), dc.k.cdtype, dc.k._stream())
@@ -275,11 +273,11 @@ def test_argument_errors_are_reported_before_anything_is_launched():
         assert rc != 0 and text in msg, (kw, msg)
     torch.cuda.synchronize()
     for q, buf in outs.items():
-        assert bool((buf == base.SENTINEL[torch.float64]).all()), q
-    assert base._intact(ws, need // 8) and bool(torch.isnan(ws[: need // 8]).all())       # nothing was launched
+        assert bool((buf == SENTINEL[torch.float64]).all()), q
+    assert _intact(ws, need // 8) and bool(torch.isnan(ws[: need // 8]).all())       # nothing was launched
     assert call(na_=0)[0] == 0 and call(nb_=0)[0] == 0                                     # an empty side: nothing to do
     torch.cuda.synchronize()
-    assert bool((outs["to_A"] == base.SENTINEL[torch.float64]).all())
+    assert bool((outs["to_A"] == SENTINEL[torch.float64]).all())
     assert call()[0] == 0
     torch.cuda.synchronize()
-    assert base._written(outs["to_A"], na * cb) and base._written(outs["to_B"], nb * ca)
+    assert _written(outs["to_A"], na * cb) and _written(outs["to_B"], nb * ca)

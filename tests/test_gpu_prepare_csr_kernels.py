@@ -13,41 +13,20 @@ import pytest
 import torch
 
 import _assign_edge_cases as ec
+from _align_kernel_scaffold import DEV, guarded, intact as _intact, kernels as _k
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 CELL_DTYPES = ["float64", "float32"]
 DATA_DTYPES = [np.float64, np.float32]
 PRODUCT_METRICS = ["euc", "square_euc", "kl", "sym_kl", "cos"]
 NS = [1, 3, 4, 5, 257]
 GS = [1, 15, 16, 17, 63, 64, 65, 130]
-GUARD = 1024
-_KERNELS = {}
-
-
-def _k(dtype):
-    if dtype not in _KERNELS:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _KERNELS[dtype] = HipKernels(DEV, dtype)
-    return _KERNELS[dtype]
-
-
-def _sentinel(tdtype):
-    return -1.2345e300 if tdtype == torch.float64 else -12345.0
 
 
 def _guarded(n, tdtype=torch.float64):
     """n elements of NaN in front of GUARD sentinels."""
-    buf = torch.full((n + GUARD,), _sentinel(tdtype), dtype=tdtype, device=DEV)
-    buf[:n] = float("nan")
-    return buf
-
-
-def _intact(buf, n):
-    return bool((buf[n:] == _sentinel(buf.dtype)).all())
+    return guarded(n, tdtype, fill=float("nan"))
 
 
 def make_csr(n, g, data_dtype, seed):
