@@ -254,7 +254,13 @@ size_t mvf_solve_minnorm_basis_bytes(int64_t m);
  * stopping tolerance); the first rejected column ends the use of the hint and the greedy steps finish.  The result does
  * not depend on the hint being good: a stale or foreign order is rejected column by column, a workspace without a
  * finished order ignores the hint.  reuse != 0: apply the decomposition of the previous call on this workspace to another
- * R (einfo[7..11] = this call's).  NOT asynchronous (status reads during the factorisation, one per Jacobi sweep). */
+ * R (einfo[7..11] = this call's).  reuse reads the workspace's state record first and is refused, with a non-zero return and
+ * before anything is launched, unless the record carries the mark of a finished factorisation with 0 <= r <= m columns - the
+ * same test mvf_lr_pivot_order and mvf_pinv_diag apply; mvf_solve_minnorm_lrd's reuse likewise.  That turns away a fresh,
+ * zeroed or overwritten workspace and one whose last call stopped in the factorisation (non-finite input: the mark is
+ * cleared when a factorisation starts and set when it ends).  It is not a proof that the record belongs to this matrix or
+ * this m: the caller passes the workspace of the previous call, as for the rank hint.
+ * NOT asynchronous (status reads during the factorisation, one per Jacobi sweep). */
 size_t mvf_solve_minnorm_lr_workspace_bytes(int64_t m, int nrhs);
 int mvf_solve_minnorm_lr(const double* G, const double* K, double lambda_sigma2, double tolf, double rcond,
                          const double* R, int64_t m, int nrhs, double* C, int* info, double* einfo, int max_sweeps,

@@ -2334,6 +2334,10 @@ static int lr_solve(const double* G, const double* K, double lambda_sigma2, doub
         // the workspace still holds the decomposition of the previous call for this matrix
         MVF_CHECK_HIP(rb_copy(st, &hs, stt, sizeof(hs)));
         MVF_CHECK_HIP(rb_sync(st));
+        // (the same test as mvf_lr_pivot_order and mvf_pinv_diag: a fresh, zeroed or foreign workspace is refused on the host,
+        // before anything is launched - hs.r sizes every launch below)
+        MVF_REQUIRE(hs.magic == PCHOL_MAGIC && hs.r >= 0 && hs.r <= m,
+                    "mvf_solve_minnorm_lr: reuse: the workspace holds no finished decomposition");
         MVF_CHECK_HIP(hipMemsetAsync(info, 0, sizeof(int), st));
         if (hs.r <= 0) {
             MVF_CHECK_HIP(hipMemsetAsync(C, 0, (size_t)m * nrhs * sizeof(double), st));
