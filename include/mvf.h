@@ -66,7 +66,8 @@ int mvf_read_back(void* dst_host, const void* src_device, size_t nbytes, void* s
  * S2^-1 in its block inverse iteration), "lr_no_direct" (1: mvf_solve_minnorm_lrd never takes its direct form),
  * "direct_accept" (v > 0: the direct form accepts at most v - 1 deflated directions), "lr_timing" (1: phase times of
  * mvf_solve_minnorm_lr on stderr), "gram_reg_cols" (1: the float32 cached Gram tile stage takes gram_cached_kernel<float>, every
- * wave widening its own column operands, instead of the kernel that shares them through LDS).  Unknown name: non-zero return.  mvf_debug_option_get returns -1 for an unknown name. */
+ * wave widening its own column operands, instead of the kernel that shares them through LDS; 2 / 3: the sharing kernel with one
+ * workgroup per job / with persistent workgroups, whatever the number of jobs).  Unknown name: non-zero return.  mvf_debug_option_get returns -1 for an unknown name. */
 int mvf_debug_option(const char* name, long long value);
 long long mvf_debug_option_get(const char* name);
 int mvf_device_count(int* count);      /* number of visible HIP devices (0 without a GPU) */

@@ -93,7 +93,10 @@ static GramPlan make_plan(int64_t n, int64_t m, mvf_dtype dtype) {
         // the capped slices need more partial tiles than the buffer holds: several launches ("phases") reuse it, each
         // folded into G before the next one starts (8 M cells x 3000: 977 slices of 8 k cells in 2 (float64) / 4 (float32)
         // phases).  Searching shorter slices / more phases by a tail model measured WORSE (56 instead of 61 TF in float64):
-        // every phase boundary drains the chip.
+        // every phase boundary drains the chip, and every job boundary left its slot empty for a while.  (The float32 tile
+        // stage now keeps its workgroups across jobs, gram_cached_kernel_shared_cols_persistent: - 7.1 ms per launch of 139
+        // rounds, the same gain per job with one launch as with four - the cost was the job turnover, not the drained tail;
+        // the plan itself is unchanged, profiles/gram_persistent_ab.md.)
         // Slices up to 10 % longer than the cap are accepted if that saves a launch (977 = 4 x 244 + 1 slices would
         // otherwise take a fifth phase for one slice).
         int64_t s = s_cap;
@@ -822,17 +825,14 @@ __device__ __forceinline__ void cached_block_shared(const float* __restrict__ ub
             }
 }
 
-__global__ __launch_bounds__(256, 2) void gram_cached_kernel_shared_cols(const float* __restrict__ ublk, const double* __restrict__ P,
-                                                                         int64_t n, int64_t n_pad, int64_t m, int nt, int npairs,
-                                                                         int64_t slice_len, int64_t slice0,
-                                                                         double* __restrict__ partial) {
-    // job decode, slices and partial-tile layout of gram_cached_kernel<float>; all LDS of the kernel is this one ring
-    __shared__ double sc_ring[SC_RING_DOUBLES];
+// One job of the shared-column tile stage: job = slice * npairs + pair, as blockIdx.x of the per-job launch; job decode, slices and
+// partial-tile layout of gram_cached_kernel<float>.
+__device__ __forceinline__ void shared_cols_job(unsigned job, int wave, unsigned lds0, const float* __restrict__ ublk,
+                                                const double* __restrict__ P, int64_t n, int64_t n_pad, int64_t m, int nt,
+                                                int npairs, int64_t slice_len, int64_t slice0, double* __restrict__ partial) {
     constexpr int TB = GT / UB;
-    const unsigned lds0 = (unsigned)(uintptr_t)sc_ring;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int pair = blockIdx.x % npairs;
-    const int64_t slice = blockIdx.x / npairs;
+    const int pair = job % npairs;
+    const int64_t slice = job / npairs;
     int ti, tj;
     decode_pair(pair, nt, ti, tj);
     const int64_t n0 = (slice0 + slice) * slice_len;
@@ -855,12 +855,54 @@ __global__ __launch_bounds__(256, 2) void gram_cached_kernel_shared_cols(const f
     }
 }
 
+__global__ __launch_bounds__(256, 2) void gram_cached_kernel_shared_cols(const float* __restrict__ ublk, const double* __restrict__ P,
+                                                                         int64_t n, int64_t n_pad, int64_t m, int nt, int npairs,
+                                                                         int64_t slice_len, int64_t slice0,
+                                                                         double* __restrict__ partial) {
+    // one workgroup per job; all LDS of the kernel is this one ring
+    __shared__ double sc_ring[SC_RING_DOUBLES];
+    const unsigned lds0 = (unsigned)(uintptr_t)sc_ring;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    shared_cols_job(blockIdx.x, wave, lds0, ublk, P, n, n_pad, m, nt, npairs, slice_len, slice0, partial);
+}
+
+// Persistent launch of the same jobs: min(njobs, resident slots) workgroups, each of which takes job numbers from a counter
+// in global memory until they run out (the host zeroes it ahead of the launch, widen_p_kernel).  Job j is what workgroup j of
+// the per-job launch computes, so the partial tiles and with them G are the same bits whatever the order.  A workgroup never
+// waits for another one: it takes the next number or leaves; the kernel has no loop whose exit depends on another workgroup.
+// Its first job is its own index and the counter hands out gridDim.x, gridDim.x + 1, ...: still slice-major, so resident
+// workgroups stream the same slices.  The number reaches the other waves through an LDS word that thread 0 writes behind the
+// job, one barrier more per job ahead of the read; the next write comes behind the next job, in which every wave passes at least
+// one barrier after it has read the word.  The same barriers order the ring: cached_block_shared reads the ring for the last
+// time ahead of a barrier that every wave passes, and the next job writes it behind that.
+__global__ __launch_bounds__(256, 2) void gram_cached_kernel_shared_cols_persistent(
+    const float* __restrict__ ublk, const double* __restrict__ P, int64_t n, int64_t n_pad, int64_t m, int nt, int npairs,
+    int64_t slice_len, int64_t slice0, double* __restrict__ partial, unsigned* __restrict__ counter, unsigned njobs) {
+    __shared__ double sc_ring[SC_RING_DOUBLES];
+    __shared__ unsigned sc_next;
+    const unsigned lds0 = (unsigned)(uintptr_t)sc_ring;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    unsigned job = blockIdx.x;  // (< njobs: the grid is no larger)
+    while (job < njobs) {
+        // the next number is taken one job ahead: the atomic's round trip runs under this job, and the barrier below waits for
+        // LDS only (a wait for the returned value behind the epilogue would wait for the 64 stores ahead of it as well)
+        unsigned taken = 0;
+        if (threadIdx.x == 0) taken = atomicAdd(counter, 1u);
+        shared_cols_job(job, wave, lds0, ublk, P, n, n_pad, m, nt, npairs, slice_len, slice0, partial);
+        if (threadIdx.x == 0) sc_next = gridDim.x + taken;
+        sc_barrier();
+        job = __builtin_amdgcn_readfirstlane(sc_next);
+    }
+}
+
 // Pd[i - c0] = (double)P[i] for the cells c0 <= i < c1 of a phase (multiples of 256), 0 for the padded cells i >= n (whose
-// cached rows are zero as well)
+// cached rows are zero as well).  `counter` (may be null): the job counter of the persistent tile kernel that follows on the
+// stream, zeroed here by one thread so that no launch or memset node of its own is needed.
 __global__ __launch_bounds__(256) void widen_p_kernel(const float* __restrict__ P, int64_t n, int64_t c0, int64_t c1,
-                                                      double* __restrict__ Pd) {
+                                                      double* __restrict__ Pd, unsigned* __restrict__ counter) {
     const int64_t i = c0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < c1) Pd[i - c0] = i < n ? (double)P[i] : 0.0;
+    if (counter && blockIdx.x == 0 && threadIdx.x == 0) *counter = 0u;
 }
 
 // ----------------------------------------------------------------------------------------------------------------
@@ -1143,8 +1185,19 @@ extern "C" int mvf_gram_cached(int stages, const void* ublk, const void* x4, con
             if (dtype == MVF_F32) {
                 // this phase's cells [c0, c1) of P, widened; the tile kernel indexes P by absolute cell
                 const int64_t c0 = s0 * p.slice_len, c1 = std::min(n_pad, c0 + ns * p.slice_len);
+                // "gram_reg_cols": 0 = the shared-column kernel, persistent where a launch has more than two rounds of jobs
+                // (below that every slot gets its jobs at once or nearly so, and the per-job launch is what was measured);
+                // 1 = the register-operand kernel; 2 / 3 = the shared-column kernel per job / persistent, whatever the size
+                const long long cols_opt = debug_opt(DBG_GRAM_REG_COLS);
+                const unsigned slots = (unsigned)gram_slots();
+                const bool persistent = cols_opt == 3 || (cols_opt == 0 && njobs > 2 * slots);
+                // The persistent kernel's job counter is the low word of element (127, 0) of the phase's first partial tile:
+                // pair 0 is the diagonal tile (0, 0), of which the shared-column kernel stores and gram_reduce_kernel reads only
+                // the blocks on or above the diagonal, so nothing else touches that word while the tile stage runs and the
+                // workspace keeps its size.  widen_p_kernel zeroes it ahead of every phase's launch.
+                unsigned* const counter = persistent ? (unsigned*)((double*)workspace + (GT - 1) * GT) : nullptr;
                 hipLaunchKernelGGL(widen_p_kernel, dim3((unsigned)((c1 - c0) / 256)), dim3(256), 0, st, (const float*)P, n,
-                                   c0, c1, pd);
+                                   c0, c1, pd, counter);
                 // Both kernels index P by ABSOLUTE cell, so they get the buffer's address biased by - c0: for every phase but
                 // the first that address lies BELOW the workspace.  Valid only because neither reads it outside [c0, c1): a
                 // job's cells are [n0, n1) with c0 <= n0 and n1 <= c1.  gram_cached_kernel<float> clamps the index of its
@@ -1152,8 +1205,12 @@ extern "C" int mvf_gram_cached(int stages, const void* ublk, const void* x4, con
                 // cells: c0 < n); gram_cached_kernel_shared_cols reads P through a buffer resource based at cell n0 whose
                 // records end at min(n1, n): reads behind it return 0 (the same exact 0 in G: those cached rows are zero).
                 const double* Pd = (const double*)((uintptr_t)pd - (uintptr_t)c0 * sizeof(double));
-                // same grid, jobs and partial tiles either way; "gram_reg_cols" forces the register-operand kernel
-                if (debug_opt(DBG_GRAM_REG_COLS) == 0) {
+                // same jobs and partial tiles whichever kernel runs them
+                if (persistent) {
+                    hipLaunchKernelGGL(gram_cached_kernel_shared_cols_persistent, dim3(std::min(njobs, slots)), dim3(256), 0, st,
+                                       (const float*)ublk, Pd, n, n_pad, m, p.nt, p.npairs, p.slice_len, s0, (double*)workspace,
+                                       counter, njobs);
+                } else if (cols_opt != 1) {
                     hipLaunchKernelGGL(gram_cached_kernel_shared_cols, dim3(njobs), dim3(256), 0, st, (const float*)ublk, Pd, n,
                                        n_pad, m, p.nt, p.npairs, p.slice_len, s0, (double*)workspace);
                 } else {
