@@ -426,6 +426,22 @@ int mvf_ublk_build_d(const void* x, int64_t n, const void* ctrl, int64_t m, int 
 int mvf_eval_d(const void* x, int64_t n, const void* ctrl, int64_t m, int d, double beta, const double* C, int dy,
                int flags, double* v, double* jac, double* div, double* acc, double* curv, mvf_dtype dtype, void* stream);
 
+/* ---- wide fields at new points: values and spatial gradients (mvf_eval_wide.hip) ----------------------------------------
+ * One addition to the table (mvf_version stays 7 by the addition rule stated at mvf_align_moments).
+ * v = K @ C and J[f][i][q] = d v_f / d x_i = -2 beta sum_m K(x_q, c_m) C[m, f] (x_q - c_m)_i for a field of ANY number of
+ * output columns dy at d = 1, 2 or 3: the field `kernel_interpolation` fits (Y = the selected obs columns and genes).
+ * x4: n x 4 and ctrl4: m x 4 (dtype), as mvf_eval takes them: centred by the caller, unused coordinates zero; K(x, c) is the
+ * value mvf_eval sees.  C: m x dy float64, row-major, row stride ldc >= dy (so a column panel is `C + f0` with the same ldc).
+ * flags: a non-empty subset of MVF_EVAL_V | MVF_EVAL_JAC.  v: n x dy float64 with row stride ldv >= dy, the columns
+ * dy .. ldv - 1 are not touched;  jac: (dy, d, n) contiguous float64 = J[f][i][q], the reference's layout.  An output that
+ * is not requested may be NULL.  1 + d matrix-core products of a generated n x m operand with C (float64 accumulation), one
+ * workgroup over all m per tile: no atomics, two calls give identical bits.  Arguments are validated before any HIP call;
+ * n == 0 or dy == 0 launches nothing, m == 0 writes zeros.
+ * Replaces: dynamo `vector_field_function` / `Jacobian_rkhs_gaussian` for Dy = #keys on the field fitted at
+ * spateo/tdr/interpolations/interpolation_sparseVFC.py:63 (Jacobian twin: morphofield_dg/GPVectorField.py:143-190). */
+int mvf_eval_wide(const void* x4, int64_t n, const void* ctrl4, int64_t m, int d, double beta, const double* C, int64_t ldc,
+                  int dy, int flags, double* v, int64_t ldv, double* jac, mvf_dtype dtype, void* stream);
+
 /* ---- trajectory integration (morphopath) ------------------------------------------------------------------------
  * Integrates dx/dt = v(x), v as in mvf_eval_affine, from the n start points x4 with classical RK4: n_out samples per
  * trajectory, `dt` apart, `substeps` RK4 steps between samples; traj (float64) = [n][n_out][3], traj[:, 0] = start.

@@ -1133,6 +1133,27 @@ class HipKernels:
         return out
 
     @_on_device
+    def eval_wide(self, x4, ctrl4, d, beta, C, flags):
+        """Values and spatial gradients of a field with any number of output columns at d <= 3 (mvf_eval_wide): x4 (n, 4) and
+        ctrl4 (m, 4) from to_x4, C (m, dy) float64 device tensor with unit column stride - a column slice of a wider matrix
+        is passed as it is, its row stride is the kernel's ldc.  flags: EVAL_V | EVAL_JAC.  Returns {flag: float64 device
+        tensor}: v (n, dy), jac (dy, d, n)."""
+        n, m = x4.shape[0], ctrl4.shape[0]
+        if C.dim() != 2 or C.shape[0] != m or C.dtype != torch.float64 or (C.shape[1] > 1 and C.stride(1) != 1):
+            raise ValueError(f"eval_wide: expected float64 coefficients ({m}, dy) with unit column stride, got "
+                             f"{tuple(C.shape)} {C.dtype} strides {tuple(C.stride())}")
+        if x4.dtype != self.tdtype or ctrl4.dtype != self.tdtype:
+            raise TypeError(f"eval_wide: expected {self.tdtype} points, got {x4.dtype} / {ctrl4.dtype}")
+        dy = C.shape[1]
+        ldc = max(int(C.stride(0)), dy) if m > 1 else dy
+        shapes = {_lib.EVAL_V: (n, dy), _lib.EVAL_JAC: (dy, int(d), n)}
+        out = {f: torch.empty(*s, dtype=torch.float64, device=self.device) for f, s in shapes.items() if flags & f}
+        _lib.check(self.lib.mvf_eval_wide(_ptr(x4), n, _ptr(ctrl4), m, int(d), float(beta), _ptr(C), ldc, dy, int(flags),
+                                          _ptr(out.get(_lib.EVAL_V)), dy, _ptr(out.get(_lib.EVAL_JAC)), self.cdtype,
+                                          self._stream()), "mvf_eval_wide")
+        return out
+
+    @_on_device
     def eval_d(self, xd, ctrld, beta, C, flags):
         """Fused evaluator for 4 <= d <= 8 (mvf_eval_d): xd (n, d), ctrld (m, d) from to_xd, C (m, dy) float64 device
         tensor, dy <= 8.  Returns {flag: float64 device tensor}: v (n, dy), jac (dy, d, n), and for dy == d div (n,),

@@ -108,6 +108,7 @@ SIGNATURES = {
                              _p]),
     "mvf_ublk_build_d": (_i, [_p, _i64, _p, _i64, _i, _d, _p, _sz, _i, _p]),
     "mvf_eval_d": (_i, [_p, _i64, _p, _i64, _i, _d, _p, _i, _i, _p, _p, _p, _p, _p, _i, _p]),
+    "mvf_eval_wide": (_i, [_p, _i64, _p, _i64, _i, _d, _p, _i64, _i, _i, _p, _i64, _p, _i, _p]),
     "mvf_integrate": (_i, [_p, _i64, _p, _i64, _d, _p, C.POINTER(C.c_double), _d, _i, _i, _p, _i, _p]),
     "mvf_integrate_rk45": (_i, [_p, _i64, _p, _i64, _d, _p, C.POINTER(C.c_double), _i, C.POINTER(C.c_double), _d, _d,
                                 _d, _d, _i, _i, _i, _p, _p, _p, _i, _p]),

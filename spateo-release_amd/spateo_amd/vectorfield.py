@@ -170,7 +170,7 @@ def _field_on_device(x, vf_dict, flags, dtype=None, device=None, rows3=False):
     if d > 3:
         return _field_on_device_d(x, Xc, Cc, vf_dict, flags, dtype, device)
     if Cc.shape[1] > 3:
-        raise NotImplementedError("the HIP evaluators support up to 3 output columns on fields of up to 3 dimensions")
+        return _field_on_device_wide(x, Xc, Cc, vf_dict, flags, dtype, device)
     k = _shared_kernels(device, dtype)
     beta = float(vf_dict["beta"])
 
@@ -184,6 +184,51 @@ def _field_on_device(x, vf_dict, flags, dtype=None, device=None, rows3=False):
         return k.eval(x4, c4, beta, Cd, fl)
 
     return _fused_eval(x, ("svc", Xc, Cc, beta), flags, k, launch, rows3)
+
+
+# mvf_eval_wide's outputs of one column chunk (v: n x cols, jac: cols x d x n, float64) stay under this many bytes on the
+# device; a chunk is copied into the host arrays as it finishes.  Whole 64-column panels of the kernel while they fit.
+_EVAL_WIDE_CHUNK_BYTES = 256 << 20
+_EVAL_WIDE_PANEL = 64
+
+
+def _wide_chunk_cols(n, per_col):
+    """Columns per chunk of the wide evaluator: as many as keep n * per_col float64 per column under the cap, at least one."""
+    cols = max(1, _EVAL_WIDE_CHUNK_BYTES // max(1, 8 * n * per_col))
+    return cols - cols % _EVAL_WIDE_PANEL if cols >= _EVAL_WIDE_PANEL else cols
+
+
+def _field_on_device_wide(x, Xc, Cc, vf_dict, flags, dtype, device):
+    """_field_on_device for d <= 3 and more than 3 output columns (mvf_eval_wide): the field `kernel_interpolation` fits, one
+    column per key.  Values and the Jacobian (dy, d, n) only - dy != d, so nothing else is defined.  Not behind `_fused_eval`:
+    nothing is prefetched and no result (gigabytes, at thousands of genes) is kept on the device."""
+    d, dy = Xc.shape[1], Cc.shape[1]
+    if flags & ~(_lib.EVAL_V | _lib.EVAL_JAC):
+        raise ValueError(f"divergence, acceleration, curvature, curl, torsion and the determinant need a field with as many "
+                         f"output columns as dimensions ({dy} != {d})")
+    k = _shared_kernels(device, dtype)
+    beta = float(vf_dict["beta"])
+    n = len(x)
+    center = Xc.mean(0)
+    x4, c4 = k.to_x4(x, center), k.to_x4(Xc, center)
+    Cd = k.h2d(np.ascontiguousarray(Cc))
+    out = {}
+    if flags & _lib.EVAL_V:
+        out[_lib.EVAL_V] = np.empty((n, dy))
+    if flags & _lib.EVAL_JAC:
+        out[_lib.EVAL_JAC] = np.empty((dy, d, n))
+    cols = _wide_chunk_cols(n, (1 if flags & _lib.EVAL_V else 0) + (d if flags & _lib.EVAL_JAC else 0))
+    for f0 in range(0, dy, cols):
+        f1 = min(f0 + cols, dy)
+        dev = k.eval_wide(x4, c4, d, beta, Cd[:, f0:f1], flags)
+        fl = list(dev)
+        for f, h in zip(fl, _to_host(k, [dev[f] for f in fl])):
+            if f == _lib.EVAL_V:
+                out[f][:, f0:f1] = h
+            else:
+                out[f][f0:f1] = h
+        del dev
+    return out
 
 
 _EVAL_D_FLAGS = _lib.EVAL_V | _lib.EVAL_JAC | _lib.EVAL_DIV | _lib.EVAL_ACC | _lib.EVAL_CURV
@@ -449,13 +494,21 @@ class SvcVectorField:
         X = np.asarray(X, dtype=np.float64)
         return _field_on_device(X, self.vf_dict, flags, self._dtype, self._device, rows3)
 
+    def _wide_outputs(self):
+        """True for a field of more than 3 output columns at d <= 3: the one `_field_on_device` hands to mvf_eval_wide."""
+        vf = self.vf_dict
+        if not isinstance(vf, dict) or "C" not in vf or "X_ctrl" not in vf:
+            return False
+        return np.asarray(vf["X_ctrl"]).shape[1] <= 3 and np.asarray(vf["C"]).shape[1] > 3
+
     @staticmethod
     def _check_method(method):
         if method != "analytical":
             raise NotImplementedError("only method='analytical' is supported (numdifftools path is out of scope)")
 
     def get_Jacobian(self, method="analytical", **kwargs):
-        """Returns ``f(x) -> (d, d, n)`` (``(d, d)`` for a 1-D x); ``J[f, i] = d f_f / d x_i``."""
+        """Returns ``f(x) -> (d, d, n)`` (``(d, d)`` for a 1-D x); ``J[f, i] = d f_f / d x_i``.  A field with dy > 3 output
+        columns at d <= 3 (``kernel_interpolation``'s) gives ``(dy, d, n)`` / ``(dy, d)``, the reference's layout."""
         self._check_method(method)
 
         def jac(x):
@@ -463,7 +516,9 @@ class SvcVectorField:
             one = x.ndim == 1
             xx = x[None, :] if one else x
             d = xx.shape[1]
-            J = self._eval(xx, _lib.EVAL_JAC)[_lib.EVAL_JAC][:d, :d, :]
+            J = self._eval(xx, _lib.EVAL_JAC)[_lib.EVAL_JAC]
+            if not self._wide_outputs():
+                J = J[:d, :d, :]
             return J[:, :, 0] if one else J
 
         return jac
@@ -475,6 +530,9 @@ class SvcVectorField:
         self._check_method(method)
         X = np.asarray(X, dtype=np.float64)
         d = X.shape[1]
+        if self._wide_outputs():
+            raise ValueError(f"the determinant of the Jacobian needs a field with as many output columns as dimensions "
+                             f"({np.asarray(self.vf_dict['C']).shape[1]} != {d})")
         o = self._eval(X, _lib.EVAL_JAC | (_lib.EVAL_JDET if d == 3 else 0))
         J = o[_lib.EVAL_JAC][:d, :d, :]
         if d == 3:
