@@ -745,6 +745,54 @@ int mvf_ublk_pack_csr(const int64_t* indptr, const int32_t* indices, const void*
                       const double* mu, int64_t n_total, int64_t row0, void* ublk, size_t ublk_bytes, void* staging,
                       size_t staging_bytes, mvf_dtype dtype, void* stream);
 
+/* ---- down-sampling: TRN, nearest row, k-means (mvf_sample.hip) -------------------------------------------------------------
+ * Five additions to the table (mvf_version stays 7 by the rule above).  Float64 arithmetic whatever the package's cell dtype -
+ * the samplers return indices -, every sum of squares ((d0 d0) + d1 d1) + d2 d2 without fused multiply-add, no atomics, every
+ * output element written by one lane with ordinary vector stores: two calls give bit-identical results.  Rows have 1 <= d <= 3
+ * float64 columns, row-major, no padding.  Arguments are validated before any HIP call. */
+#define MVF_TRN_MAX_NODES 4096
+/* One TRN problem: every pointer a DEVICE pointer.  X (N x d); w_idx (n int64): the start draw, W starts as X[w_idx]; p_idx
+ * (T int64): the sample of every step; l, ep (T float64): the step's schedule values, computed by the HOST as the reference
+ * computes them; kc (T float64, NULL when the cutoff c is 0): -l log(c / ep); W (n x d): the nodes, out.  A row index outside
+ * [0, N) is clamped into it before it is used as an address. */
+typedef struct mvf_trn_problem {
+    const double* X;
+    int64_t N;
+    int64_t d;
+    int64_t n;
+    int64_t T;
+    const int64_t* w_idx;
+    const int64_t* p_idx;
+    const double* l;
+    const double* ep;
+    const double* kc;
+    double* W;
+} mvf_trn_problem;
+/* Replaces: `TRNET.run` / `TRNET.runOnce` (spateo/alignment/methods/sampling.py:103-155) for `nproblems` slices at once.
+ * problems: HOST array.  One workgroup per problem runs all T steps, strictly in order, the nodes in registers; per step
+ *   D = p - W;  sD_i = ((D_i0 D_i0) + D_i1 D_i1) + D_i2 D_i2;  k_i = #{j : (sD_j, j) < (sD_i, i)}  (the stable rank: the lower
+ *   node first among equal distances);  W_i += (ep exp(-k_i / l)) D_i  for every node (kc NULL) or for k_i < kc.
+ * Up to 32 problems share a launch (more: one launch per 32); no workgroup waits on another.  n <= MVF_TRN_MAX_NODES; a problem
+ * with n == 0 is skipped, nproblems == 0 launches nothing. */
+int mvf_trn(const mvf_trn_problem* problems, int nproblems, void* stream);
+/* Replaces: the nearest-neighbour query that turns nodes into cells - `k_nearest_neighbors(X, query_X=W, k=0)` of `trn`
+ * (sampling.py:214-222) and `nearest_neighbors(C, X, k=1)` of `sample_by_kmeans` (:255).  idx[i] (n int64) = the row of X
+ * (N x d) nearest to Q[i] (n x d): exact, the smallest index among equal squared distances.  workspace:
+ * mvf_nearest_rows_workspace_bytes(N, n) (0 up to 4096 rows), 8-byte aligned.  n == 0 launches nothing. */
+size_t mvf_nearest_rows_workspace_bytes(int64_t N, int64_t n);
+int mvf_nearest_rows(const double* X, int64_t N, int d, const double* Q, int64_t n, int64_t* idx, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* Replaces: `scipy.cluster.vq.kmeans2(X, C0, iter, minit="matrix", missing="warn")` of `sample_by_kmeans` (sampling.py:254).
+ * C (n x d): the start matrix in, the centroids out.  `iter` >= 1 Lloyd steps are queued on the stream with no host round trip
+ * between them: labels (N int32) = argmin of the squared distance, the first centroid among equal ones (vq's rule); centroid =
+ * sum of its members / their number, the sum taken over fixed blocks of rows (a function of N alone) in row order and the
+ * blocks in order; a cluster without members keeps its centroid.  labels are those of the last step's assignment (made with the
+ * centroids BEFORE its update, as kmeans2 returns them), counts (n int64) their histogram.  workspace:
+ * mvf_kmeans_workspace_bytes(N, n), 8-byte aligned.  N == 0 or n == 0 launches nothing. */
+size_t mvf_kmeans_workspace_bytes(int64_t N, int64_t n);
+int mvf_kmeans(const double* X, int64_t N, int d, double* C, int64_t n, int iter, int32_t* labels, int64_t* counts,
+               void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,3 +70,18 @@ class AnnDataLite:
         for k, v in self.obs.items():
             new.obs[k] = v
         return new
+
+    def select_obs(self, idx):
+        """A copy restricted to the cells ``idx`` (integer positions, in their order, repeats allowed: ``adata[idx, :]``):
+        ``obs``, ``obsm``, ``X`` and every layer row-selected - a sparse matrix as CSR -, ``var``, ``var_names`` and ``uns``
+        carried over (``uns`` copied, so the subset's results do not land in the parent)."""
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < -self.n_obs or idx.max() >= self.n_obs):
+            raise IndexError(f"cell positions must lie inside 0 .. {self.n_obs}")
+        take = lambda m: m.tocsr()[idx] if _is_sparse(m) else m[idx]  # noqa: E731
+        new = AnnDataLite(obsm={k: np.asarray(v)[idx] for k, v in self.obsm.items()}, uns=copy.deepcopy(self.uns), n_obs=len(idx),
+                          X=None if self.X is None else take(self.X), var_names=list(self.var_names),
+                          layers={k: take(v) for k, v in self.layers.items()}, var=dict(self.var))
+        for k, v in self.obs.items():
+            new.obs[k] = v.iloc[idx].reset_index(drop=True) if hasattr(v, "iloc") else v[idx]
+        return new

@@ -935,6 +935,57 @@ class HipKernels:
                                                     float(step), _ptr(PXB_term), _ptr(Y4), _ptr(Pw), self.cdtype, self._stream()),
                    "mvf_align_transform_svi")
 
+    # ---- down-sampling (mvf_sample.hip): float64 whatever the cell dtype, host arrays in, host arrays out ----
+    def _f64_rows(self, X):
+        return self.h2d(np.ascontiguousarray(X, dtype=np.float64))
+
+    @_on_device
+    def trn(self, problems):
+        """mvf_trn for a list of problems in one call: each a dict with X (N, d), w_idx (n,), p_idx (T,) int64 and the
+        schedules l, ep (T,), kc (T,) or None.  Returns the list of node matrices W (n, d), host float64."""
+        recs = (_lib.TrnProblem * max(len(problems), 1))()
+        keep, outs = [], []
+        for rec, pr in zip(recs, problems):
+            X = self._f64_rows(pr["X"])
+            n, T = len(pr["w_idx"]), len(pr["p_idx"])
+            dev = [self.h2d(np.ascontiguousarray(pr[k], dtype=np.int64)) for k in ("w_idx", "p_idx")]
+            dev += [self.h2d(np.ascontiguousarray(pr[k], dtype=np.float64)) for k in ("l", "ep")]
+            kc = None if pr.get("kc") is None else self.h2d(np.ascontiguousarray(pr["kc"], dtype=np.float64))
+            W = self.empty(n, X.shape[1], dtype=torch.float64)
+            rec.X, rec.N, rec.d, rec.n, rec.T = _ptr(X), X.shape[0], X.shape[1], n, T
+            rec.w_idx, rec.p_idx, rec.l, rec.ep, rec.kc, rec.W = _ptr(dev[0]), _ptr(dev[1]), _ptr(dev[2]), _ptr(dev[3]), _ptr(kc), _ptr(W)
+            keep.append((X, dev, kc))
+            outs.append(W)
+        _lib.check(self.lib.mvf_trn(recs, len(problems), self._stream()), "mvf_trn")
+        return [np.array(w) for w in self.to_host(outs, own_pinned=False)] if outs else []
+
+    @_on_device
+    def nearest_rows(self, X, Q):
+        """mvf_nearest_rows: for every row of Q (n, d) the index of the nearest row of X (N, d), the smallest among equal
+        distances; host int64 (n,)."""
+        Xd, Qd = self._f64_rows(X), self._f64_rows(Q)
+        N, n = Xd.shape[0], Qd.shape[0]
+        need = int(self.lib.mvf_nearest_rows_workspace_bytes(N, n))
+        ws = self.empty(max(need // 8, 1), dtype=torch.float64)
+        idx = self.empty(n, dtype=torch.int64)
+        _lib.check(self.lib.mvf_nearest_rows(_ptr(Xd), N, Xd.shape[1], _ptr(Qd), n, _ptr(idx), _ptr(ws), ws.numel() * 8,
+                                             self._stream()), "mvf_nearest_rows")
+        return np.array(self.d2h(idx))
+
+    @_on_device
+    def kmeans(self, X, C0, iters):
+        """mvf_kmeans: `iters` Lloyd steps from the start matrix C0 (n, d) on X (N, d), all queued at once.  Returns host
+        (centroids (n, d) float64, labels (N,) int32, counts (n,) int64)."""
+        Xd, Cd = self._f64_rows(X), self._f64_rows(np.array(C0, dtype=np.float64))
+        N, n = Xd.shape[0], Cd.shape[0]
+        need = int(self.lib.mvf_kmeans_workspace_bytes(N, n))
+        ws = self.empty(max(need // 8, 1), dtype=torch.float64)
+        labels, counts = self.empty(N, dtype=torch.int32), self.empty(n, dtype=torch.int64)
+        _lib.check(self.lib.mvf_kmeans(_ptr(Xd), N, Xd.shape[1], _ptr(Cd), n, int(iters), _ptr(labels), _ptr(counts), _ptr(ws),
+                                       ws.numel() * 8, self._stream()), "mvf_kmeans")
+        C, lab, cnt = self.to_host([Cd, labels, counts], own_pinned=False)
+        return np.array(C), np.array(lab), np.array(cnt)
+
     # ---- PCA across slices on the kernel-value cache (mvf_pca.hip + the cached Gram / apply kernels, unchanged) ----
     PCA_UPLOAD_BYTES = 256 << 20  # rows of a dense slice travel in chunks of at most this much (each chunk is a slice of its own)
 

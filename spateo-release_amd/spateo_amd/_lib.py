@@ -41,6 +41,7 @@ ALIGN_MOMENT_DOUBLES = 64
 # grid.y = nt (nt + 1) / 2 <= 65535  ->  nt <= 361), and mvf_apply_cached projects at most 128 columns per pass over the cache
 PCA_MAX_FEATURES = 361 * 128
 PCA_MAX_COMPS = 128
+TRN_MAX_NODES = 4096  # MVF_TRN_MAX_NODES: mvf_trn keeps the nodes of a problem in one workgroup's registers, their keys in its LDS
 EVAL_V, EVAL_JAC, EVAL_DIV, EVAL_CURL, EVAL_ACC, EVAL_CURV, EVAL_TORS, EVAL_JDET = 1, 2, 4, 8, 16, 32, 64, 128
 
 _p, _i64, _i, _d, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_size_t
@@ -51,6 +52,12 @@ class AssignLayer(C.Structure):
     """mvf_assign_layer of include/mvf.h: one prepared expression / representation layer (device pointers)."""
     _fields_ = [("Xp", C.c_void_p), ("Yp", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("ld", C.c_int64),
                 ("metric", C.c_int), ("prob", C.c_int), ("param", C.c_double)]
+
+
+class TrnProblem(C.Structure):
+    """mvf_trn_problem of include/mvf.h: one TRN problem (device pointers, sizes)."""
+    _fields_ = [("X", C.c_void_p), ("N", C.c_int64), ("d", C.c_int64), ("n", C.c_int64), ("T", C.c_int64), ("w_idx", C.c_void_p),
+                ("p_idx", C.c_void_p), ("l", C.c_void_p), ("ep", C.c_void_p), ("kc", C.c_void_p), ("W", C.c_void_p)]
 
 
 # name -> (restype, argtypes); mirrors include/mvf.h one to one
@@ -146,6 +153,11 @@ SIGNATURES = {
     "mvf_ublk_pack": (_i, [_p, _i, _i64, _i64, _p, _i64, _i64, _p, _sz, _i, _p]),
     "mvf_colmeans_csr": (_i, [_p, _p, _p, _i, _i64, _i64, _i64, _i64, _p, _p, _sz, _p, _sz, _p]),
     "mvf_ublk_pack_csr": (_i, [_p, _p, _p, _i, _i64, _i64, _p, _i64, _i64, _p, _sz, _p, _sz, _i, _p]),
+    "mvf_trn": (_i, [C.POINTER(TrnProblem), _i, _p]),
+    "mvf_nearest_rows_workspace_bytes": (_sz, [_i64, _i64]),
+    "mvf_nearest_rows": (_i, [_p, _i64, _i, _p, _i64, _p, _p, _sz, _p]),
+    "mvf_kmeans_workspace_bytes": (_sz, [_i64, _i64]),
+    "mvf_kmeans": (_i, [_p, _i64, _i, _p, _i64, _i, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None
