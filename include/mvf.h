@@ -793,6 +793,81 @@ size_t mvf_kmeans_workspace_bytes(int64_t N, int64_t n);
 int mvf_kmeans(const double* X, int64_t N, int d, double* C, int64_t n, int iter, int32_t* labels, int64_t* counts,
                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- mesh correction: batched 2-D ICP, the cut of a transformed surface mesh (mvf_icp.hip) -------------------------------
+ * Five additions to the table (mvf_version stays 7 by the rule above).  The conventions are the sampling section's: float64
+ * arithmetic whatever the package's cell dtype, no fused multiply-add, no atomics, every output element written by one lane
+ * with ordinary vector stores, two calls give bit-identical results, the lower index wins among equal distances.  Every sum
+ * over points is taken in one fixed order: a lane of the 256 adds its points j = lane, lane + 256 in that order, the 64 lanes
+ * of a wave fold by halving (i += i + 32, 16, .. 1), the four waves add in wave order.  Arguments are validated before any HIP
+ * call.  Contours are row-major n x 2 float64 and must hold finite numbers.
+ *
+ * Thinning: a contour of n > subsample points (subsample > 0) is reduced to the rows floor(j n / subsample), j = 0 ..
+ * subsample - 1.  A deviation: the reference draws `np.random.choice(n, subsample, replace=False)` from the global generator,
+ * which cannot be pinned; a caller that wants that draw passes contours it has thinned itself. */
+#define MVF_ICP_MAX_POINTS 512
+/* One ICP problem: every pointer a DEVICE pointer.  contour_1 (n1 x 2): the data; contour_2 (n2 x 2): the model, the one that
+ * moves; gamma (1 float64), stats (2 int32: the rounds run, the inliers of the last query): out; T_contour_2 (min(n2,
+ * subsample) x 2 float64, may be NULL): the transformed - thinned - model points in the frame of contour_1, out; translation
+ * (2 float64, may be NULL): what the reference returns for allow_rotation == 0 (:494), scale t + centre_1 - centre_2 with the t
+ * of the LAST round (0 when that round found fewer than 3 inliers), out. */
+typedef struct mvf_icp_problem {
+    const double* contour_1;
+    int64_t n1;
+    const double* contour_2;
+    int64_t n2;
+    double* gamma;
+    int32_t* stats;
+    double* T_contour_2;
+    double* translation;
+} mvf_icp_problem;
+/* Replaces: `ICP` (spateo/alignment/methods/mesh_correction_utils.py:404-498) up to its line 492, for D = 2 and `nproblems`
+ * pairs of contours at once; the closing `solve_RT_by_correspondence` (:496) stays with the host.  problems: HOST array, copied
+ * to `workspace` on the stream (it must stay untouched until the stream has passed the call).  One workgroup per problem, both
+ * thinned contours in LDS:
+ *   centre each at its mid-range (max + min) / 2, divide both by scale = (rms_1 + rms_2) / 2;  T = the model;  up to max_iter
+ *   rounds:  d_j = the distance from T_j to its exact nearest data point;  inliers: d_j < inlier_threshold;  fewer than 3 of
+ *   them: stop, T stays;  else the means of the inliers and of their partners, the translation between them
+ *   (allow_rotation == 0) or R = V U^T of the 2 x 2 covariance H = U S V^T - the closed-form orthogonal polar factor of H^T, a
+ *   reflection when det H < 0: the reference's loop corrects no determinant - and t = mean_1 - R mean_T;  T = R T + t;  stop
+ *   when the mean inlier distance moved by less than error_threshold.
+ *   gamma = #{d_j < gamma_threshold} / M with the distances of the last query;  T_contour_2 = scale T + centre_1.
+ * max_iter >= 1; n1, n2 >= 1; min(n, subsample) <= MVF_ICP_MAX_POINTS (subsample <= 0: no thinning).  Up to 4096 problems share
+ * a launch; no workgroup waits on another.  workspace: mvf_icp_batch_workspace_bytes(nproblems), 8-byte aligned.  nproblems == 0
+ * launches nothing. */
+size_t mvf_icp_batch_workspace_bytes(int64_t nproblems);
+int mvf_icp_batch(const mvf_icp_problem* problems, int64_t nproblems, int max_iter, double error_threshold,
+                  double inlier_threshold, double gamma_threshold, int subsample, int allow_rotation, void* workspace,
+                  size_t workspace_bytes, void* stream);
+/* Replaces: `_calculate_loss` (mesh_correction_utils.py:371-401) with `_transform_points` (:27-85),
+ * `_extract_contours_from_mesh` (:224-238) and one `ICP(c, m_c, allow_rotation=True)` per slice under it, for n_T candidate
+ * transformations at once (`_get_binary_values`, :350-367, calls it label_num^2 times per pair of parameters).
+ * verts (V x 3 float64), edges (E x 2 int32: the unique edges of the triangles, built once by the host; an index outside
+ * [0, V) is clamped into it), params (n_T x 5 float64: rotation about x, y, z in degrees, z translation, scale), heights (n_S),
+ * contours (contour_total x 2: the slices' contours packed), offsets (n_S + 1 int64: slice s owns the rows offsets[s] ..
+ * offsets[s + 1], clamped into [0, contour_total]): DEVICE.  mean: HOST double[3], the vertex mean.  Per transformation:
+ *   p' = scale ((p - mean) (R_z R_y R_x)^T) + mean;  p'_z += translation - on z of EVERY vertex, what the reference's docstring
+ *   says (its line :83 adds it to the first two rows instead);
+ *   per height h: one point per edge whose ends classify differently under z >= h (VTK's contour rule: a vertex on the plane is
+ *   above it), a + ((h - z_a) / (z_b - z_a)) (b - a) in x and y, in edge-index order; thinned; the ICP above with that slice's
+ *   contour as the data;
+ *   loss = (sum over slices, in order, of (1 - gamma)) / n_S, or 1e6 / n_S when any height cuts no edge (:397-399).
+ * One workgroup per (transformation, slice), at most 4096 transformations per launch.  loss (n_T); gamma (n_T x n_S, 0 where
+ * nothing is cut) and count (n_T x n_S int32: the contour sizes before thinning) may be NULL.  1 <= subsample <=
+ * MVF_ICP_MAX_POINTS; 1 <= n_S < 2^24.  workspace: mvf_mesh_loss_workspace_bytes(n_T, n_S), 16-byte aligned, bounded by the launch chunk.
+ * n_T == 0 launches nothing. */
+size_t mvf_mesh_loss_workspace_bytes(int64_t n_T, int64_t n_S);
+int mvf_mesh_loss(const double* verts, int64_t V, const int32_t* edges, int64_t E, const double* mean, const double* params,
+                  int64_t n_T, const double* heights, const double* contours, const int64_t* offsets, int64_t contour_total,
+                  int64_t n_S, int max_iter, double error_threshold, double inlier_threshold, double gamma_threshold,
+                  int subsample, double* loss, double* gamma, int32_t* count, void* workspace, size_t workspace_bytes,
+                  void* stream);
+/* Replaces: `_extract_contours_from_mesh` (mesh_correction_utils.py:224-238: `mesh.contour(isosurfaces=z_values)`) after
+ * `_transform_points`, for one transformation.  param: HOST double[5] as a row of params above; mean: HOST double[3].  Slice s
+ * gets counts[s] (int32) = the number of crossing edges and its first min(counts[s], capacity) points at points[s][0 ..]
+ * (n_S x capacity x 2 float64; 1 <= n_S < 2^24), the rest of the row untouched: the same points, in the same order, the loss kernel cuts. */
+int mvf_mesh_contours(const double* verts, int64_t V, const int32_t* edges, int64_t E, const double* mean, const double* param,
+                      const double* heights, int64_t n_S, int64_t capacity, double* points, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

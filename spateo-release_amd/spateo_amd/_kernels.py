@@ -5,6 +5,7 @@ device tensors.  Nothing here computes on the host and nothing falls back to tor
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import NamedTuple
 
 import numpy as np
@@ -985,6 +986,106 @@ class HipKernels:
                                        ws.numel() * 8, self._stream()), "mvf_kmeans")
         C, lab, cnt = self.to_host([Cd, labels, counts], own_pinned=False)
         return np.array(C), np.array(lab), np.array(cnt)
+
+    # ---- mesh correction (mvf_icp.hip): float64 whatever the cell dtype, host arrays in, host arrays out ----
+    @staticmethod
+    def _pack_rows(arrays, width):
+        """(the arrays stacked into one (total, width) float64 matrix, offsets (len + 1,) int64 of their first rows)."""
+        offsets = np.zeros(len(arrays) + 1, dtype=np.int64)
+        np.cumsum([len(a) for a in arrays], out=offsets[1:])
+        flat = np.concatenate(arrays, axis=0) if arrays else np.zeros((0, width))
+        return np.ascontiguousarray(flat, dtype=np.float64).reshape(-1, width), offsets
+
+    @_on_device
+    def icp_batch(self, contours_1, contours_2, max_iter, error_threshold, inlier_threshold, gamma_threshold, subsample,
+                  allow_rotation, want_T=True):
+        """mvf_icp_batch for lists of (n, 2) float64 contours, one launch per 4096 pairs.  Returns host arrays gamma (P,), stats
+        (P, 2) int32 (rounds, inliers of the last query), translation (P, 2) and the list of T_contour_2 (None without want_T)."""
+        P = len(contours_1)
+        if P == 0:
+            return np.zeros(0), np.zeros((0, 2), dtype=np.int32), np.zeros((0, 2)), ([] if want_T else None)
+        c1, o1 = self._pack_rows(contours_1, 2)
+        c2, o2 = self._pack_rows(contours_2, 2)
+        n1, n2 = np.diff(o1), np.diff(o2)
+        m2 = np.where((subsample > 0) & (n2 > subsample), subsample, n2)  # rows of every T_contour_2
+        oT = np.zeros(P + 1, dtype=np.int64)
+        np.cumsum(m2, out=oT[1:])
+        d1, d2 = self.h2d(c1), self.h2d(c2)
+        gamma, stats = self.empty(P, dtype=torch.float64), self.empty(P, 2, dtype=torch.int32)
+        shift = self.empty(P, 2, dtype=torch.float64)
+        T = self.empty(max(int(oT[-1]), 1), 2, dtype=torch.float64) if want_T else None
+        recs = np.zeros(P, dtype=np.dtype([(f, np.int64) for f, _ in _lib.IcpProblem._fields_]))
+        assert recs.dtype.itemsize == C.sizeof(_lib.IcpProblem)
+        recs["contour_1"], recs["n1"] = _ptr(d1) + o1[:-1] * 16, n1
+        recs["contour_2"], recs["n2"] = _ptr(d2) + o2[:-1] * 16, n2
+        recs["gamma"] = _ptr(gamma) + np.arange(P, dtype=np.int64) * 8
+        recs["stats"] = _ptr(stats) + np.arange(P, dtype=np.int64) * 8
+        recs["translation"] = _ptr(shift) + np.arange(P, dtype=np.int64) * 16
+        recs["T_contour_2"] = (_ptr(T) + oT[:-1] * 16) if want_T else 0
+        need = int(self.lib.mvf_icp_batch_workspace_bytes(P))
+        ws = self.empty(max(need // 8, 1), dtype=torch.float64)
+        _lib.check(self.lib.mvf_icp_batch(recs.ctypes.data_as(C.POINTER(_lib.IcpProblem)), P, int(max_iter), float(error_threshold),
+                                          float(inlier_threshold), float(gamma_threshold), int(subsample), int(bool(allow_rotation)),
+                                          _ptr(ws), ws.numel() * 8, self._stream()), "mvf_icp_batch")
+        outs = self.to_host([gamma, stats, shift] + ([T] if want_T else []), own_pinned=False)  # (synchronises: recs may go)
+        g, st, sh = (np.array(o) for o in outs[:3])
+        Ts = None
+        if want_T:
+            Th = np.array(outs[3])
+            Ts = [Th[oT[i]:oT[i + 1]] for i in range(P)]
+        return g, st, sh, Ts
+
+    def mesh_upload(self, points, edges):
+        """The device copies (verts (V, 3) float64, edges (E, 2) int32) of a mesh, for the two calls below."""
+        return self.h2d(np.ascontiguousarray(points, dtype=np.float64)), self.h2d(np.ascontiguousarray(edges, dtype=np.int32))
+
+    @_on_device
+    def mesh_loss(self, dev_mesh, mean, params, heights, contours, max_iter, error_threshold, inlier_threshold, gamma_threshold,
+                  subsample):
+        """mvf_mesh_loss: params (n_T, 5), heights (n_S,), contours: list of n_S (n, 2) arrays.  Returns host (loss (n_T,), gamma
+        (n_T, n_S), count (n_T, n_S) int32)."""
+        verts, edges = dev_mesh
+        params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 5)
+        nT, nS = len(params), len(heights)
+        if nT == 0:
+            return np.zeros(0), np.zeros((0, nS)), np.zeros((0, nS), dtype=np.int32)
+        flat, off = self._pack_rows(list(contours), 2)
+        dp, dh, dc, do = self.h2d(params), self.h2d(np.ascontiguousarray(heights, dtype=np.float64)), self.h2d(flat), self.h2d(off)
+        loss, gamma = self.empty(nT, dtype=torch.float64), self.empty(nT, nS, dtype=torch.float64)
+        count = self.empty(nT, nS, dtype=torch.int32)
+        need = int(self.lib.mvf_mesh_loss_workspace_bytes(nT, nS))
+        ws = self.empty(max(need // 8, 2), dtype=torch.float64)
+        m3 = (C.c_double * 3)(*[float(v) for v in mean])
+        _lib.check(self.lib.mvf_mesh_loss(_ptr(verts), verts.shape[0], _ptr(edges), edges.shape[0], m3, _ptr(dp), nT, _ptr(dh), _ptr(dc),
+                                          _ptr(do), flat.shape[0], nS, int(max_iter), float(error_threshold), float(inlier_threshold),
+                                          float(gamma_threshold), int(subsample), _ptr(loss), _ptr(gamma), _ptr(count), _ptr(ws),
+                                          ws.numel() * 8, self._stream()), "mvf_mesh_loss")
+        return tuple(np.array(o) for o in self.to_host([loss, gamma, count], own_pinned=False))
+
+    @_on_device
+    def mesh_contours(self, dev_mesh, mean, param, heights):
+        """mvf_mesh_contours: the list of n_S (n, 2) contours of the mesh under one transformation (5 numbers), whole.  Two
+        calls: with capacity 0 for the counts, then with the largest count as the capacity."""
+        verts, edges = dev_mesh
+        nS = len(heights)
+        dh = self.h2d(np.ascontiguousarray(heights, dtype=np.float64))
+        counts = self.empty(nS, dtype=torch.int32)
+        m3 = (C.c_double * 3)(*[float(v) for v in mean])
+        p5 = (C.c_double * 5)(*[float(v) for v in param])
+
+        def call(cap, pts):
+            _lib.check(self.lib.mvf_mesh_contours(_ptr(verts), verts.shape[0], _ptr(edges), edges.shape[0], m3, p5, _ptr(dh), nS, cap,
+                                                  _ptr(pts), _ptr(counts), self._stream()), "mvf_mesh_contours")
+
+        call(0, None)
+        cnt = np.array(self.d2h(counts))
+        cap = int(cnt.max())
+        if cap == 0:
+            return [np.zeros((0, 2)) for _ in range(nS)]
+        pts = self.empty(nS, cap, 2, dtype=torch.float64)
+        call(cap, pts)
+        host = np.array(self.d2h(pts))
+        return [host[s, : cnt[s]].copy() for s in range(nS)]
 
     # ---- PCA across slices on the kernel-value cache (mvf_pca.hip + the cached Gram / apply kernels, unchanged) ----
     PCA_UPLOAD_BYTES = 256 << 20  # rows of a dense slice travel in chunks of at most this much (each chunk is a slice of its own)

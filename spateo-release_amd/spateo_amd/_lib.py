@@ -42,6 +42,7 @@ ALIGN_MOMENT_DOUBLES = 64
 PCA_MAX_FEATURES = 361 * 128
 PCA_MAX_COMPS = 128
 TRN_MAX_NODES = 4096  # MVF_TRN_MAX_NODES: mvf_trn keeps the nodes of a problem in one workgroup's registers, their keys in its LDS
+ICP_MAX_POINTS = 512  # MVF_ICP_MAX_POINTS: mvf_icp_batch / mvf_mesh_loss keep both (thinned) contours of a problem in one workgroup's LDS
 EVAL_V, EVAL_JAC, EVAL_DIV, EVAL_CURL, EVAL_ACC, EVAL_CURV, EVAL_TORS, EVAL_JDET = 1, 2, 4, 8, 16, 32, 64, 128
 
 _p, _i64, _i, _d, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_size_t
@@ -58,6 +59,12 @@ class TrnProblem(C.Structure):
     """mvf_trn_problem of include/mvf.h: one TRN problem (device pointers, sizes)."""
     _fields_ = [("X", C.c_void_p), ("N", C.c_int64), ("d", C.c_int64), ("n", C.c_int64), ("T", C.c_int64), ("w_idx", C.c_void_p),
                 ("p_idx", C.c_void_p), ("l", C.c_void_p), ("ep", C.c_void_p), ("kc", C.c_void_p), ("W", C.c_void_p)]
+
+
+class IcpProblem(C.Structure):
+    """mvf_icp_problem of include/mvf.h: one pair of contours (device pointers, sizes) and its outputs."""
+    _fields_ = [("contour_1", C.c_void_p), ("n1", C.c_int64), ("contour_2", C.c_void_p), ("n2", C.c_int64), ("gamma", C.c_void_p),
+                ("stats", C.c_void_p), ("T_contour_2", C.c_void_p), ("translation", C.c_void_p)]
 
 
 # name -> (restype, argtypes); mirrors include/mvf.h one to one
@@ -158,6 +165,12 @@ SIGNATURES = {
     "mvf_nearest_rows": (_i, [_p, _i64, _i, _p, _i64, _p, _p, _sz, _p]),
     "mvf_kmeans_workspace_bytes": (_sz, [_i64, _i64]),
     "mvf_kmeans": (_i, [_p, _i64, _i, _p, _i64, _i, _p, _p, _p, _sz, _p]),
+    "mvf_icp_batch_workspace_bytes": (_sz, [_i64]),
+    "mvf_icp_batch": (_i, [C.POINTER(IcpProblem), _i64, _i, _d, _d, _d, _i, _i, _p, _sz, _p]),
+    "mvf_mesh_loss_workspace_bytes": (_sz, [_i64, _i64]),
+    "mvf_mesh_loss": (_i, [_p, _i64, _p, _i64, C.POINTER(C.c_double), _p, _i64, _p, _p, _p, _i64, _i64, _i, _d, _d, _d, _i, _p, _p,
+                           _p, _p, _sz, _p]),
+    "mvf_mesh_contours": (_i, [_p, _i64, _p, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), _p, _i64, _i64, _p, _p, _p]),
 }
 
 _lib = None

@@ -23,7 +23,8 @@ from .vectorfield import vector_field_function
 __all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate", "morpho_iterate_svi",
            "optimal_mapping", "mapping_from_best", "apply_assignment", "label_transfer_matrix", "init_sigma2", "init_probability_parameters", "coarse_rigid_alignment", "morpho_start",
            "Morpho_pairwise", "morpho_align", "pca", "group_pca", "trn", "sample_by_kmeans", "sample", "downsampling",
-           "solve_RT_by_correspondence", "morpho_align_transformation", "morpho_align_apply_transformation", "morpho_align_ref"]
+           "solve_RT_by_correspondence", "morpho_align_transformation", "morpho_align_apply_transformation", "morpho_align_ref",
+           "icp", "icp_batch", "mesh_contours", "mesh_correction_loss", "Mesh_correction"]
 
 RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
 
@@ -1779,3 +1780,5 @@ from ._morpho_pairwise import Morpho_pairwise, morpho_align  # noqa: E402
 # ... and its reference-model route with the samplers under it
 from ._downsampling import (downsampling, morpho_align_apply_transformation, morpho_align_ref,  # noqa: E402
                             morpho_align_transformation, sample, sample_by_kmeans, solve_RT_by_correspondence, trn)
+# ... and the correction of the aligned stack against a surface mesh
+from ._mesh_correction import Mesh_correction, icp, icp_batch, mesh_contours, mesh_correction_loss  # noqa: E402
