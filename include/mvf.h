@@ -868,6 +868,42 @@ int mvf_mesh_loss(const double* verts, int64_t V, const int32_t* edges, int64_t 
 int mvf_mesh_contours(const double* verts, int64_t V, const int32_t* edges, int64_t E, const double* mean, const double* param,
                       const double* heights, int64_t n_S, int64_t capacity, double* points, int32_t* counts, void* stream);
 
+/* ---- density of the cloud: the fused log of a kernel sum per (target, group of sources) (mvf_kde.hip) -------------------
+ * Two additions to the table (mvf_version stays 7 by the rule above).  The six kernels of sklearn.neighbors.KernelDensity, with
+ * r = dist / h and sklearn's strict support dist < h for the four compact ones:  log K = -r^2 / 2 | -r | 0 | log(1 - r^2) |
+ * log(1 - r) | log cos(pi r / 2). */
+enum {
+    MVF_KDE_GAUSSIAN = 0,
+    MVF_KDE_EXPONENTIAL = 1,
+    MVF_KDE_TOPHAT = 2,
+    MVF_KDE_EPANECHNIKOV = 3,
+    MVF_KDE_LINEAR = 4,
+    MVF_KDE_COSINE = 5
+};
+#define MVF_KDE_MAX_COLUMNS 64
+/* Replaces: `KernelDensity(kernel=kernel, bandwidth=bandwidth).fit(coords).score_samples(coords)` of `pc_KDE`
+ * (spateo/tdr/morphometrics/morphology.py:109), without its normalising constants: the caller adds log_norm(h, d, kernel) -
+ * log(sum of the group's weights).  t4 (n x 4 targets), s4 (N x 4 sources): x4 layout of `dtype`, both centred by the caller
+ * with the same centre; d in {1, 2, 3} (the unused coordinates are 0).  weight (N float64; NULL = 1): finite, zero or a normal
+ * positive number.  group (N int32; NULL = every source in column 0): a source whose group lies outside [0, C) belongs to no
+ * column.  1 <= C <= MVF_KDE_MAX_COLUMNS (the caller runs more columns in chunks).
+ *   out[i, c] (n x C float64) = log sum_{j: group[j] == c, w_j > 0} w_j K(|t_i - s_j| / h), -inf when no such source is in
+ *   reach (an empty group, all weights zero, a compact kernel with every distance >= h).
+ * Every distance is formed from the coordinate differences in float64 whatever `dtype` (the storage of the coordinates only);
+ * exponent, sum and logarithm are float64.  Two passes over tiles of 256 sources: the largest log term log w_j + log K_ij per
+ * (target, column) first - log K at the nearest source when the weights are equal -, then sum_j exp(log w_j + log K_ij - that),
+ * whose largest term is 1: a target 40 bandwidths from every source gets -800 - .., not log 0.  The compact kernels take the
+ * largest weight in reach as their shift and add (w_j / shift) K_ij without an exp.  No atomics: the sources are split over
+ * workgroups (a number fixed by n and N alone: at least 4096 sources each, about 1024 workgroups per column), the partials go to the workspace and are folded in split order; within a split a target's
+ * terms are added in source order; two calls give equal bits.  workspace: mvf_kde_workspace_bytes(n, N, C), 8-byte aligned.
+ * Refused: "bad shape" (n, N < 0, d outside 1 .. 3, C outside 1 .. 64, h <= 0 or not finite), "bad kernel", "bad dtype", "null
+ * pointer", "workspace too small".  n == 0 or C == 0 returns 0 before anything is looked at; N == 0 fills out with -inf. */
+int mvf_kde(const void* t4, int64_t n, const void* s4, int64_t N, int d, int kernel, double h, const double* weight,
+            const int32_t* group, int C, double* out, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+/* Replaces: the memory `score_samples` (morphology.py:109) takes for itself.  (splits + 1) x n x C float64: the splits' partials
+ * and the shifts; 0 for an empty or refused shape. */
+size_t mvf_kde_workspace_bytes(int64_t n, int64_t N, int C);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1087,6 +1087,32 @@ class HipKernels:
         host = np.array(self.d2h(pts))
         return [host[s, : cnt[s]].copy() for s in range(nS)]
 
+    # ---- density of the cloud (mvf_kde.hip): centred host arrays in, a host (n, C) float64 array out ----
+    @_on_device
+    def kde(self, targets, sources, kernel, bandwidth, weight=None, group=None, C=1):
+        """mvf_kde: out[i, c] = log sum over the sources j of column c (group[j] == c; one column without `group`) of
+        w_j K(|t_i - s_j| / bandwidth), unnormalised, -inf where nothing is in reach.  targets (n, d), sources (N, d): host
+        float64, d <= 3, centred by the caller (they are rounded to the cell dtype here; every distance is float64); weight (N,)
+        float64 or None; group (N,) integers in [0, C) or None.  The columns run in chunks of KDE_MAX_COLUMNS."""
+        t4, s4 = self.to_x4(targets), self.to_x4(sources)
+        n, N, d, C = int(t4.shape[0]), int(s4.shape[0]), int(np.shape(sources)[1]), int(C)
+        w = None if weight is None else self.h2d(np.ascontiguousarray(weight, dtype=np.float64))
+        g = None if group is None else self.h2d(np.ascontiguousarray(group, dtype=np.int32))
+        out = self.empty(n, C, dtype=torch.float64)
+        ws = None
+        for c0 in range(0, C, _lib.KDE_MAX_COLUMNS):
+            cc = min(_lib.KDE_MAX_COLUMNS, C - c0)
+            need = int(self.lib.mvf_kde_workspace_bytes(n, N, cc))
+            if ws is None or ws.numel() * 8 < need:
+                ws = self.empty(max(need // 8, 1), dtype=torch.float64)
+            part = out if cc == C else self.empty(n, cc, dtype=torch.float64)
+            gc = g if (g is None or c0 == 0) else g - c0   # a source of another chunk falls outside [0, cc): in no column
+            _lib.check(self.lib.mvf_kde(_ptr(t4), n, _ptr(s4), N, d, _lib.KDE_KERNELS[kernel], float(bandwidth), _ptr(w), _ptr(gc), cc,
+                                        _ptr(part), _ptr(ws), ws.numel() * 8, self.cdtype, self._stream()), "mvf_kde")
+            if part is not out:
+                out[:, c0 : c0 + cc] = part
+        return np.array(self.d2h(out))
+
     # ---- PCA across slices on the kernel-value cache (mvf_pca.hip + the cached Gram / apply kernels, unchanged) ----
     PCA_UPLOAD_BYTES = 256 << 20  # rows of a dense slice travel in chunks of at most this much (each chunk is a slice of its own)
 

@@ -15,3 +15,4 @@ from .morphofield_dg import (
     morphofield_torsion,
     morphofield_velocity,
 )
+from .morphology import cell_density, kernel_density, pc_KDE
