@@ -1,86 +1,18 @@
 """Scaffolding of the kernel-level GPU tests of the alignment path (tests/test_gpu_assign*_kernels.py,
-test_gpu_align*_kernels.py, test_gpu_prepare_csr_kernels.py): the cached ``HipKernels`` per cell dtype, guarded buffers and
-their checks, the bit comparison, the table of largest deviations, and the device cases and raw-ABI calls that several of
-those modules share.  No test module imports another one: what two of them need lives here."""
+test_gpu_align*_kernels.py, test_gpu_prepare_csr_kernels.py): the ``HipKernels`` per cell dtype that those nine modules share,
+and the device cases and raw-ABI calls that several of them need.  What knows nothing about the alignment path - guarded
+buffers, bit comparisons, the table of largest deviations - lives in tests/_kernel_scaffold.py and is imported from there.
+No test module imports another one: what two of them need lives here."""
 import numpy as np
-import pytest
 import torch
 
 import _assign_edge_cases as ec
 import _assign_label_case as lab
+from _kernel_scaffold import dev, guarded, intact, kernel_cache, nan_workspace, written
 
-DEV = "cuda:0"
-DTYPES = ["float64", "float32"]
-GUARD = 4096  # elements behind every buffer
-SENTINEL = {torch.float64: -1.2345e300, torch.float32: -1.2345e30, torch.uint8: 0xA5, torch.int32: -12345}
 LABEL, PROBS = 5, {"gauss": 0, "cos": 1, "prob": 2}  # MVF_ASSIGN_LABEL and the probability types of include/mvf.h
-_KERNELS = {}
+kernels = kernel_cache()  # one cache for the nine alignment modules
 _CASES = {}
-
-
-def kernels(dtype):
-    if dtype not in _KERNELS:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _KERNELS[dtype] = HipKernels(DEV, dtype)
-    return _KERNELS[dtype]
-
-
-def deviation_table(header):
-    """(note, fixture) of one test module: ``note(family, dtype, value)`` keeps the largest value per (family, dtype); the
-    module-scoped autouse fixture - to be bound to a name of the module - prints them under ``header`` when the module is done."""
-    worst = {}
-
-    def note(family, dtype, value):
-        worst[(family, dtype)] = max(worst.get((family, dtype), 0.0), float(value))
-
-    @pytest.fixture(scope="module", autouse=True)
-    def table():
-        yield
-        print(f"\n{header}\n|---|---|---|")
-        for (fam, dtype), v in sorted(worst.items()):
-            print(f"| {fam} | {dtype} | {v:.3g} |")
-
-    return note, table
-
-
-def dev(a, tdtype=torch.float64):
-    """A host array on the device as ``tdtype`` (None: its own dtype)."""
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if tdtype is None else t.to(tdtype)).to(DEV)
-
-
-def guarded(n, tdtype=torch.float64, fill=None):
-    """n live elements and GUARD more, all holding the sentinel (``fill``: the live ones hold it instead)."""
-    buf = torch.full((n + GUARD,), SENTINEL[tdtype], dtype=tdtype, device=DEV)
-    if fill is not None:
-        buf[:n] = fill
-    return buf
-
-
-def intact(buf, n):
-    return bool((buf[n:] == SENTINEL[buf.dtype]).all())
-
-
-def written(buf, n):
-    return bool((buf[:n] != SENTINEL[buf.dtype]).all())
-
-
-def nan_workspace(nbytes):
-    """A guarded workspace whose live bytes are NaN bit patterns: a kernel that reads workspace it did not write returns NaN."""
-    assert nbytes % 8 == 0
-    return guarded(nbytes // 8, fill=float("nan"))
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({8: np.int64, 4: np.int32, 1: np.uint8}[a.dtype.itemsize])
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(bits(a), bits(b))
 
 
 # ------------------------------------------------------------------------------------------------------ raw calls

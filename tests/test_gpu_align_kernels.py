@@ -19,8 +19,9 @@ import pytest
 import torch
 
 import _align_loop_case as lc
-from _align_kernel_scaffold import (DEV, DTYPES, GUARD, SENTINEL, deviation_table, dev as _dev, guarded as _guarded,
-                                    intact as _intact, kernels as _k, same_bits as _same_bits)
+from _align_kernel_scaffold import kernels as _k
+from _kernel_scaffold import (DEV, DTYPES, GUARD, SENTINEL, dev as _dev, deviation_table, guarded as _guarded,
+                              intact as _intact, same_bits as _same_bits)
 
 pytestmark = pytest.mark.gpu
 

@@ -19,8 +19,9 @@ import torch
 import _align_start_case as sc
 import _assign_case as ac
 import _assign_edge_cases as ec
-from _align_kernel_scaffold import (DEV, DTYPES, GUARD, dev as _dev, guarded as _guarded, intact as _intact, kernels as _k,
-                                    nan_workspace as _nan_workspace, prepare as _prepare, written as _written)
+from _align_kernel_scaffold import kernels as _k, prepare as _prepare
+from _kernel_scaffold import (DEV, DTYPES, GUARD, dev as _dev, guarded as _guarded, intact as _intact,
+                              nan_workspace as _nan_workspace, written as _written)
 
 pytestmark = pytest.mark.gpu
 

@@ -16,8 +16,8 @@ import pytest
 import torch
 
 import _align_svi_case as sc
-from _align_kernel_scaffold import (DEV, DTYPES, dev as _dev, guarded as _guarded, intact as _intact, kernels as _k,
-                                    same_bits as _same_bits)
+from _align_kernel_scaffold import kernels as _k
+from _kernel_scaffold import DEV, DTYPES, dev as _dev, guarded as _guarded, intact as _intact, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 

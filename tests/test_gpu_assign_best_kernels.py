@@ -19,9 +19,9 @@ import torch
 import _assign_best_case as bc
 import _assign_case as ac
 import _assign_edge_cases as ec
-from _align_kernel_scaffold import (DEV, DTYPES, GUARD, SENTINEL, LabelCase as _LabelCase, device_case as _case,
-                                    guarded as _guarded, intact as _intact, kernels as _k, layer_struct as _layer_array,
-                                    nan_workspace as _nan_workspace, written as _written)
+from _align_kernel_scaffold import device_case as _case, kernels as _k, LabelCase as _LabelCase, layer_struct as _layer_array
+from _kernel_scaffold import (DEV, DTYPES, GUARD, SENTINEL, guarded as _guarded, intact as _intact,
+                              nan_workspace as _nan_workspace, written as _written)
 
 pytestmark = pytest.mark.gpu
 

@@ -25,9 +25,9 @@ import torch
 
 import _assign_case as ac
 import _assign_edge_cases as ec
-from _align_kernel_scaffold import (DEV, DTYPES, assign as _assign, deviation_table, device_case, guarded as _guarded,
-                                    kernels as _k, nan_workspace as _nan_workspace, prepare as _prepare,
-                                    same_bits as _same_bits)
+from _align_kernel_scaffold import assign as _assign, device_case, kernels as _k, prepare as _prepare
+from _kernel_scaffold import (DEV, DTYPES, deviation_table, guarded as _guarded, nan_workspace as _nan_workspace,
+                              same_bits as _same_bits)
 
 pytestmark = pytest.mark.gpu
 

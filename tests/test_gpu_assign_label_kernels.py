@@ -17,8 +17,8 @@ import _assign_case as ac
 import _assign_edge_cases as ec
 import _assign_label_case as lab
 import _assign_topk_case as tk
-from _align_kernel_scaffold import (DTYPES, LABEL, PROBS, LabelCase as _Case, dev as _dev, guarded as _guarded,
-                                    intact as _intact, label_prepare as _label_prepare)
+from _align_kernel_scaffold import LABEL, PROBS, label_prepare as _label_prepare, LabelCase as _Case
+from _kernel_scaffold import DTYPES, dev as _dev, guarded as _guarded, intact as _intact
 
 pytestmark = pytest.mark.gpu
 

@@ -18,9 +18,9 @@ import torch
 import _assign_case as ac
 import _assign_edge_cases as ec
 import _assign_topk_case as tk
-from _align_kernel_scaffold import (DEV, DTYPES, GUARD, assign as _assign, device_case as _case, guarded as _guarded,
-                                    intact as _intact, layer_struct as _layer_array, nan_workspace as _nan_workspace,
-                                    same_bits as _same_bits, written as _written)
+from _align_kernel_scaffold import assign as _assign, device_case as _case, layer_struct as _layer_array
+from _kernel_scaffold import (DEV, DTYPES, GUARD, guarded as _guarded, intact as _intact, nan_workspace as _nan_workspace,
+                              same_bits as _same_bits, written as _written)
 
 pytestmark = pytest.mark.gpu
 

@@ -19,9 +19,10 @@ import torch
 import _assign_case as ac
 import _assign_edge_cases as ec
 import _assign_transfer_case as tc
-from _align_kernel_scaffold import (DEV, DTYPES, SENTINEL, LabelCase as _LabelCase, assign as _assign, dev as _dev,
-                                    device_case as _case, guarded as _guarded, intact as _intact,
-                                    layer_struct as _layer_array, nan_workspace as _nan_workspace, written as _written)
+from _align_kernel_scaffold import (assign as _assign, device_case as _case, LabelCase as _LabelCase,
+                                    layer_struct as _layer_array)
+from _kernel_scaffold import (DEV, DTYPES, SENTINEL, dev as _dev, guarded as _guarded, intact as _intact,
+                              nan_workspace as _nan_workspace, written as _written)
 
 pytestmark = pytest.mark.gpu
 

@@ -18,41 +18,13 @@ import torch
 
 import _cell_cases as cc
 from _cpu_kernels import CpuKernels
+from _kernel_scaffold import (DEV, DTYPES, GUARD, bits_equal as _bits_equal, dev as _dev, deviation_table,
+                              guarded as _guarded, intact as _intact, kernel_cache)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-DTYPES = ["float64", "float32"]
-SENTINEL = -1.2345e300
-GUARD = 4096  # float64 elements behind every output buffer
-_KERNELS = {}
-_WORST = {}
-
-
-def _k(dtype):
-    if dtype not in _KERNELS:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _KERNELS[dtype] = HipKernels(DEV, dtype)
-    return _KERNELS[dtype]
-
-
-def _note(family, dtype, value):
-    key = (family, dtype)
-    _WORST[key] = max(_WORST.get(key, 0.0), float(value))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _deviation_table():
-    yield
-    print("\n| case family | dtype | largest deviation |\n|---|---|---|")
-    for (family, dtype), v in sorted(_WORST.items()):
-        print(f"| {family} | {dtype} | {v:.3g} |")
-
-
-def _dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(DEV)
+_k = kernel_cache()
+_note, _deviation_table = deviation_table("| case family | dtype | largest deviation |")
 
 
 def _x4(k, a):
@@ -62,11 +34,6 @@ def _x4(k, a):
 
 def _host(d):
     return {f: t.cpu().numpy() for f, t in d.items()}
-
-
-def _bits_equal(a, b):
-    """Same bytes (NaNs included)."""
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
 
 
 def _eval_setup(dtype, case):
@@ -158,7 +125,7 @@ def _eval_raw(k, x4, c4, Cd, case, flags):
     bufs = {}
     for f in cc.EVAL_FLAGS:
         if flags & f:
-            bufs[f] = torch.full((int(np.prod(cc.EVAL_SHAPES[f](n))) + GUARD,), SENTINEL, dtype=torch.float64, device=DEV)
+            bufs[f] = _guarded(int(np.prod(cc.EVAL_SHAPES[f](n))))
     ptr = [bufs[f].data_ptr() if f in bufs else None for f in
            (cc.EVAL_V, cc.EVAL_JAC, cc.EVAL_DIV, cc.EVAL_CURL, cc.EVAL_ACC, cc.EVAL_CURV, cc.EVAL_TORS, cc.EVAL_JDET)]
     from spateo_amd import _lib
@@ -180,7 +147,7 @@ def test_eval_writes_nothing_behind_its_buffers(dtype, n):
         assert set(bufs) == {f for f in cc.EVAL_FLAGS if flags & f}
         for f, b in bufs.items():
             live = b.numel() - GUARD
-            assert bool((b[live:] == SENTINEL).all()), cc.EVAL_NAMES[f]
+            assert _intact(b, live), cc.EVAL_NAMES[f]
             assert _bits_equal(b[:live].view(cc.EVAL_SHAPES[f](n)), full[f]), cc.EVAL_NAMES[f]  # (and every element written)
 
 
@@ -234,12 +201,12 @@ def _rk4_run(dtype, n, m, affine, dt, substeps, n_out):
     assert np.array_equal(x4.double().cpu().numpy()[:, :3], case["X"])  # the float32 grid: no rounding on the way in
     outs = []
     for _ in range(2):
-        buf = torch.full((n * n_out * 3 + GUARD,), SENTINEL, dtype=torch.float64, device=DEV)
+        buf = _guarded(n * n_out * 3)
         _lib.check(k.lib.mvf_integrate(x4.data_ptr(), n, c4.data_ptr(), m, float(case["beta"]), Cd.data_ptr(),
                                        k._affine_buf(case["affine"]), float(dt), int(substeps), int(n_out), buf.data_ptr(),
                                        k.cdtype, k._stream()), "mvf_integrate")
         torch.cuda.synchronize()
-        assert bool((buf[n * n_out * 3:] == SENTINEL).all())
+        assert _intact(buf, n * n_out * 3)
         outs.append(buf[: n * n_out * 3].view(n, n_out, 3))
     assert _bits_equal(outs[0], outs[1])  # deterministic
     via_wrapper = k.integrate(x4, c4, case["beta"], Cd, dt, substeps, n_out, affine=case["affine"])
@@ -355,14 +322,14 @@ def test_estep_sizes_dimensions_and_underflow_families(dtype, n, kind, dy, gamma
 def test_quadform_shapes(m, nrhs):
     K, C = cc.quadform_case(m, nrhs)
     k = _k("float64")
-    out = torch.full((1 + GUARD,), SENTINEL, dtype=torch.float64, device=DEV)
+    out = _guarded(1)
     k.quadform(_dev(K), _dev(C), out)
     ref = cc.quadform_reference(K, C)
     got = float(out[0])
     err = abs(got - ref) / ref
     print(f"quadform m={m} nrhs={nrhs}: {err:.2e}")
     _note("quadform", "float64", err)
-    assert bool((out[1:] == SENTINEL).all())
+    assert _intact(out, 1)
     np.testing.assert_allclose(got, ref, rtol=1e-11)
 
 
@@ -377,7 +344,7 @@ def test_lincomb3_lengths_absent_terms_and_aliasing(n):
             dev = {"A": _dev(A)}
             dev.update({key: _dev(v) for key, v in kw.items() if key in "BC"})
             if alias is None:
-                buf = torch.full((n + GUARD,), SENTINEL, dtype=torch.float64, device=DEV)
+                buf = _guarded(n)
                 out = buf[:n]
             else:
                 buf, out = None, dev[alias]
@@ -387,7 +354,7 @@ def test_lincomb3_lengths_absent_terms_and_aliasing(n):
             worst = max(worst, float(ulps.max()))
             assert ulps.max() <= 1.0, (sorted(kw), alias)
             if buf is not None:
-                assert bool((buf[n:] == SENTINEL).all())
+                assert _intact(buf, n)
             for key, t in dev.items():  # inputs that are not the output are untouched
                 if key != alias:
                     assert np.array_equal(t.cpu().numpy(), {"A": A, "B": B, "C": C}[key])
@@ -400,15 +367,15 @@ def test_sym_pack_and_unpack_bit_for_bit(m):
     G = cc.sym_case(m)
     k = _k("float64")
     nt = m * (m + 1) // 2
-    tri = torch.full((nt + GUARD,), SENTINEL, dtype=torch.float64, device=DEV)
+    tri = _guarded(nt)
     k.sym_pack(_dev(G), tri[:nt])
     torch.cuda.synchronize()
     np.testing.assert_array_equal(tri[:nt].cpu().numpy(), G[np.triu_indices(m)])
-    assert bool((tri[nt:] == SENTINEL).all())
-    full = torch.full((m * m + GUARD,), SENTINEL, dtype=torch.float64, device=DEV)
+    assert _intact(tri, nt)
+    full = _guarded(m * m)
     k.sym_unpack(tri[:nt], full[: m * m].view(m, m))
     torch.cuda.synchronize()
     F = full[: m * m].view(m, m).cpu().numpy()
     np.testing.assert_array_equal(F, cc.sym_completion(G[np.triu_indices(m)], m))
-    assert bool((full[m * m:] == SENTINEL).all()) and bool((tri[nt:] == SENTINEL).all())
+    assert _intact(full, m * m) and _intact(tri, nt)
     np.testing.assert_array_equal(tri[:nt].cpu().numpy(), G[np.triu_indices(m)])  # unpack leaves the packed values alone

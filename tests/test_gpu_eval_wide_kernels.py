@@ -13,27 +13,12 @@ import torch
 
 import _eval_wide_cases as wc
 from _cell_cases import EVAL_JAC, EVAL_V, TOL, relmax
+from _kernel_scaffold import DEV, DTYPES, SENTINEL as _SENTINEL, guarded as _buf, intact as _intact, kernel_cache
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-DTYPES = ["float64", "float32"]
-SENTINEL = -1.2345e300
-GUARD = 4096  # float64 elements behind every output buffer
-_KERNELS = {}
-
-
-def _k(dtype):
-    if dtype not in _KERNELS:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _KERNELS[dtype] = HipKernels(DEV, dtype)
-    return _KERNELS[dtype]
-
-
-def _buf(numel):
-    return torch.full((numel + GUARD,), SENTINEL, dtype=torch.float64, device=DEV)
+SENTINEL = _SENTINEL[torch.float64]  # (every output of the evaluator is float64: what the host copies below are compared with)
+_k = kernel_cache()
 
 
 def _inputs(dtype, n, m, dy, d):
@@ -161,7 +146,7 @@ def test_empty_problems(dtype):
     _run(k, empty4, c4, d, c["beta"], Cd.data_ptr(), dy, dy, both, vb.data_ptr(), dy, jb.data_ptr())      # n = 0
     _run(k, x4, c4, d, c["beta"], Cd.data_ptr(), dy, 0, both, vb.data_ptr(), dy, jb.data_ptr())           # dy = 0
     torch.cuda.synchronize()
-    assert bool((vb == SENTINEL).all()) and bool((jb == SENTINEL).all()), "an empty problem wrote something"
+    assert _intact(vb, 0) and _intact(jb, 0), "an empty problem wrote something"
     _run(k, x4, empty4, d, c["beta"], None, dy, dy, both, vb.data_ptr(), dy, jb.data_ptr())               # m = 0: zeros
     v, j = vb.cpu().numpy(), jb.cpu().numpy()
     assert np.all(v[: n * dy] == 0.0) and np.all(j[: dy * d * n] == 0.0)

@@ -12,63 +12,33 @@ within that bound and that each targeted defect leaves it by >= 100 x.
 Everything else is exact: all paths bit-equal to each other, G == G^T, repeated calls, a NaN-filled workspace between calls
 (the reductions read no word the tile kernels skip), stage masks, the raw ABI inside sentinel buffers, refusals.  Run with
 ``-s`` for the largest |deviation| / bound per case family (profiles/gram_kernel_edges.md records them)."""
-import time
-
 import numpy as np
 import pytest
 import torch
 
 import _gram_cases as gc
+from _kernel_scaffold import (DEV, DTYPES, SENTINEL as _SENTINEL, WS_FILL, bits_equal as _bits_equal, deviation_table,
+                              guarded as _guarded, intact as _intact, kernel_cache, option as _option, Out as _Out,
+                              Ws as _Ws)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-DTYPES = ["float64", "float32"]
-SENTINEL = -1.2345e300
-SENTINEL_T = {"float64": -1.2345e300, "float32": -1.2345e30}
-GUARD = 4096       # elements in front of and behind every output buffer
-GUARD_BYTES = 4096  # bytes in front of and behind the workspace (keeps its 256-byte alignment)
-WS_FILL = 0xA5
+SENTINEL = _SENTINEL[torch.float64]  # what an untouched G or R holds
 TILES, RHS, REDUCE, REDUCE_RHS = 1, 2, 4, 8
 ALL = 15
-_KERNELS = {}
-_WORST = {}
 _COUNT = [0]
+_k = kernel_cache()
 
 
-def _k(dtype):
-    if dtype not in _KERNELS:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _KERNELS[dtype] = HipKernels(DEV, dtype)
-    return _KERNELS[dtype]
-
-
-def _note(family, dtype, what, value):
-    key = (family, dtype, what)
-    _WORST[key] = max(_WORST.get(key, 0.0), float(value))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _deviation_table():
-    t0 = time.perf_counter()
-    yield
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    for k in _KERNELS.values():
+def _drop_caches():
+    for k in _k.cache.values():
         k.drop_ublk()
         k._gram_ws = None
-    print(f"\ntest_gpu_gram_kernels: {time.perf_counter() - t0:.1f} s, {_COUNT[0]} reference comparisons")
-    print("| case family | dtype | quantity | largest |deviation| / bound |\n|---|---|---|---|")
-    for (family, dtype, what), v in sorted(_WORST.items()):
-        print(f"| {family} | {dtype} | {what} | {v:.3g} |")
 
 
-def _bits_equal(a, b):
-    """Same bytes (NaNs and the sign of zero included)."""
-    it = torch.int32 if a.dtype == torch.float32 else torch.int64
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(it), b.contiguous().view(it))
+_note, _deviation_table = deviation_table(
+    "| case family | dtype | quantity | largest |deviation| / bound |", columns=4, on_done=_drop_caches,
+    footer=lambda seconds, notes: f"test_gpu_gram_kernels: {seconds:.1f} s, {_COUNT[0]} reference comparisons")
 
 
 def _x4(k, a, center):
@@ -83,27 +53,7 @@ def _device_case(k, c):
 
 
 def _gr(m):
-    return (torch.full((m, m), SENTINEL, dtype=torch.float64, device=DEV),
-            torch.full((m, 3), SENTINEL, dtype=torch.float64, device=DEV))
-
-
-class _option:
-    """A developer option of the library for the length of a block; restored on the way out."""
-
-    def __init__(self, name, value):
-        self.name, self.value = name, value
-
-    def __enter__(self):
-        from spateo_amd import _lib
-
-        if self.value:
-            _lib.debug_option(self.name, self.value)
-
-    def __exit__(self, *exc):
-        from spateo_amd import _lib
-
-        if self.value:
-            _lib.debug_option(self.name, 0)
+    return _Out(m, m).t, _Out(m, 3).t
 
 
 def _paths(dtype):
@@ -156,11 +106,11 @@ def _decoded_cache(k, dtype, x4, c4, beta):
     K = k.con_k(x4[:, :3].contiguous(), c4[:, :3].contiguous(), beta)
     live = U[:n, :m].contiguous()
     assert _bits_equal(live, K)
-    buf = torch.full((n_pad * m_pad + GUARD,), SENTINEL_T[dtype], dtype=k.tdtype, device=DEV)
+    buf = _guarded(n_pad * m_pad, k.tdtype)
     torch.cuda.synchronize()
     rc = k.lib.mvf_ublk_build(x4.data_ptr(), n, c4.data_ptr(), m, float(beta), buf.data_ptr(), need, k.cdtype, k._stream())
     torch.cuda.synchronize()
-    assert rc == 0 and bool((buf[n_pad * m_pad:] == SENTINEL_T[dtype]).all()) and _bits_equal(buf[:n_pad * m_pad], k._ublk)
+    assert rc == 0 and _intact(buf, n_pad * m_pad) and _bits_equal(buf[:n_pad * m_pad], k._ublk)
     return live
 
 
@@ -361,14 +311,6 @@ def test_stage_masks(dtype, n, m):
     k.drop_ublk()
 
 
-def _guarded(elems):
-    return torch.full((GUARD + elems + GUARD,), SENTINEL, dtype=torch.float64, device=DEV)
-
-
-def _guards_intact(buf, elems):
-    return bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[GUARD + elems:] == SENTINEL).all())
-
-
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("n,m", [(300, 129), (257, 193), (513, 440)])
 def test_raw_abi_writes_nothing_outside_its_buffers(dtype, n, m):
@@ -380,15 +322,15 @@ def test_raw_abi_writes_nothing_outside_its_buffers(dtype, n, m):
     need = int(k.lib.mvf_gram_workspace_bytes(n, m, k.cdtype))
     for path in ("recompute", "cached"):
         G1, R1 = _gram(k, path, x4, P, y4, c4, c["beta"])
-        Gb, Rb = _guarded(m * m), _guarded(m * 3)
-        wsb = torch.full((GUARD_BYTES + need + GUARD_BYTES,), WS_FILL, dtype=torch.uint8, device=DEV)
-        assert (wsb.data_ptr() + GUARD_BYTES) % 256 == 0
-        rc = _raw(k, ALL, x4, P, y4, c4, c["beta"], Gb.data_ptr() + 8 * GUARD, Rb.data_ptr() + 8 * GUARD,
-                  wsb.data_ptr() + GUARD_BYTES, need, k._ublk.data_ptr() if path == "cached" else None)
+        Gb, Rb = _Out(m * m), _Out(m * 3)
+        wsb = _Ws(need)
+        assert wsb.ptr % 256 == 0
+        rc = _raw(k, ALL, x4, P, y4, c4, c["beta"], Gb.ptr, Rb.ptr, wsb.ptr, need,
+                  k._ublk.data_ptr() if path == "cached" else None)
         assert rc == 0, path
-        assert _guards_intact(Gb, m * m) and _guards_intact(Rb, m * 3), path
-        assert bool((wsb[:GUARD_BYTES] == WS_FILL).all()) and bool((wsb[GUARD_BYTES + need:] == WS_FILL).all()), path
-        assert _bits_equal(Gb[GUARD:GUARD + m * m].view(m, m), G1) and _bits_equal(Rb[GUARD:GUARD + m * 3].view(m, 3), R1), path
+        assert Gb.guards_intact() and Rb.guards_intact(), path
+        assert wsb.guards_intact(), path
+        assert _bits_equal(Gb.t.view(m, m), G1) and _bits_equal(Rb.t.view(m, 3), R1), path
     k.drop_ublk()
 
 
@@ -399,15 +341,15 @@ def test_degenerate_shapes(dtype):
     c = gc.case("degenerate", n, m)
     k = _k(dtype)
     x4, c4, y4, P = _device_case(k, c)
-    ws = torch.full((int(k.lib.mvf_gram_workspace_bytes(n, m, k.cdtype)),), WS_FILL, dtype=torch.uint8, device=DEV)
-    Gb, Rb = _guarded(m * m), _guarded(m * 3)
-    rc = _raw(k, ALL, x4, P, y4, c4, c["beta"], Gb.data_ptr() + 8 * GUARD, Rb.data_ptr() + 8 * GUARD, ws.data_ptr(), ws.numel(), n=0)
-    assert rc == 0 and _guards_intact(Gb, m * m) and _guards_intact(Rb, m * 3)
-    assert not Gb[GUARD:GUARD + m * m].any() and not Rb[GUARD:GUARD + m * 3].any()
-    assert bool((ws == WS_FILL).all())
-    Gb, Rb = _guarded(m * m), _guarded(m * 3)
-    rc = _raw(k, ALL, x4, P, y4, c4, c["beta"], Gb.data_ptr() + 8 * GUARD, Rb.data_ptr() + 8 * GUARD, ws.data_ptr(), ws.numel(), m=0)
-    assert rc == 0 and bool((Gb == SENTINEL).all()) and bool((Rb == SENTINEL).all()) and bool((ws == WS_FILL).all())
+    ws = _Ws(k.lib.mvf_gram_workspace_bytes(n, m, k.cdtype))
+    Gb, Rb = _Out(m * m), _Out(m * 3)
+    rc = _raw(k, ALL, x4, P, y4, c4, c["beta"], Gb.ptr, Rb.ptr, ws.ptr, ws.nbytes, n=0)
+    assert rc == 0 and Gb.guards_intact() and Rb.guards_intact()
+    assert not Gb.t.any() and not Rb.t.any()
+    assert bool((ws.big == WS_FILL).all())
+    Gb, Rb = _Out(m * m), _Out(m * 3)
+    rc = _raw(k, ALL, x4, P, y4, c4, c["beta"], Gb.ptr, Rb.ptr, ws.ptr, ws.nbytes, m=0)
+    assert rc == 0 and bool((Gb.big == SENTINEL).all()) and bool((Rb.big == SENTINEL).all()) and bool((ws.big == WS_FILL).all())
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -422,9 +364,9 @@ def test_refusals_leave_the_outputs_untouched(dtype):
     need = int(k.lib.mvf_gram_workspace_bytes(n, m, k.cdtype))
     # what the recompute path itself needs: the widened P behind the partials belongs to the float32 cached tile stage
     need_stages = need - (gc.align_up(8 * gc.pads(n, m)[0]) if dtype == "float32" else 0)
-    ws = torch.full((need,), WS_FILL, dtype=torch.uint8, device=DEV)
+    ws = _Ws(need)
     G, R = _gr(m)
-    g, r, w = G.data_ptr(), R.data_ptr(), ws.data_ptr()
+    g, r, w = G.data_ptr(), R.data_ptr(), ws.ptr
     calls = {
         "beta < 0": dict(beta=-beta), "beta = inf": dict(beta=float("inf")),
         "beta < 0, cached": dict(beta=-beta, ublk=ublk), "beta = inf, cached": dict(beta=float("inf"), ublk=ublk),
@@ -453,10 +395,10 @@ def test_refusals_leave_the_outputs_untouched(dtype):
     builds = {"n = 0": dict(n=0), "m = 0": dict(m=0), "beta < 0": dict(beta=-beta), "beta = inf": dict(beta=float("inf")),
               "cache buffer one byte short": dict(short=1)}
     for name, kw in builds.items():
-        buf = torch.full((n_pad * m_pad + GUARD,), SENTINEL_T[dtype], dtype=k.tdtype, device=DEV)
+        buf = _guarded(n_pad * m_pad, k.tdtype)
         torch.cuda.synchronize()
         rc = k.lib.mvf_ublk_build(x4.data_ptr(), kw.get("n", n), c4.data_ptr(), kw.get("m", m), float(kw.get("beta", beta)),
                                   buf.data_ptr(), bytes_ - kw.get("short", 0), k.cdtype, k._stream())
         torch.cuda.synchronize()
         assert rc != 0, name
-        assert bool((buf == SENTINEL_T[dtype]).all()), name
+        assert _intact(buf, 0), name

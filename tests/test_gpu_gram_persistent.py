@@ -20,19 +20,14 @@ import numpy as np
 import pytest
 import torch
 
+from _kernel_scaffold import DEV, fresh_kernels as _k, option as _option
+
 pytestmark = pytest.mark.gpu
 
 BETA = 0.003
-DEV = "cuda:0"
 REG_COLS, PER_JOB, PERSISTENT = 1, 2, 3
 SLICE = 256
 MIN_BUFFER_TILES = int(3e9 // (128 * 128 * 8))  # make_plan: the partial-tile buffer holds at least 3 GB
-
-
-def _k():
-    from spateo_amd._kernels import HipKernels
-
-    return HipKernels(DEV, "float32")
 
 
 def _slots():
@@ -65,39 +60,15 @@ def _weights(seed, n):
     return torch.from_numpy(np.random.default_rng(10_000 + seed).uniform(1e-5, 1.0, n).astype(np.float32)).to(DEV)
 
 
-class _options:
-    """Developer options for the duration of a block (process-wide), back to their defaults behind it."""
-
-    def __init__(self, **opts):
-        self.opts = opts
-
-    def __enter__(self):
-        from spateo_amd import _lib
-
-        for name, value in self.opts.items():
-            _lib.debug_option(name, value)
-
-    def __exit__(self, *exc):
-        from spateo_amd import _lib
-
-        for name in self.opts:
-            _lib.debug_option(name, 0)
-
-
 def _gram(kk, path, x4, P, y4, c4, m, poison=False):
     """G, R of the cached path `path` (a value of "gram_reg_cols"); poison: every byte of the workspace set first (a
     counter that is not zeroed again then hands out no job at all, and the partial tiles read back as NaN)."""
-    from spateo_amd import _lib
-
     G = torch.empty(m, m, dtype=torch.float64, device=DEV)
     R = torch.empty(m, 3, dtype=torch.float64, device=DEV)
     if poison and kk._gram_ws is not None:
         kk._gram_ws.fill_(0xFF)
-    _lib.debug_option("gram_reg_cols", path)
-    try:
+    with _option("gram_reg_cols", path):
         kk.gram(x4, P, y4, c4, BETA, G, R, cache_only=True)
-    finally:
-        _lib.debug_option("gram_reg_cols", 0)
     return G, R
 
 
@@ -119,8 +90,8 @@ def _check_paths(kk, x4, P, y4, c4, m, auto=True):
 @pytest.mark.parametrize("n", [70_001, SLICE * 37 + 5])
 def test_persistent_equals_per_job_and_register_operands(n, m):
     """Tile shapes by m, cell counts that leave a padded last slice: 274 and 38 slices of 256 cells."""
-    with _options(slice_len=SLICE):
-        kk = _k()
+    with _option("slice_len", SLICE):
+        kk = _k("float32")
         x4, c4, y4, P = _inputs(kk, n + m, n, m)
         kk.build_ublk(x4, c4, BETA)
         _check_paths(kk, x4, P, y4, c4, m)
@@ -137,8 +108,8 @@ def test_job_counts_around_the_resident_slots(edge):
                "just past two rounds": 2 * slots + 1, "far above": 4 * slots + 3}[edge]
     n = SLICE * (nslices - 1) + 17
     assert _jobs_per_phase(n, m) == (nslices, 1)
-    with _options(slice_len=SLICE):
-        kk = _k()
+    with _option("slice_len", SLICE):
+        kk = _k("float32")
         x4, c4, y4, P = _inputs(kk, nslices, n, m)
         kk.build_ublk(x4, c4, BETA)
         _check_paths(kk, x4, P, y4, c4, m)
@@ -151,8 +122,8 @@ def test_job_counts_around_the_resident_slots_three_pairs(delta):
     slots, m = _slots(), 130
     nslices = slots // 3 + delta
     n = SLICE * nslices
-    with _options(slice_len=SLICE):
-        kk = _k()
+    with _option("slice_len", SLICE):
+        kk = _k("float32")
         x4, c4, y4, P = _inputs(kk, 50 + delta, n, m)
         kk.build_ublk(x4, c4, BETA)
         _check_paths(kk, x4, P, y4, c4, m)
@@ -168,8 +139,8 @@ def test_phases_on_one_workspace_with_the_counter_zeroed_every_phase(nslices, np
     n = SLICE * (nslices - 1) + 5
     jobs, ph = _jobs_per_phase(n, m)
     assert ph == nphases and jobs > 2 * _slots()  # the plan's own choice is the persistent launch
-    with _options(slice_len=SLICE):
-        kk = _k()
+    with _option("slice_len", SLICE):
+        kk = _k("float32")
         x4, c4, y4, P = _inputs(kk, nslices, n, m)
         kk.build_ublk(x4, c4, BETA)
         G1, R1 = _check_paths(kk, x4, P, y4, c4, m)
@@ -189,7 +160,7 @@ def test_two_engines_on_two_streams_equal_the_sequential_run():
 
     def run(seed, n, m, out, i, stream=None):
         def work():
-            kk = _k()
+            kk = _k("float32")
             x4, c4, y4, P = _inputs(kk, seed, n, m)
             kk.build_ublk(x4, c4, BETA)
             res = []
@@ -213,11 +184,11 @@ def test_two_engines_on_two_streams_equal_the_sequential_run():
 
     for _, n, m in shapes:
         assert _jobs_per_phase(n, m)[1] == 1
-    with _options(slice_len=SLICE, gram_reg_cols=PER_JOB):
+    with _option("slice_len", SLICE), _option("gram_reg_cols", PER_JOB):
         want = [None, None]
         for i, (seed, n, m) in enumerate(shapes):
             run(seed, n, m, want, i)
-    with _options(slice_len=SLICE, gram_reg_cols=PERSISTENT):
+    with _option("slice_len", SLICE), _option("gram_reg_cols", PERSISTENT):
         seq, par = [None, None], [None, None]
         for i, (seed, n, m) in enumerate(shapes):
             run(seed, n, m, seq, i)

@@ -10,15 +10,11 @@ import numpy as np
 import pytest
 import torch
 
+from _kernel_scaffold import fresh_kernels as _k, option as _option
+
 pytestmark = pytest.mark.gpu
 
 BETA = 0.003
-
-
-def _k():
-    from spateo_amd._kernels import HipKernels
-
-    return HipKernels("cuda:0", "float32")
 
 
 def _inputs(k, seed, n, m, spread=30.0):
@@ -38,14 +34,11 @@ def _gr(m):
 def _cached(kk, x4, P, y4, c4, beta, m, reg_cols):
     from spateo_amd import _lib
 
-    _lib.debug_option("gram_reg_cols", 1 if reg_cols else 0)
-    try:
+    with _option("gram_reg_cols", 1 if reg_cols else 0):
         if reg_cols:
             assert _lib.debug_options().get("gram_reg_cols") == 1  # what the bench reports as developer_options
         G, R = _gr(m)
         kk.gram(x4, P, y4, c4, beta, G, R, cache_only=True)
-    finally:
-        _lib.debug_option("gram_reg_cols", 0)
     return G, R
 
 
@@ -66,7 +59,7 @@ def _check(kk, x4, P, y4, c4, beta, m):
 @pytest.mark.parametrize("m", [16, 64, 65, 130, 192, 193, 440])
 @pytest.mark.parametrize("n", [1, 255, 256, 257, 511, 4097])
 def test_shared_cols_equal_recompute_and_register_operands(n, m):
-    kk = _k()
+    kk = _k("float32")
     x4, c4, y4, P = _inputs(kk, 3000 + n + m, n, m)
     _check(kk, x4, P, y4, c4, BETA, m)
     kk.drop_ublk()
@@ -75,26 +68,21 @@ def test_shared_cols_equal_recompute_and_register_operands(n, m):
 def test_two_phases_of_256_cell_slices_twice_on_one_workspace():
     """slice_len forced to 256 at m = 300: 1 200 001 cells need two phases (the partial-tile buffer is smaller than all
     partial tiles); a second call on the same HipKernels gives the same bits."""
-    from spateo_amd import _lib
-
     n, m = 1_200_001, 300
-    _lib.debug_option("slice_len", 256)
-    try:
-        kk = _k()
+    with _option("slice_len", 256):
+        kk = _k("float32")
         x4, c4, y4, P = _inputs(kk, 6, n, m)
         assert kk.lib.mvf_gram_workspace_bytes(n, m, kk.cdtype) < (n // 256) * 6 * 128 * 128 * 8  # more than one phase
         Gs, Rs = _check(kk, x4, P, y4, c4, BETA, m)
         G2, R2 = _cached(kk, x4, P, y4, c4, BETA, m, reg_cols=False)
         assert torch.equal(G2, Gs) and torch.equal(R2, Rs)
         kk.drop_ublk()
-    finally:
-        _lib.debug_option("slice_len", 0)
 
 
 def test_p_with_exact_zeros_and_the_floor():
     """P holds exact zeros and 1e-5 next to ordinary weights (a zero P K product in a row operand)."""
     n, m = 4097, 193
-    kk = _k()
+    kk = _k("float32")
     x4, c4, y4, P = _inputs(kk, 77, n, m)
     Ph = P.cpu().numpy().copy()
     Ph[::3] = 0.0
@@ -109,7 +97,7 @@ def test_kernel_values_that_underflow_to_denormals_and_to_zero():
     """A large beta on the same geometry: many float32 kernel values exp2(-e) fall into the denormal range (126 < e <= 149)
     and many below it.  Checked on the CPU first, in float32 arithmetic on the scaled coordinates the kernels use."""
     n, m, beta = 4097, 193, 0.05
-    kk = _k()
+    kk = _k("float32")
     x4, c4, y4, P = _inputs(kk, 78, n, m)
     s = np.float32(np.sqrt(beta * np.log2(np.e)))
     xs, cs = x4.cpu().numpy()[:, :3] * s, c4.cpu().numpy()[:, :3] * s

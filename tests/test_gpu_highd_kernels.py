@@ -12,53 +12,19 @@ Tolerances: evaluator 1e-10 (float64) / 2e-4 (float32) of each quantity's maximu
 _highd_cases.curv_scale); mvf_con_k 1e-11 / 2e-5 (test_gpu_kernels.py::test_con_k_vs_oracle); cache against mvf_con_k,
 repeated calls, flag subsets, prefixes of the query list, guards and refusals bit for bit.  Run with ``-s`` to see the largest
 deviation of every case family and the module's running time (profiles/highd_kernel_edges.md records them)."""
-import time
-
 import numpy as np
 import pytest
 import torch
 
 import _highd_cases as hc
+from _kernel_scaffold import (DEV, DTYPES, GUARD, bits_equal as _bits_equal, dev as _dev, deviation_table,
+                              guarded as _guarded, intact as _intact, kernel_cache, written as _written)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-DTYPES = ["float64", "float32"]
-SENTINEL = -1.2345e300                                       # evaluator outputs are float64 in both cell dtypes
-SENTINEL_T = {"float64": -1.2345e300, "float32": -1.2345e30}  # the cache holds the cell dtype
-GUARD = 4096  # elements behind every output buffer
-_KERNELS = {}
-_WORST = {}
-
-
-def _k(dtype):
-    if dtype not in _KERNELS:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _KERNELS[dtype] = HipKernels(DEV, dtype)
-    return _KERNELS[dtype]
-
-
-def _note(family, dtype, value):
-    key = (family, dtype)
-    _WORST[key] = max(_WORST.get(key, 0.0), float(value))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _deviation_table():
-    t0 = time.perf_counter()
-    yield
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    print(f"\ntest_gpu_highd_kernels: {time.perf_counter() - t0:.1f} s")
-    print("| case family | dtype | largest deviation |\n|---|---|---|")
-    for (family, dtype), v in sorted(_WORST.items()):
-        print(f"| {family} | {dtype} | {v:.3g} |")
-
-
-def _dev(a, dtype=torch.float64):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(DEV)
+_k = kernel_cache()
+_note, _deviation_table = deviation_table("| case family | dtype | largest deviation |",
+                                           footer=lambda seconds, notes: f"test_gpu_highd_kernels: {seconds:.1f} s")
 
 
 def _xd(k, a):
@@ -68,12 +34,6 @@ def _xd(k, a):
 
 def _host(d):
     return {f: t.cpu().numpy() for f, t in d.items()}
-
-
-def _bits_equal(a, b):
-    """Same bytes (NaNs included)."""
-    it = torch.int32 if a.dtype == torch.float32 else torch.int64
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(it), b.contiguous().view(it))
 
 
 def _setup(dtype, case):
@@ -171,7 +131,7 @@ def _eval_raw(k, xd, cd, Cd, beta, flags, *, n=None, m=None, d=None, dy=None, nu
     for f in hc.HD_FLAGS:
         if elems is not None or flags & f:
             size = int(np.prod(shapes[f])) if elems is None else elems
-            bufs[f] = torch.full((size + GUARD,), SENTINEL, dtype=torch.float64, device=DEV)
+            bufs[f] = _guarded(size)
     ptr = [bufs[f].data_ptr() if f in bufs and f not in null else None for f in hc.HD_FLAGS]
     torch.cuda.synchronize()
     rc = k.lib.mvf_eval_d(xd.data_ptr(), n, None if nullin else cd.data_ptr(), m, d, float(beta),
@@ -195,7 +155,7 @@ def test_eval_d_writes_its_buffers_whole_and_nothing_behind_them(dtype, n, d, dy
         assert rc == 0 and set(bufs) == {f for f in hc.HD_FLAGS if fl & f}
         for f, b in bufs.items():
             live = b.numel() - GUARD
-            assert bool((b[live:] == SENTINEL).all()), hc.HD_NAMES[f]
+            assert _intact(b, live), hc.HD_NAMES[f]
             assert _bits_equal(b[:live].view(shapes[f]), full[f]), hc.HD_NAMES[f]
 
 
@@ -215,7 +175,7 @@ def test_eval_d_without_control_points(dtype, n, d, dy):
     assert rc == 0 and set(got) == set(ref) == set(bufs)
     for f, g in got.items():
         raw = bufs[f][: g.size].view(shapes[f]).cpu().numpy()
-        assert g.shape == shapes[f] and bool((bufs[f][g.size:] == SENTINEL).all()), hc.HD_NAMES[f]
+        assert g.shape == shapes[f] and _intact(bufs[f], g.size), hc.HD_NAMES[f]
         if f == hc.EVAL_CURV:
             assert np.isnan(g).all() and np.isnan(ref[f]).all() and np.isnan(raw).all()
         else:
@@ -229,7 +189,7 @@ def test_eval_d_without_queries_returns_0_and_writes_nothing(dtype):
     rc, bufs = _eval_raw(k, xd, cd, Cd, case["beta"], hc.HD_ALL, n=0)
     assert rc == 0 and len(bufs) == 5
     for f, b in bufs.items():
-        assert bool((b == SENTINEL).all()), hc.HD_NAMES[f]
+        assert _intact(b, 0), hc.HD_NAMES[f]
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -281,10 +241,10 @@ def test_eval_d_refusals_leave_the_outputs_untouched(dtype):
                              null=kw.get("null", ()), elems=81 * n)
         assert rc != 0 and len(bufs) == 5, name
         for b in bufs.values():
-            assert bool((b == SENTINEL).all()), name
+            assert _intact(b, 0), name
     # (the same buffers and claims pass where nothing is wrong: the refusals above are about what they name)
     rc, bufs = _eval_raw(k, xd, cd, Cd, hc.BETA, hc.HD_ALL, d=6, dy=6, elems=81 * n)
-    assert rc == 0 and all(bool((b[:n] != SENTINEL).all()) and bool((b[81 * n:] == SENTINEL).all()) for b in bufs.values())
+    assert rc == 0 and all(_written(b, n) and _intact(b, 81 * n) for b in bufs.values())
 
 
 # ------------------------------------------------------------------------------------------------------ con_K, cache
@@ -311,7 +271,7 @@ def _build_raw(k, dtype, xd, cd, *, n=None, m=None, d=None, beta=hc.UBLK_BETA, s
     item = 4 if dtype == "float32" else 8
     need = k.ublk_bytes(tn, tm)
     live = need // item if elems is None else elems
-    buf = torch.full((live + GUARD,), SENTINEL_T[dtype], dtype=k.tdtype, device=DEV)
+    buf = _guarded(live, k.tdtype)
     torch.cuda.synchronize()
     rc = k.lib.mvf_ublk_build_d(xd.data_ptr(), tn if n is None else n, cd.data_ptr(), tm if m is None else m,
                                 xd.shape[1] if d is None else d, float(beta), buf.data_ptr(), need - short, k.cdtype, k._stream())
@@ -326,7 +286,7 @@ def _check_cache(dtype, d, x, y):
     rc, buf, live = _build_raw(k, dtype, xd, yd)
     n_pad, m_pad = k.wide_pads(n, m)
     assert rc == 0 and live == n_pad * m_pad
-    assert bool((buf[live:] == SENTINEL_T[dtype]).all())  # nothing behind the cache
+    assert _intact(buf, live)  # nothing behind the cache
     U = buf[:live].view(m_pad // 16, n_pad, 16).permute(1, 0, 2).reshape(n_pad, m_pad)
     K = k.con_k(xd, yd, hc.UBLK_BETA)
     torch.cuda.synchronize()
@@ -366,6 +326,6 @@ def test_ublk_build_d_refusals_leave_the_buffer_untouched(dtype):
     for name, kw in calls.items():
         rc, buf, _ = _build_raw(k, dtype, xd, cd, **kw)
         assert rc != 0, name
-        assert bool((buf == SENTINEL_T[dtype]).all()), name
+        assert _intact(buf, 0), name
     rc, buf, live = _build_raw(k, dtype, xd, cd, d=4)  # (the same call with nothing wrong passes)
-    assert rc == 0 and bool((buf[:live] != SENTINEL_T[dtype]).all()) and bool((buf[live:] == SENTINEL_T[dtype]).all())
+    assert rc == 0 and _written(buf, live) and _intact(buf, live)

@@ -10,12 +10,10 @@ import pytest
 import torch
 
 import _icp_cases as ic
+from _kernel_scaffold import DEV, dev as _dev, guarded as _guarded, intact as _intact, stream as _stream, take as _take
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-GUARD = 64
-SENT = {torch.float64: -7.25e300, torch.int32: -77}
 PAR = dict(max_iter=20, error_threshold=1e-6, inlier_threshold=0.1, gamma_threshold=0.05, subsample=500, allow_rotation=False)
 
 
@@ -30,23 +28,6 @@ def lib():
 @pytest.fixture(scope="module")
 def G():
     return ic.load()
-
-
-def _stream():
-    return torch.cuda.current_stream(DEV).cuda_stream
-
-
-def _dev(a, dtype=np.float64):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(DEV)
-
-
-def _guarded(n, tdtype):
-    return torch.full((n + GUARD,), SENT[tdtype], dtype=tdtype, device=DEV)
-
-
-def _take(t, n):
-    assert bool((t[n:] == SENT[t.dtype]).all()), "wrote past the end of an output"
-    return t[:n].cpu().numpy()
 
 
 def run_batch(lib, pairs, want_T=True, **kw):
@@ -70,12 +51,12 @@ def run_batch(lib, pairs, want_T=True, **kw):
         outs.append(o)
     need = int(lib.mvf_icp_batch_workspace_bytes(P))
     assert need == min(P, 4096) * ctypes.sizeof(_lib.IcpProblem)
-    ws = torch.zeros(need // 8 + GUARD, dtype=torch.float64, device=DEV)
+    ws = _guarded(need // 8, fill=0.0)
     rc = lib.mvf_icp_batch(recs, P, par["max_iter"], par["error_threshold"], par["inlier_threshold"], par["gamma_threshold"],
                            par["subsample"], int(par["allow_rotation"]), ws.data_ptr(), need, _stream())
     assert rc == 0, lib.mvf_last_error()
     torch.cuda.synchronize()
-    assert bool((ws[need // 8:] == 0).all()), "wrote past the end of the workspace"
+    assert _intact(ws, need // 8), "wrote past the end of the workspace"
     res = []
     for o, m in zip(outs, m2):
         st = _take(o["stats"], 2)
@@ -201,7 +182,7 @@ def test_refusals_on_real_buffers(lib):
         assert call(**kw) != 0 and b"mvf_icp_batch" in lib.mvf_last_error(), kw
     assert call(nprob=0) == 0
     torch.cuda.synchronize()
-    assert bool((out == SENT[torch.float64]).all()) and bool((st == SENT[torch.int32]).all())   # nothing was launched
+    assert _intact(out, 0) and _intact(st, 0)   # nothing was launched
 
 
 # ---- the API ----

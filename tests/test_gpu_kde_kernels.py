@@ -9,12 +9,10 @@ import pytest
 import torch
 
 import _kde_cases as kc
+from _kernel_scaffold import (dev as _dev, guarded as _guarded, intact as _intact, ptr as _ptr, stream as _stream,
+                              take as _take, x4 as _x4)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-GUARD = 512
-SENT = -7.25e300
 
 
 @pytest.fixture(scope="module")
@@ -25,44 +23,17 @@ def lib():
     return _lib.load()
 
 
-def _stream():
-    return torch.cuda.current_stream(DEV).cuda_stream
-
-
-def _dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(DEV)
-
-
-def _guarded(n):
-    return torch.full((n + GUARD,), SENT, dtype=torch.float64, device=DEV)
-
-
-def _take(t, n):
-    assert bool((t[n:] == SENT).all()), "wrote past the end of a buffer"
-    return t[:n].cpu().numpy()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _x4(a, dtype):
-    out = np.zeros((len(a), 4), dtype=np.float32 if dtype == "float32" else np.float64)
-    out[:, : a.shape[1]] = a
-    return _dev(out)
-
-
 def _raw(lib, case, dtype):
     """Unnormalised (n, C) log sums of a case, the columns in chunks of 64; guards checked."""
     from spateo_amd import _lib
 
     t4, s4 = _x4(case["T"], dtype), _x4(case["X"], dtype)
     n, N, C = len(case["T"]), len(case["X"]), case["C"]
-    w = None if case["w"] is None else _dev(case["w"], np.float64)
+    w = None if case["w"] is None else _dev(case["w"])
     out = np.empty((n, C))
     for c0 in range(0, C, kc.MAX_COLUMNS):
         cc = min(kc.MAX_COLUMNS, C - c0)
-        g = None if case["g"] is None else _dev(case["g"] - c0, np.int32)
+        g = None if case["g"] is None else _dev(case["g"] - c0, torch.int32)
         need = int(lib.mvf_kde_workspace_bytes(n, N, cc))
         assert need == (kc.splits(n, N) + 1) * n * cc * 8
         ws, o = _guarded(need // 8), _guarded(n * cc)
@@ -127,7 +98,7 @@ def test_no_sources_fills_minus_infinity_and_empty_calls_launch_nothing(lib):
     assert lib.mvf_kde(_ptr(t4), 0, _ptr(t4), 300, 3, 0, 1.0, None, None, 1, _ptr(o), None, 0, _lib.MVF_F64, _stream()) == 0
     assert lib.mvf_kde(_ptr(t4), 300, _ptr(t4), 300, 3, 0, 1.0, None, None, 0, _ptr(o), None, 0, _lib.MVF_F64, _stream()) == 0
     torch.cuda.synchronize()
-    assert bool((o == SENT).all())
+    assert _intact(o, 0)  # (from element 0 on: nothing at all was written)
 
 
 def test_refusals_on_device_buffers(lib):
@@ -149,4 +120,4 @@ def test_refusals_on_device_buffers(lib):
                          a["ws_bytes"], a["dtype"], _stream())
         assert rc != 0 and b"mvf_kde" in lib.mvf_last_error() and msg in lib.mvf_last_error(), (kw, lib.mvf_last_error())
     torch.cuda.synchronize()
-    assert bool((o == SENT).all()) and bool((ws == SENT).all())
+    assert _intact(o, 0) and _intact(ws, 0)

@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import dg_oracle as dgo  # noqa: E402
 from oracle import sparsevfc_oracle as svo  # noqa: E402
+from _kernel_scaffold import fresh_kernels as _k  # noqa: E402
 
 DTYPES = [("float64", 1e-11), ("float32", 2e-5)]
 
@@ -23,12 +24,6 @@ def st():
 
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     return spateo_amd
-
-
-def _k(dtype):
-    from spateo_amd._kernels import HipKernels
-
-    return HipKernels("cuda:0", dtype)
 
 
 def _relmax(a, b):

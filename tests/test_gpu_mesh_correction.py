@@ -12,11 +12,10 @@ import pytest
 import torch
 
 import _icp_cases as ic
+from _kernel_scaffold import SENTINEL, dev as _dev, guarded as _guarded, intact as _intact, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-GUARD = 64
 HEIGHTS = np.array([30.0, 36.0, 44.0, 50.0])
 TRUTH = np.array([4.0, -3.0, 10.0, 1.0, 1.05])
 IDENTITY = np.array([0.0, 0.0, 0.0, 0.0, 1.0])
@@ -37,55 +36,47 @@ def case():
     return dict(verts=verts, tri=tri, edges=ic.unique_edges(tri), mean=verts.mean(0), contours=contours)
 
 
-def _stream():
-    return torch.cuda.current_stream(DEV).cuda_stream
-
-
-def _dev(a, dtype=np.float64):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(DEV)
-
-
 def _loss_bound(loss, n_slices):
     return n_slices * 2.0 ** -52 * np.maximum(1.0, np.abs(loss))
 
 
 def raw_contours(lib, case, param, heights, cap):
-    verts, edges = _dev(case["verts"]), _dev(case["edges"], np.int32)
+    verts, edges = _dev(case["verts"]), _dev(case["edges"], torch.int32)
     nS = len(heights)
-    pts = torch.full((nS * cap * 2 + GUARD,), -7.25e300, dtype=torch.float64, device=DEV)
-    cnt = torch.full((nS + GUARD,), -77, dtype=torch.int32, device=DEV)
+    pts = _guarded(nS * cap * 2)
+    cnt = _guarded(nS, torch.int32)
     m3, p5 = (ctypes.c_double * 3)(*case["mean"]), (ctypes.c_double * 5)(*param)
     rc = lib.mvf_mesh_contours(verts.data_ptr(), len(case["verts"]), edges.data_ptr(), len(case["edges"]), m3, p5,
                                _dev(heights).data_ptr(), nS, cap, pts.data_ptr(), cnt.data_ptr(), _stream())
     assert rc == 0, lib.mvf_last_error()
     torch.cuda.synchronize()
-    assert bool((pts[nS * cap * 2:] == -7.25e300).all()) and bool((cnt[nS:] == -77).all()), "wrote past the end of an output"
+    assert _intact(pts, nS * cap * 2) and _intact(cnt, nS), "wrote past the end of an output"
     return pts[: nS * cap * 2].cpu().numpy().reshape(nS, cap, 2), cnt[:nS].cpu().numpy()
 
 
 def raw_loss(lib, case, params, heights, contours, subsample=500, details=True):
-    verts, edges = _dev(case["verts"]), _dev(case["edges"], np.int32)
+    verts, edges = _dev(case["verts"]), _dev(case["edges"], torch.int32)
     params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 5)
     nT, nS = len(params), len(heights)
     flat = np.concatenate(contours)
     off = np.concatenate([[0], np.cumsum([len(c) for c in contours])]).astype(np.int64)
-    loss = torch.full((nT + GUARD,), -7.25e300, dtype=torch.float64, device=DEV)
-    gamma = torch.full((nT * nS + GUARD,), -7.25e300, dtype=torch.float64, device=DEV)
-    count = torch.full((nT * nS + GUARD,), -77, dtype=torch.int32, device=DEV)
+    loss = _guarded(nT)
+    gamma = _guarded(nT * nS)
+    count = _guarded(nT * nS, torch.int32)
     need = int(lib.mvf_mesh_loss_workspace_bytes(nT, nS))
-    ws = torch.zeros(need // 8 + GUARD, dtype=torch.float64, device=DEV)
+    ws = _guarded(need // 8, fill=0.0)
     m3 = (ctypes.c_double * 3)(*case["mean"])
-    keep = [_dev(params), _dev(heights), _dev(flat), _dev(off, np.int64)]
+    keep = [_dev(params), _dev(heights), _dev(flat), _dev(off, torch.int64)]
     rc = lib.mvf_mesh_loss(verts.data_ptr(), len(case["verts"]), edges.data_ptr(), len(case["edges"]), m3, keep[0].data_ptr(), nT,
                            keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), len(flat), nS, 20, 1e-6, 0.1, 0.05, subsample,
                            loss.data_ptr(), gamma.data_ptr() if details else None, count.data_ptr() if details else None,
                            ws.data_ptr(), need, _stream())
     assert rc == 0, lib.mvf_last_error()
     torch.cuda.synchronize()
-    assert bool((loss[nT:] == -7.25e300).all()) and bool((gamma[nT * nS:] == -7.25e300).all()) and bool((count[nT * nS:] == -77).all())
-    assert bool((ws[need // 8:] == 0).all()), "wrote past the end of the workspace"
+    assert _intact(loss, nT) and _intact(gamma, nT * nS) and _intact(count, nT * nS)
+    assert _intact(ws, need // 8), "wrote past the end of the workspace"
     if not details:
-        assert bool((gamma == -7.25e300).all()) and bool((count == -77).all())
+        assert _intact(gamma, 0) and _intact(count, 0)
         return loss[:nT].cpu().numpy()
     return loss[:nT].cpu().numpy(), gamma[: nT * nS].cpu().numpy().reshape(nT, nS), count[: nT * nS].cpu().numpy().reshape(nT, nS)
 
@@ -106,7 +97,7 @@ def test_contours_equal_the_restatement(lib, case, param):
     assert np.array_equal(cnt, [len(w) for w in want]) and cnt[-1] == 0 and (cnt[:-1] > 0).all()
     for s, w in enumerate(want):
         assert np.abs(pts[s, : len(w)] - w).max(initial=0.0) <= bound
-        assert (pts[s, len(w):] == -7.25e300).all()         # the rest of the row is untouched
+        assert (pts[s, len(w):] == SENTINEL[torch.float64]).all()       # the rest of the row is untouched
     small, cnt2 = raw_contours(lib, case, param, heights, 5)   # a capacity below the counts: the counts stay, 5 points are written
     assert np.array_equal(cnt2, cnt) and np.array_equal(small[:-1], pts[:-1, :5])
     _, cnt0 = raw_contours(lib, case, param, heights, 0)

@@ -22,6 +22,7 @@ import pytest
 import scipy.sparse as sp
 
 import _morpho_align_case as mc
+from _kernel_scaffold import fresh_kernels as _k, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -50,16 +51,11 @@ def _ratio_table():
         print(f"| {tag} | {dtype} | {v:.3g} | {q} |")
 
 
-def _note(tag, dtype, q, dev, tol):
+def _ratio(tag, dtype, q, dev, tol):
     r = dev / tol
     if r > _WORST.get((tag, dtype), (0.0, ""))[0]:
         _WORST[(tag, dtype)] = (r, q)
     return r
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.tobytes()
 
 
 # ---- sparse layers: the same bits as dense ones ----
@@ -86,7 +82,7 @@ def test_update_assignment_csr_layers_equal_dense_layers(dtype):
         assert want.keys() == got.keys()
         for q in want:
             a, b = (v.toarray() if sp.issparse(v) else np.asarray(v) for v in (want[q], got[q]))
-            assert _bits(a) == _bits(b), (extra, q)
+            assert _same_bits(a, b), (extra, q)
 
 
 @pytest.mark.parametrize("dtype", ["float64", "float32"])
@@ -96,9 +92,8 @@ def test_assign_prepare_from_csr_equals_the_dense_path(dtype):
     import torch
 
     from spateo_amd import _lib
-    from spateo_amd._kernels import HipKernels
 
-    k = HipKernels("cuda:0", dtype)
+    k = _k(dtype)
     rng = np.random.default_rng(11)
     for n, g, density in ((607, 33, 0.5), (451, 33, 0.5), (64, 64, 1.0), (300, 7, 0.1), (1000, 130, 0.05), (9, 40, 0.0)):
         dense = rng.poisson(3.0, (n, g)).astype(np.float64) * (rng.random((n, g)) < density)
@@ -131,8 +126,8 @@ def test_csr_X_equals_dense_X_and_two_runs_agree(dtype):
         runs.append(_outputs(m))
     assert sp.issparse(mc.pair_samples(G, "1")[0].X)
     for q in runs[0]:
-        assert _bits(runs[0][q]) == _bits(runs[1][q]), ("two runs", q)
-        assert _bits(runs[0][q]) == _bits(runs[2][q]), ("CSR against dense", q)
+        assert _same_bits(runs[0][q], runs[1][q]), ("two runs", q)
+        assert _same_bits(runs[0][q], runs[2][q]), ("CSR against dense", q)
 
 
 # ---- the reference's cases ----
@@ -149,7 +144,7 @@ def test_pairwise_cases_against_the_reference(tag, dtype):
         got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
         assert got.shape == ref.shape, (q, got.shape, ref.shape)
         dev = float(np.abs(got - ref).max() / (scale if scale is not None else np.abs(ref).max()))
-        r = _note(tag, dtype, q, dev, tol)
+        r = _ratio(tag, dtype, q, dev, tol)
         print(f"  case {tag} {dtype} {q}: {dev:.2e} / {tol:.2e} ({r:.2g}x)")
         if not dev <= tol:
             bad.append((q, dev, tol))
@@ -231,7 +226,7 @@ def test_morpho_align_over_three_slices(mode, dtype):
             ref = G[f"4_{m_}_slice{i}_{key}"]
             tol = mc.bound(G[f"4_{m_}_slice{i}_g_{key}"], G[f"4_{m_}_slice{i}_f32_{key}"], f32)
             dev = float(np.abs(aligned[i].obsm[key] - ref).max() / np.abs(ref).max())
-            r = _note(tag, dtype, f"slice {i} {key}", dev, tol)
+            r = _ratio(tag, dtype, f"slice {i} {key}", dev, tol)
             print(f"  case {tag} {dtype} slice {i} {key}: {dev:.2e} / {tol:.2e} ({r:.2g}x)")
             if not dev <= tol:
                 bad.append((i, key, dev, tol))

@@ -14,6 +14,7 @@ import scipy.sparse as sp
 import torch
 
 import _pca_case as pc
+from _kernel_scaffold import bits as _bits
 
 pytestmark = pytest.mark.gpu
 
@@ -44,10 +45,6 @@ def _case(name):
             X = pc.planted(1000, 96, 10, seed=13)
             _DATA[name] = ([X[:400], sp.csr_matrix(X[400:750]), X[750:]], X, 10)
     return _DATA[name]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
 
 
 @pytest.mark.parametrize("dtype", ["float64", "float32"])

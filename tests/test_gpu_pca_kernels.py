@@ -15,12 +15,10 @@ import pytest
 import torch
 
 import _pca_case as pc
+from _kernel_scaffold import DEV, bits as _bits, guarded as _guarded, intact as _guard_ok, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-GUARD = 4096
-SENT = {torch.float64: -7.25e300, torch.float32: -7.25e30, torch.uint8: 0xA5}
 TD = {"float32": torch.float32, "float64": torch.float64}
 SHAPES = [(1, 1), (1, 129), (255, 15), (255, 128), (256, 16), (256, 200), (257, 17), (257, 127), (700, 1), (700, 129), (700, 200),
           (256, 128)]
@@ -38,23 +36,6 @@ def _cd(cell):
     from spateo_amd import _lib
 
     return _lib.MVF_F32 if cell == "float32" else _lib.MVF_F64
-
-
-def _guarded(n, tdtype=torch.float64):
-    return torch.full((n + GUARD,), SENT[tdtype], dtype=tdtype, device=DEV)
-
-
-def _guard_ok(t, n):
-    return bool((t[n:] == SENT[t.dtype]).all())
-
-
-def _stream():
-    return torch.cuda.current_stream(DEV).cuda_stream
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
 
 
 def _check(lib, rc, what):
@@ -251,7 +232,7 @@ def test_gram_on_a_packed_cache(lib, n, g, cell, tol):
     _, flat = run.host()
     Xc = pc.from_ublk(flat, n, g)[:n, :g].astype(np.float64)   # the operands as the device holds them
     ws_bytes = int(lib.mvf_gram_workspace_bytes(n, g, _cd(cell)))
-    ws = torch.full((ws_bytes + GUARD,), SENT[torch.uint8], dtype=torch.uint8, device=DEV)
+    ws = _guarded(ws_bytes, torch.uint8)
     P = torch.ones(n, dtype=TD[cell], device=DEV)
     got = []
     for _ in range(2):

@@ -13,7 +13,8 @@ import pytest
 import torch
 
 import _assign_edge_cases as ec
-from _align_kernel_scaffold import DEV, guarded, intact as _intact, kernels as _k
+from _align_kernel_scaffold import kernels as _k
+from _kernel_scaffold import DEV, guarded, intact as _intact
 
 pytestmark = pytest.mark.gpu
 

@@ -23,39 +23,14 @@ import pytest
 import torch
 
 import _rk45_cases as rc
+from _kernel_scaffold import DEV, bits as _bits, deviation_table, kernel_cache, Out as _Out, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 DTYPES = list(rc.DTYPES)
-SENTINEL = -1.2345e300   # t and traj are float64 in both cell dtypes (mvf.h: mvf_integrate_rk45), stats int32
-SENTINEL_I = -123456789
-GUARD = 4096  # elements in front of and behind every output buffer
 MAX_STEPS = 100_000
-_KERNELS = {}
-_WORST = {}
-
-
-def _k(dtype):
-    if dtype not in _KERNELS:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _KERNELS[dtype] = HipKernels(DEV, dtype)
-    return _KERNELS[dtype]
-
-
-def _note(family, dtype, value):
-    key = (family, dtype)
-    _WORST[key] = max(_WORST.get(key, 0.0), float(value))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _deviation_table():
-    yield
-    print("\n| case family | dtype | largest deviation |\n|---|---|---|")
-    for (family, dtype), v in sorted(_WORST.items()):
-        print(f"| {family} | {dtype} | {v:.3g} |")
+_k = kernel_cache()
+_note, _deviation_table = deviation_table("| case family | dtype | largest deviation |")
 
 
 def _x4(k, a):
@@ -86,13 +61,9 @@ def _tile(case, n):
     return case["starts"][idx], idx
 
 
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int64 if a.dtype == np.float64 else np.int32)
-
-
-def _same_bits(a, b):
-    return all(x.shape == y.shape and np.array_equal(_bits(x), _bits(y)) for x, y in zip(a, b))
+def _all_same_bits(a, b):
+    """Two tuples of outputs, array for array."""
+    return all(same_bits(x, y) for x, y in zip(a, b))
 
 
 def _check_rows_repeat(out, idx):
@@ -181,7 +152,7 @@ def test_lane_position(dtype, n, chunked):
     for sampling, n_out in (("uniform_time", 101), ("arc_length", 40)):
         out = _run(dtype, case, starts, n_out, sampling)
         assert out[0].shape == (n, n_out) and out[1].shape == (n, n_out, 3) and out[2].shape == (n, 4)
-        assert _same_bits(out, _run(dtype, case, starts, n_out, sampling))
+        assert _all_same_bits(out, _run(dtype, case, starts, n_out, sampling))
         _check_rows_repeat(out, idx)
         _check_scipy(dtype, "lanes" + (" (chunked)" if chunked else ""), case, out, n_out, sampling,
                      rows=_first_rows(idx, len(case["starts"])))
@@ -241,7 +212,7 @@ def test_zero_coefficient_tail_gives_the_bits_of_the_shorter_list(dtype, chunks)
     assert len(longer["ctrl"]) == chunks * cap + 1
     starts, _ = _tile(case, rc.COUNT_N)
     for sampling in rc.SAMPLINGS:
-        assert _same_bits(_run(dtype, case, starts, 40, sampling), _run(dtype, longer, starts, 40, sampling))
+        assert _all_same_bits(_run(dtype, case, starts, 40, sampling), _run(dtype, longer, starts, 40, sampling))
 
 
 # ------------------------------------------------------------------------------------------------------ c. dimension
@@ -259,7 +230,7 @@ def test_dimension(dtype, d):
             if d < 3:
                 g = rc.with_garbage(case)
                 assert (g["starts"][:, d:] == 7.0).all() and (g["C"][:, d:] == 7.0).all()
-                assert _same_bits(out, _run(dtype, g, None, 40, sampling))
+                assert _all_same_bits(out, _run(dtype, g, None, 40, sampling))
 
 
 # ------------------------------------------------------------------------------------------------------ d. sampling
@@ -323,7 +294,7 @@ def test_step_cap(dtype, sampling):
         if r["status"] == -2:
             assert stats[j, 0] + stats[j, 1] == rc.CAPPED_STEPS
         else:   # unaffected by the cap: the bits of the uncapped call
-            assert _same_bits([a[j] for a in (t, x, stats)], [a[j] for a in free])
+            assert _all_same_bits([a[j] for a in (t, x, stats)], [a[j] for a in free])
         if dtype == "float64":
             assert stats[j, 0] == r["accepted"] and stats[j, 1] == r["rejected"] and stats[j, 2] == 2 + 6 * (r["accepted"] + r["rejected"])
         et, ex = rc.resample(r["t"], r["x"], r["dense"], case["t_bound"], n_out, sampling)
@@ -354,7 +325,7 @@ def test_nonfinite_rows_in_a_chunked_block(dtype):
         t, x, stats = _run(dtype, case, bad, 12, sampling)
         assert (stats[lanes, 3] == -3).all() and np.isnan(t[lanes]).all() and np.isnan(x[lanes]).all()
         assert (clean[2][:, 3] == 0).all()
-        assert _same_bits([t[ok], x[ok], stats[ok]], [a[ok] for a in clean])
+        assert _all_same_bits([t[ok], x[ok], stats[ok]], [a[ok] for a in clean])
         _check_rows_repeat([a[ok] for a in (t, x, stats)], idx[ok])
 
 
@@ -388,18 +359,15 @@ def test_writes_nothing_around_its_buffers(dtype, n, chunked):
     k, x4, c4, Cd, code = _inputs(dtype, case, starts)
     for sampling, n_out in (("uniform_time", 9), ("arc_length", 2)):
         want = _run(dtype, case, starts, n_out, sampling)
-        tb = torch.full((2 * GUARD + n * n_out,), SENTINEL, dtype=torch.float64, device=DEV)
-        xb = torch.full((2 * GUARD + 3 * n * n_out,), SENTINEL, dtype=torch.float64, device=DEV)
-        sb = torch.full((2 * GUARD + 4 * n,), SENTINEL_I, dtype=torch.int32, device=DEV)
+        tb, xb, sb = _Out(n * n_out), _Out(3 * n * n_out), _Out(4 * n, dtype=torch.int32)  # t, traj: float64 in both cell dtypes
         w = (ctypes.c_double * 6)(*case["scale"], *case["offset"])
         _lib.check(k.lib.mvf_integrate_rk45(x4.data_ptr(), n, c4.data_ptr(), c4.shape[0], float(case["beta"]), Cd.data_ptr(),
                                             k._affine_buf(case["affine"]), case["d"], w, case["t_bound"], rc.RTOL, rc.ATOL,
-                                            case["max_step"], MAX_STEPS, code[sampling], n_out, tb[GUARD:].data_ptr(),
-                                            xb[GUARD:].data_ptr(), sb[GUARD:].data_ptr(), k.cdtype, k._stream()), "mvf_integrate_rk45")
+                                            case["max_step"], MAX_STEPS, code[sampling], n_out, tb.ptr, xb.ptr, sb.ptr,
+                                            k.cdtype, k._stream()), "mvf_integrate_rk45")
         torch.cuda.synchronize()
-        for buf, sentinel, ref in ((tb, SENTINEL, want[0]), (xb, SENTINEL, want[1]), (sb, SENTINEL_I, want[2])):
-            live = buf.numel() - 2 * GUARD
-            assert bool((buf[:GUARD] == sentinel).all()) and bool((buf[GUARD + live:] == sentinel).all())
-            got = buf[GUARD:GUARD + live].cpu().numpy()
-            assert not (got == sentinel).any()
+        for o, ref in ((tb, want[0]), (xb, want[1]), (sb, want[2])):
+            assert o.guards_intact()
+            got = o.host()
+            assert not (got == o.sent).any()
             assert np.array_equal(_bits(got), _bits(ref.reshape(-1)))

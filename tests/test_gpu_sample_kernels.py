@@ -12,13 +12,10 @@ import pytest
 import torch
 
 import _sample_cases as sc
+from _kernel_scaffold import (dev as _dev, guarded as _guarded, intact as _intact, ptr as _ptr, stream as _stream,
+                              take as _take)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-GUARD = 512
-SENT = {torch.float64: -7.25e300, torch.int64: -77, torch.int32: -77}
-
 
 @pytest.fixture(scope="module")
 def lib():
@@ -33,28 +30,6 @@ def G():
     return sc.load()
 
 
-def _stream():
-    return torch.cuda.current_stream(DEV).cuda_stream
-
-
-def _dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(DEV)
-
-
-def _guarded(n, tdtype):
-    return torch.full((n + GUARD,), SENT[tdtype], dtype=tdtype, device=DEV)
-
-
-def _take(t, n):
-    """The n live elements of a guarded output; the guard must be untouched."""
-    assert bool((t[n:] == SENT[t.dtype]).all()), "wrote past the end of an output"
-    return t[:n].cpu().numpy()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 class Trn:
     """One problem staged on the device: draws and schedules from the restatement's own helpers."""
 
@@ -64,7 +39,8 @@ class Trn:
         self.X, self.n, self.d = np.ascontiguousarray(X, dtype=np.float64), n, X.shape[1]
         w_idx, p_idx = sc.trn_draws(self.X, n, seed, tmax)
         l, ep, kc = sc.trn_schedule(n, tmax, c=c)
-        self.keep = [_dev(self.X), _dev(w_idx, np.int64), _dev(p_idx, np.int64), _dev(l), _dev(ep), None if kc is None else _dev(kc)]
+        self.keep = [_dev(self.X, None), _dev(w_idx, torch.int64), _dev(p_idx, torch.int64), _dev(l, None), _dev(ep, None),
+                     None if kc is None else _dev(kc, None)]
         self.W = _guarded(n * self.d, torch.float64)
         k = self.keep
         self.rec = _lib.TrnProblem(X=_ptr(k[0]), N=len(self.X), d=self.d, n=n, T=len(p_idx), w_idx=_ptr(k[1]), p_idx=_ptr(k[2]),
@@ -85,7 +61,7 @@ def _run_trn(lib, problems):
 
 def _nearest(lib, X, Q):
     X, Q = np.ascontiguousarray(X, dtype=np.float64), np.ascontiguousarray(Q, dtype=np.float64)
-    Xd, Qd = _dev(X), _dev(Q)
+    Xd, Qd = _dev(X, None), _dev(Q, None)
     need = int(lib.mvf_nearest_rows_workspace_bytes(len(X), len(Q)))
     ws = _guarded(need // 8, torch.float64)
     idx = _guarded(len(Q), torch.int64)
@@ -159,7 +135,7 @@ def test_trn_refusals_on_device_buffers(lib):
         setattr(rec, field, bad)
         assert lib.mvf_trn((_lib.TrnProblem * 1)(rec), 1, _stream()) != 0 and b"mvf_trn" in lib.mvf_last_error(), field
     torch.cuda.synchronize()
-    assert bool((pr.W == SENT[torch.float64]).all())                     # nothing was launched
+    assert _intact(pr.W, 0)                     # nothing was launched
 
 
 # --------------------------------------------------------------------------------------------------------- mvf_nearest_rows
@@ -185,7 +161,7 @@ def test_nearest_rows_many_queries_and_refusals(lib):
     X = sc.uniform_cloud(5000, 3, seed=2)                                # two chunks of candidates x 1000 queries (4 workgroups)
     Q = sc.uniform_cloud(1000, 3, seed=3)
     assert np.array_equal(_nearest(lib, X, Q), sc.nearest_restate(X, Q))
-    Xd, Qd, idx = _dev(X), _dev(Q), _guarded(1000, torch.int64)
+    Xd, Qd, idx = _dev(X, None), _dev(Q, None), _guarded(1000, torch.int64)
     need = int(lib.mvf_nearest_rows_workspace_bytes(5000, 1000))
     ws = _guarded(need // 8, torch.float64)
     for kw in (dict(d=4), dict(N=0), dict(ws_bytes=need - 1), dict(ws=None), dict(idx=None)):
@@ -194,16 +170,16 @@ def test_nearest_rows_many_queries_and_refusals(lib):
         rc = lib.mvf_nearest_rows(a["X"], a["N"], a["d"], a["Q"], a["n"], a["idx"], a["ws"], a["ws_bytes"], _stream())
         assert rc != 0 and b"mvf_nearest_rows" in lib.mvf_last_error(), kw
     torch.cuda.synchronize()
-    assert bool((idx == SENT[torch.int64]).all()) and bool((ws == SENT[torch.float64]).all())
+    assert _intact(idx, 0) and _intact(ws, 0)
 
 
 # --------------------------------------------------------------------------------------------------------------- mvf_kmeans
 def _kmeans(lib, X, C0, iters):
     X = np.ascontiguousarray(X, dtype=np.float64)
     N, d, n = len(X), X.shape[1], len(C0)
-    Xd = _dev(X)
+    Xd = _dev(X, None)
     C = _guarded(n * d, torch.float64)
-    C[: n * d] = _dev(C0).reshape(-1)
+    C[: n * d] = _dev(C0, None).reshape(-1)
     need = int(lib.mvf_kmeans_workspace_bytes(N, n))
     ws = _guarded(need // 8, torch.float64)
     labels, counts = _guarded(N, torch.int32), _guarded(n, torch.int64)
@@ -252,7 +228,7 @@ def test_kmeans_empty_cluster_keeps_its_centroid(lib):
 
 def test_kmeans_refusals_on_device_buffers(lib):
     X = sc.uniform_cloud(500, 2, seed=1)
-    Xd, C = _dev(X), _guarded(8 * 2, torch.float64)
+    Xd, C = _dev(X, None), _guarded(8 * 2, torch.float64)
     need = int(lib.mvf_kmeans_workspace_bytes(500, 8))
     ws, labels, counts = _guarded(need // 8, torch.float64), _guarded(500, torch.int32), _guarded(8, torch.int64)
     for kw in (dict(d=0), dict(iters=0), dict(ws_bytes=need - 1), dict(ws=None), dict(labels=None), dict(counts=None), dict(N=-1)):
@@ -263,4 +239,4 @@ def test_kmeans_refusals_on_device_buffers(lib):
         assert rc != 0 and b"mvf_kmeans" in lib.mvf_last_error(), kw
     torch.cuda.synchronize()
     for t in (C, ws, labels, counts):
-        assert bool((t == SENT[t.dtype]).all())
+        assert _intact(t, 0)

@@ -16,129 +16,32 @@ figures: the warm start's sweep count on the rank-1 family on a moved matrix, an
 mvf_solve_minnorm_lrd (block Ritz values, 5e-7 ... 4e-4 above the eigenvalue).  Run with ``-s`` for the largest |deviation| / bound per (entry point, family):
 profiles/solve_kernel_edges.md records them."""
 import ctypes
-import time
 
 import numpy as np
 import pytest
 import torch
 
 import _solve_cases as sc
+from _kernel_scaffold import (SENTINEL as _SENTINEL, WS_FILL, dev as _dev, deviation_table, kernel_cache, option as _option,
+                              Out as _Out, same_bits as _same_bits, stream as _stream, Ws as _Ws, x4 as _x4)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 LD = np.longdouble
-SENTINEL = -1.2345e300
-ISENTINEL = -777
-GUARD = 4096        # elements in front of and behind every output buffer
-GUARD_BYTES = 4096  # bytes in front of and behind the workspace (keeps its 256-byte alignment)
-WS_FILL = 0xA5
-_K = {}
-_WORST = {}
-_COUNT = [0]
+SENTINEL, ISENTINEL = _SENTINEL[torch.float64], _SENTINEL[torch.int32]  # what untouched float64 / int32 outputs hold
 _REFS = {}
-
-
-def _k(dtype="float64"):
-    if dtype not in _K:
-        from spateo_amd._kernels import HipKernels
-
-        assert torch.cuda.is_available(), "GPU tests need a HIP device"
-        _K[dtype] = HipKernels(DEV, dtype)
-    return _K[dtype]
+_k = kernel_cache()
+_note, _deviation_table = deviation_table(
+    "| entry point | family | largest |deviation| / bound |",
+    footer=lambda seconds, notes: f"test_gpu_solve_kernels: {seconds:.1f} s, {notes} reference comparisons")
 
 
 def _lib():
     return _k().lib
 
 
-def _stream():
-    return _k()._stream()
-
-
 def _last_error():
     return _lib().mvf_last_error().decode("utf-8", "replace")
-
-
-def _note(entry, family, value):
-    key = (entry, family)
-    _WORST[key] = max(_WORST.get(key, 0.0), float(value))
-    _COUNT[0] += 1
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _deviation_table():
-    t0 = time.perf_counter()
-    yield
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    print(f"\ntest_gpu_solve_kernels: {time.perf_counter() - t0:.1f} s, {_COUNT[0]} reference comparisons")
-    print("| entry point | family | largest |deviation| / bound |\n|---|---|---|")
-    for (entry, family), v in sorted(_WORST.items()):
-        print(f"| {entry} | {family} | {v:.3g} |")
-
-
-class _option:
-    """A developer option of the library for the length of a block; restored on the way out."""
-
-    def __init__(self, name, value):
-        self.name, self.value = name, value
-
-    def __enter__(self):
-        from spateo_amd import _lib
-
-        self.old = _lib.debug_option(self.name, self.value)
-
-    def __exit__(self, *exc):
-        from spateo_amd import _lib
-
-        _lib.debug_option(self.name, self.old)
-
-
-class _Out:
-    """An output buffer inside a larger tensor: GUARD sentinel elements either side, the payload sentinel-filled too."""
-
-    def __init__(self, *shape, dtype=torch.float64, fill=None):
-        self.sent = (SENTINEL if dtype.is_floating_point else ISENTINEL) if fill is None else fill
-        n = int(np.prod(shape)) if shape else 1
-        self.big = torch.full((n + 2 * GUARD,), self.sent, dtype=dtype, device=DEV)
-        self.t = self.big[GUARD:GUARD + n].view(*shape)
-        self.n = n
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def guards_intact(self):
-        return bool((self.big[:GUARD] == self.sent).all()) and bool((self.big[GUARD + self.n:] == self.sent).all())
-
-    def untouched(self):
-        return bool((self.t == self.sent).all())
-
-    def host(self):
-        return self.t.cpu().numpy().copy()
-
-
-class _Ws:
-    """A workspace of exactly `nbytes` inside GUARD_BYTES either side, everything filled with WS_FILL (`fill` for the payload)."""
-
-    def __init__(self, nbytes, fill=WS_FILL):
-        self.nbytes = int(nbytes)
-        self.big = torch.full((self.nbytes + 2 * GUARD_BYTES,), WS_FILL, dtype=torch.uint8, device=DEV)
-        if fill != WS_FILL:
-            self.big[GUARD_BYTES:GUARD_BYTES + self.nbytes] = fill
-        assert self.big.data_ptr() % 256 == 0
-
-    @property
-    def ptr(self):
-        return self.big.data_ptr() + GUARD_BYTES
-
-    def guards_intact(self):
-        return bool((self.big[:GUARD_BYTES] == WS_FILL).all()) and bool((self.big[GUARD_BYTES + self.nbytes:] == WS_FILL).all())
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(DEV)
 
 
 _DEVICE_CASES = {}
@@ -192,14 +95,6 @@ def _call(entry, Gd, Kd, ls2, R, *, jitter=0.0, shift=sc.SHIFT, rcond=2.0 ** -52
     out.rc, out.ws, out.C_untouched, out.piv_untouched = rc, ws, C.untouched(), piv.untouched()
     out.C, out.info, out.piv, out.einfo = C.host(), int(info.host()[0]), piv.host(), einfo.host()
     return out
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int64)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
 def _cstar(c, R):
@@ -752,12 +647,6 @@ def test_lrd_async_is_refused_outside_128_to_640(m):
 PINV_N = [0, 1, 7, 8, 9, 257]
 
 
-def _x4(a, dtype):
-    buf = np.zeros((len(a), 4), dtype=dtype)
-    buf[:, :3] = a
-    return torch.from_numpy(buf).to(DEV)
-
-
 def _leverage_case(m, dtype):
     """The system and the longdouble reference of one (m, cell dtype): A = U^T U of 257 cells (float64 coordinates, one
     float64 eigh), leverage = sum over the kept eigenpairs of (U q)^2 / lambda with U taken at the coordinates rounded to the
@@ -800,7 +689,7 @@ def test_pinv_diag_is_the_leverage(m, lowrank, dtype):
             assert out.untouched()
             continue
         d = out.host()[:n]
-        assert bool((out.t[n:] == SENTINEL).all())
+        assert bool((out.t[n:] == out.sent).all())
         dev = float(np.abs(d.astype(LD) - lc["ref"][:n]).max() / lc["ref"].max())
         _note(f"mvf_pinv_diag[{dtype}, lowrank {lowrank}]", f"m {m}", dev / bound)
         print(f"    n {n}: |d - ref| / max ref = {dev:.3g} (bound {bound:.3g})")

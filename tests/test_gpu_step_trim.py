@@ -23,12 +23,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_golden_step_trim as gen  # noqa: E402
-
-
-def _k(dtype="float32"):
-    from spateo_amd._kernels import HipKernels
-
-    return HipKernels("cuda:0", dtype)
+from _kernel_scaffold import fresh_kernels as _k, option as _option  # noqa: E402
 
 
 def _inputs(k, seed, n, m):
@@ -60,7 +55,7 @@ def _recompute_and_cached(kk, x4, P, y4, c4, beta, m):
 @pytest.mark.parametrize("n", [255, 256, 4097, 70_001])
 def test_cached_equals_recompute_float32(n, m):
     """The tail of the widened P (n not a multiple of 256, the last slice padded) and the rhs next to it."""
-    kk = _k()
+    kk = _k("float32")
     x4, c4, y4, P = _inputs(kk, 1000 + n + m, n, m)
     G, R, Gc, Rc = _recompute_and_cached(kk, x4, P, y4, c4, 0.003, m)
     assert torch.equal(G, Gc) and torch.equal(R, Rc)
@@ -74,12 +69,9 @@ def test_phases_and_workspace_reuse_float32(n_first, n):
     HipKernels: what the earlier call left in the workspace (its widened P among it) must not leak, and a second call gives the
     same bits.  At 300 001 cells the 1172 slices x 6 tile pairs still fit the minimum partial-tile buffer (one phase); 1 200 001
     cells need two phases, each widening its own cells of P."""
-    from spateo_amd import _lib
-
     m, beta = 300, 0.003
-    _lib.debug_option("slice_len", 256)
-    try:
-        kk = _k()
+    with _option("slice_len", 256):
+        kk = _k("float32")
         x4, c4, y4, P = _inputs(kk, 5, n_first, m)
         kk.build_ublk(x4, c4, beta)
         kk.gram(x4, P, y4, c4, beta, *_gr(m))  # the longer call: fills the workspace
@@ -97,8 +89,6 @@ def test_phases_and_workspace_reuse_float32(n_first, n):
         kk.gram(x4, P, y4, c4, beta, G3, R3)
         assert len(kk.gram_events) == 1 and torch.equal(G3, Gc) and torch.equal(R3, Rc)
         kk.drop_ublk()
-    finally:
-        _lib.debug_option("slice_len", 0)
 
 
 @pytest.mark.parametrize("m,dtype", gen.CASES)
@@ -173,7 +163,7 @@ def test_apply_packed_lanes_equal_one_cell_per_lane(n, cpt, m):
     must agree bit for bit.  (The parent-bits fixture's 70 001 cells run one cell per lane: it pins the rhs kernel and the rest
     of the step, this test pins the packed apply.)  m = 130: one LDS stage, padded to a multiple of 4; m = 600: two stages."""
     assert (-(-n // (256 * cpt)) >= 1024) and (cpt == 4 or -(-n // (256 * 2 * cpt)) < 1024)  # the launch really takes `cpt`
-    kk = _k()
+    kk = _k("float32")
     x4, c4, y4, P = _inputs(kk, 2000 + n + m, n, m)
     C = torch.from_numpy(np.random.default_rng(3).standard_normal((m, 3))).to("cuda:0")
     beta = 0.003

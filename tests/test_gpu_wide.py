@@ -15,21 +15,15 @@ import numpy as np
 import pytest
 import torch
 
+from _kernel_scaffold import DTYPES, bits_equal as _same_bits, fresh_kernels as _k
+
 pytestmark = pytest.mark.gpu
 
 U64 = 2.0 ** -53
 UT = {"float32": 2.0 ** -24, "float64": 2.0 ** -53}
 NPT = {"float32": np.float32, "float64": np.float64}
-DTYPES = ["float64", "float32"]
 SENT = -7.25  # sentinel of the "nothing is written outside the live region" tests
 RATIOS = {}   # (quantity, dtype) -> largest error / bound over the cases run so far (printed with every case)
-
-
-def _k(dtype):
-    from spateo_amd._kernels import HipKernels
-
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return HipKernels("cuda:0", dtype)
 
 
 def _cdiv(a, b):
@@ -38,15 +32,6 @@ def _cdiv(a, b):
 
 def _pad16(dy):
     return _cdiv(dy, 16) * 16
-
-
-def _bits(t):
-    """The tensor's bit patterns: equality below is equality of bits (-0.0 != +0.0, a NaN equals itself)."""
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
 
 
 class Case:
@@ -160,7 +145,7 @@ class Case:
         return R, Vd, r, stats
 
 
-def _note(name, dtype, err, bound):
+def _ratio(name, dtype, err, bound):
     """Largest err / bound of this array (0 / 0 counts as 0); keeps the running maximum per (quantity, dtype)."""
     err, bound = np.asarray(err, dtype=np.float64), np.asarray(bound, dtype=np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -192,22 +177,22 @@ def check_against_float64(case):
     Rg = R.cpu().numpy()
     assert Rg.shape == (m, dy) and np.isfinite(Rg).all()
     err, bound = np.abs(Rg - R_ref), (n + 2) * U64 * R_abs
-    out["rhs"] = _note("rhs", dtype, err, bound)
+    out["rhs"] = _ratio("rhs", dtype, err, bound)
     # ---- apply: V
     Vg = Vd.cpu().numpy().astype(np.float64)[:, :dy]
     assert np.isfinite(Vg).all()
     errv, boundv = np.abs(Vg - V_ref), (case.m_pad + 1) * U64 * V_abs + uT * np.abs(V_ref)
-    out["V"] = _note("V", dtype, errv, boundv)
+    out["V"] = _ratio("V", dtype, errv, boundv)
     # ---- apply: r against the field as read back
     rg = r.cpu().numpy().astype(np.float64)
     r_ref = np.sum((Y.astype(ld) - Vg.astype(ld)) ** 2, 1)
     errr, boundr = np.abs(rg.astype(ld) - r_ref), ((dy + 2) * U64 + _cdiv(dy, 128) * uT) * r_ref
-    out["r"] = _note("r", dtype, errr, boundr)
+    out["r"] = _ratio("r", dtype, errr, boundr)
     # ---- apply: stats[0] += sum P r, with r as read back
     sg = float(stats.cpu()[0])
     pr = P.astype(ld) * rg.astype(ld)
     errs, bounds = abs(ld(sg) - (ld(s0) + pr.sum())), (n + 2) * U64 * pr.sum()
-    out["stats"] = _note("stats", dtype, [errs], [bounds])
+    out["stats"] = _ratio("stats", dtype, [errs], [bounds])
     print(f"wide n={n} m={m} dy={dy} D={case.D} {dtype}: error / bound  " + "  ".join(f"{q} {v:.2e}" for q, v in out.items())
           + "   | maxima so far  " + "  ".join(f"{q}/{d} {v:.2e}" for (q, d), v in sorted(RATIOS.items())))
     assert (err <= bound).all(), f"rhs: {int((err > bound).sum())} of {err.size} entries outside the bound, worst ratio {out['rhs']:.3g}"
