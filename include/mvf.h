@@ -97,7 +97,9 @@ int mvf_knn_rowsum(const double* X, int64_t m, int d, int k, double* rowsum, voi
  * A point lies in a convex hull iff it is on the inner side of every facet: inside[i] = (max_f n_f . p_i + d_f <= tol).
  * points: n x 3 float64 row-major; equations: nfacets x 4 float64 = SciPy `ConvexHull(X).equations` (built on the host
  * with Qhull, as the reference does); inside: n bytes (0 / 1).  tol: the caller passes 100 eps x the hull's extent,
- * the scale of find_simplex's own barycentric tolerance. */
+ * the scale of find_simplex's own barycentric tolerance.  A point at margin exactly tol is inside; a point with a NaN or
+ * infinite coordinate is outside.  Limit: the equations must be finite - a facet whose value at a point is NaN does not
+ * constrain that point (fmax drops a NaN operand), so a row of NaN acts as if it were not in the list. */
 int mvf_hull_mask(const double* points, int64_t n, const double* equations, int64_t nfacets, double tol,
                   unsigned char* inside, void* stream);
 
@@ -107,7 +109,8 @@ int mvf_hull_mask(const double* points, int64_t n, const double* equations, int6
  * (cdist path :21-24).  x: n x d, y: m x d, plain row-major (NOT x4), 1 <= d <= 8.  HBM-write-bound. */
 int mvf_con_k(const void* x, int64_t n, const void* y, int64_t m, int d, double beta, void* K, mvf_dtype dtype,
               void* stream);
-/* return_d=True variant (gaussian_process.py:25-29): also D[n, :, m] = x_n - y_m as n x d x m. */
+/* return_d=True variant (gaussian_process.py:25-29): also D[n, :, m] = x_n - y_m as n x d x m.  At most 65535 rows per call;
+ * K is computed first, so a call refused for its row count or a null D has already written K and leaves D alone. */
 int mvf_con_k_d(const void* x, int64_t n, const void* y, int64_t m, int d, double beta, void* K, void* D,
                 mvf_dtype dtype, void* stream);
 
