@@ -907,6 +907,40 @@ int mvf_kde(const void* t4, int64_t n, const void* s4, int64_t N, int d, int ker
  * and the shifts; 0 for an empty or refused shape. */
 size_t mvf_kde_workspace_bytes(int64_t n, int64_t N, int C);
 
+/* ---- shape of the cloud: the per-subspace descriptors of the shape similarity (mvf_shape.hip) -----------------------------
+ * Two additions to the table (mvf_version stays 7 by the rule above). */
+#define MVF_SHAPE_MAX_NSUB 128
+/* Replaces: the loop of `model_eigenvector` (spateo/tdr/morphometrics/shape_similarity.py:164-177) over `rough_subspace`
+ * (15-56), `subspace_surface_fitting` (59-110), `dist_global_centroid_to_subspace` (113-120) and
+ * `cos_global_centroid_to_subspace` (123-133).  float64 throughout and no dtype argument: the fit is a polynomial in raw
+ * monomials whose condition number sits at 1 / eps, and float32 storage of the coordinates would decide its rank.
+ *   pts (n x 3 float64, device), 1 <= n < 2^31.  lo, hi (3 x nsub float64 each, device; axis-major): the interval ends of the
+ *   voxels, computed by the host with the reference's own expressions `min + j * size` and `(min + j * size) + size`.
+ *   1 <= nsub <= MVF_SHAPE_MAX_NSUB.  order: 1 linear [x, y, 1], 2 quadratic [1, x, y, xy, x^2, y^2], 3 cubic
+ *   [1, x, y, x^2, xy, y^2, x^3, x^2 y, x y^2, y^3].  centroid (3 float64, HOST): the mean of all points.
+ * Outputs (device):
+ *   point_voxel (n int32): the voxel (layer nsub^2 + line nsub + piece; piece x, line y, layer z) whose intervals hold the
+ *     point with `lo <= x` and `x < hi`, or -1 when none does (an upper face of the cuboid when ceil(ptp) == ptp).  A point
+ *     two intervals of one axis hold goes to the lower one - the reference would count it twice.
+ *   per kept voxel (count >= 2), in voxel order, min(nsub^3, n / 2) entries each: voxel (int32), count (int64), cosine
+ *     (|c_z - g_z| / |c - g|, c the voxel's centroid), dist (the mean distance from the global centroid to the 20 x 20
+ *     surface of the fit over the voxel's own x, y extent), rank (int32: singular values above 2^-52 sigma_max, gelsd's
+ *     cond=None; the coefficients are the minimum-norm solution), sv (2 float64: sigma_max, and the smallest kept singular
+ *     value over sigma_max).
+ *   counts (3 int64): the number of kept voxels, of points with voxel -1 (n_dropped), and of points two intervals of one axis
+ *     hold (n_overlap).
+ * The points are grouped by a stable sort on the voxel id, each voxel is fitted by one workgroup (Householder QR of the
+ * streamed rows, one-sided Jacobi SVD of the triangle), every sum in an order fixed by the counts: two calls give equal bits.
+ * workspace: mvf_shape_descriptors_workspace_bytes(n, nsub), 256-byte aligned.  Refused: "bad shape" (n, nsub), "bad order",
+ * "null pointer", "workspace too small". */
+int mvf_shape_descriptors(const double* pts, int64_t n, const double* lo, const double* hi, int nsub, int order,
+                          const double* centroid, int32_t* point_voxel, int32_t* voxel, int64_t* count, double* cosine,
+                          double* dist, int32_t* rank, double* sv, int64_t* counts, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* Replaces: the copies `rough_subspace` (shape_similarity.py:46-51) makes of the cloud.  The sort buffers of the grouping
+ * and two int32 per voxel; 0 for a refused shape. */
+size_t mvf_shape_descriptors_workspace_bytes(int64_t n, int nsub);
+
 #ifdef __cplusplus
 }
 #endif

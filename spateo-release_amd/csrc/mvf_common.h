@@ -159,6 +159,13 @@ inline EvalAffine eval_affine_from_host(const double* affine) {
     return af;
 }
 
+// The stable LSD radix sort of (uint64 key, int64 value) pairs of mvf_prep.hip, for the other source files: n < 2^32 pairs, by
+// the low `bits` key bits (8 per pass).  The caller writes the pairs into the buffers sort_pairs_input names inside a workspace
+// of sort_pairs_bytes(n) (256-byte aligned); sort_pairs leaves the buffers that hold the result in *keys / *vals.
+size_t sort_pairs_bytes(int64_t n);
+void sort_pairs_input(void* workspace, int64_t n, unsigned long long** keys, long long** vals);
+void sort_pairs(hipStream_t st, void* workspace, int64_t n, int bits, unsigned long long** keys, long long** vals);
+
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

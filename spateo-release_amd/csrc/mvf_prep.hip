@@ -296,11 +296,12 @@ static void exclusive_scan_u32(hipStream_t st, unsigned int* t, int64_t L, unsig
     hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nseg), dim3(256), 0, st, t, L, segsum);
 }
 
-// stable sort of (keys, vals) by all 64 key bits; result in (*ka, *ia) - the buffers are swapped as the passes go
+// stable sort of (keys, vals) by the low `bits` key bits (all 64 by default); result in (*ka, *ia) - the buffers are swapped as
+// the passes go
 static void radix_sort_pairs_u64(hipStream_t st, const PrepPlan& p, int64_t n, unsigned long long*& ka,
                                  unsigned long long*& kb, long long*& ia, long long*& ib, unsigned int* hist,
-                                 unsigned int* segsum) {
-    for (int shift = 0; shift < 64; shift += 8) {
+                                 unsigned int* segsum, int bits = 64) {
+    for (int shift = 0; shift < bits; shift += 8) {
         hipLaunchKernelGGL(rs_hist_kernel, dim3((unsigned)p.nblocks), dim3(256), 0, st, ka, n, shift, p.nblocks, hist);
         exclusive_scan_u32(st, hist, p.L, segsum, nullptr);
         hipLaunchKernelGGL(rs_scatter_kernel, dim3((unsigned)p.nblocks), dim3(256), 0, st, ka, ia, kb, ib, n, shift,
@@ -310,6 +311,21 @@ static void radix_sort_pairs_u64(hipStream_t st, const PrepPlan& p, int64_t n, u
     }
 }
 
+// The same sort for another source file (mvf_shape.hip groups its points by voxel with it; declared in mvf_common.h)
+size_t sort_pairs_bytes(int64_t n) { return prep_plan(n).total; }
+void sort_pairs_input(void* workspace, int64_t n, unsigned long long** keys, long long** vals) {
+    const PrepPlan p = prep_plan(n);
+    *keys = (unsigned long long*)((char*)workspace + p.off_keys_a);
+    *vals = (long long*)((char*)workspace + p.off_idx_a);
+}
+void sort_pairs(hipStream_t st, void* workspace, int64_t n, int bits, unsigned long long** keys, long long** vals) {
+    const PrepPlan p = prep_plan(n);
+    char* ws = (char*)workspace;
+    unsigned long long *ka = (unsigned long long*)(ws + p.off_keys_a), *kb = (unsigned long long*)(ws + p.off_keys_b);
+    long long *ia = (long long*)(ws + p.off_idx_a), *ib = (long long*)(ws + p.off_idx_b);
+    radix_sort_pairs_u64(st, p, n, ka, kb, ia, ib, (unsigned int*)(ws + p.off_hist), (unsigned int*)(ws + p.off_seg), bits);
+    *keys = ka, *vals = ia;
+}
 
 // ---- kNN bandwidth of the control points ----------------------------------------------------------------------------
 // dynamo `bandwidth_selector`: exact kNN with k = max(2, int(0.2 m)) neighbours (self included), d = mean of the k - 1

@@ -1113,6 +1113,41 @@ class HipKernels:
                 out[:, c0 : c0 + cc] = part
         return np.array(self.d2h(out))
 
+    # ---- shape of the cloud (mvf_shape.hip): float64 whatever the cell dtype ----
+    @_on_device
+    def shape_queue(self, pts, lo, hi, order, centroid):
+        """mvf_shape_descriptors queued on the current stream, nothing read back: pts (n, 3) host float64, lo / hi the (3, nsub)
+        interval tables, order 1 | 2 | 3, centroid the mean of the points.  Returns what ``shape_read`` takes; each queued call
+        owns its buffers, so any number of them may wait for one read."""
+        pts = np.ascontiguousarray(pts, dtype=np.float64)
+        n, nsub = int(pts.shape[0]), int(np.shape(lo)[1])
+        cap = max(min(nsub ** 3, n // 2), 1)
+        dp = self.h2d(pts)
+        dlo, dhi = self.h2d(np.ascontiguousarray(lo, dtype=np.float64)), self.h2d(np.ascontiguousarray(hi, dtype=np.float64))
+        i32, i64, f64 = torch.int32, torch.int64, torch.float64
+        outs = [self.empty(n, dtype=i32), self.empty(cap, dtype=i32), self.empty(cap, dtype=i64), self.empty(cap, dtype=f64),
+                self.empty(cap, dtype=f64), self.empty(cap, dtype=i32), self.empty(cap, 2, dtype=f64), self.empty(3, dtype=i64)]
+        need = int(self.lib.mvf_shape_descriptors_workspace_bytes(n, nsub))
+        ws = self.empty(max(need // 8, 1), dtype=f64)
+        g = (C.c_double * 3)(*[float(v) for v in centroid])
+        _lib.check(self.lib.mvf_shape_descriptors(_ptr(dp), n, _ptr(dlo), _ptr(dhi), nsub, int(order), g, *[_ptr(t) for t in outs],
+                                                  _ptr(ws), ws.numel() * 8, self._stream()), "mvf_shape_descriptors")
+        return outs, (dp, dlo, dhi, ws)  # (the inputs and the workspace live until the read)
+
+    @_on_device
+    def shape_read(self, queued):
+        """The results of ``shape_queue`` calls with one synchronisation: a list of dicts of host arrays, the per-subspace ones
+        cut to the number of kept subspaces."""
+        host = self.to_host([t for outs, _ in queued for t in outs], own_pinned=False)
+        res = []
+        for q in range(len(queued)):
+            pv, voxel, count, cosine, dist, rank, sv, counts = host[8 * q : 8 * q + 8]
+            m = int(counts[0])
+            res.append(dict(voxel=voxel[:m].copy(), count=count[:m].copy(), cosine=cosine[:m].copy(), dist=dist[:m].copy(),
+                            rank=rank[:m].copy(), sigma_max=sv[:m, 0].copy(), sigma_min_ratio=sv[:m, 1].copy(), point_voxel=pv,
+                            n_dropped=int(counts[1]), n_overlap=int(counts[2])))
+        return res
+
     # ---- PCA across slices on the kernel-value cache (mvf_pca.hip + the cached Gram / apply kernels, unchanged) ----
     PCA_UPLOAD_BYTES = 256 << 20  # rows of a dense slice travel in chunks of at most this much (each chunk is a slice of its own)
 

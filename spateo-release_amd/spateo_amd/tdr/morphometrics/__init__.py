@@ -1,3 +1,4 @@
+from .model_morphology import model_morphology
 from .morphofield import (
     _morphofield_sparsevfc,
     cell_directions,
@@ -16,3 +17,10 @@ from .morphofield_dg import (
     morphofield_velocity,
 )
 from .morphology import cell_density, kernel_density, pc_KDE
+from .shape_similarity import (
+    calculate_eigenvector,
+    model_eigenvector,
+    pairwise_shape_similarity,
+    shape_similarity_matrix,
+    subspace_descriptors,
+)

@@ -8,7 +8,8 @@ not ``log 0``.  ``kernel_density`` is the general form (other targets, ``sample_
 ``cell_density`` the same on an AnnData.
 
 Not here, by name: d > 3; sklearn's ``atol`` / ``rtol`` (the device result is the exact sum); ``bandwidth="scott"`` /
-``"silverman"``; metrics other than the Euclidean; ``model_morphology`` (needs a surface mesh's area and volume from pyvista).
+``"silverman"``; metrics other than the Euclidean.  ``model_morphology`` of the same reference module lives in
+``model_morphology.py``.
 """
 from __future__ import annotations
 
