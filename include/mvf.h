@@ -941,6 +941,47 @@ int mvf_shape_descriptors(const double* pts, int64_t n, const double* lo, const 
  * and two int32 per voxel; 0 for a refused shape. */
 size_t mvf_shape_descriptors_workspace_bytes(int64_t n, int nsub);
 
+/* ---- digitization: the two Jacobi relaxations of the heat equation, whole loops on the device (mvf_heat.hip) -------------
+ * Four additions to the table (mvf_version stays 7 by the rule above).  float64 throughout, no floating-point atomics: two calls
+ * give equal bits.  Both entries run the whole loop, read the device's status block every few batches and return when it has
+ * stopped: they block.  The stop rule is the reference's `while (err > max_err) and (itr <= max_itr)`, evaluated like that: a NaN
+ * err (an all-zero field gives 0 / 0) ends the loop after one sweep, and floor(max_itr) + 1 sweeps run at most.
+ * Host outputs of both: sweeps (the reference's `itr`), err (the last one; 1 when no sweep ran), hit_max_itr (1 when
+ * err > max_err still held at the end: the sweep budget ended the loop). */
+#define MVF_HEAT_MAX_STEPS 8
+/* Replaces: the loop of `domain_heat_eqn_solver` (spateo/digitization/utils.py:508-522) with `effective_L2_error` (445-461).
+ *   init (H x W float64, device): the heat field with the four boundary lines written (`init_field`); border, mask (H x W
+ *   float64 each, device): `field_border` and `field_mask` as the reference takes them - a pixel is fixed when border != 0 or
+ *   when it lies on the array's outer rows or columns, and the mask is a weight (its values multiply).  3 <= H, W < 2^20.
+ *   One sweep: new[y, x] = 0.25 * (((old[y, x+1] + old[y, x-1]) + old[y+1, x]) + old[y-1, x]) on every pixel that is not fixed, the
+ *   whole array over; S1 = sum (new - old)^2 mask, S0 = sum old^2 mask, err = sqrt(S1 / S0).
+ *   block_steps: the sweeps one launch runs in LDS, 1 .. MVF_HEAT_MAX_STEPS (1: the plain one-sweep kernel), or 0 for the
+ *   dispatcher's choice (MVF_HEAT_MAX_STEPS: faster at every raster measured).  The field does not depend on it, bit for bit.
+ *   out (H x W float64, device): field * mask.
+ * workspace: mvf_heat_grid_workspace_bytes(H, W), 256-byte aligned.  Refused, with nothing launched: "bad shape", "bad
+ * block_steps", "null pointer", "workspace too small". */
+int mvf_heat_grid(const double* init, const double* border, const double* mask, int64_t H, int64_t W, double max_err,
+                  double max_itr, int block_steps, double* out, int64_t* sweeps, double* err, int* hit_max_itr,
+                  void* workspace, size_t workspace_bytes, void* stream);
+/* Replaces: the copies the loop makes per sweep (utils.py:512-516).  The status block, two fields, MVF_HEAT_MAX_STEPS pairs of
+ * partial sums per 32 x 64 tile and one byte per pixel; 0 for a refused shape. */
+size_t mvf_heat_grid_workspace_bytes(int64_t H, int64_t W);
+/* Replaces: the loop of `digitize_general` (spateo/digitization/utils.py:553-575) and its dense N x N `adj_mtx`.
+ *   indptr (n + 1 int64), indices (nnz int32), values (nnz float64): the CSC arrays of `adj_mtx`, on the HOST - for node j the
+ *   rows i with A_ij != 0 in ascending i; they are checked here and copied into the workspace.  fixed_value (n float64, HOST):
+ *   the reference's `mask_field`, which is also the starting field.  1 <= n < 2^31.
+ *   One sweep: new_j = sum_i old_i A_ij, added one after the other in ascending i from 0; a node with fixed_value != 0 then takes
+ *   fixed_value (heat 0 is not held).  S1 = sum (new - old)^2, S0 = sum new^2, err = sqrt(S1 / S0).  One launch per sweep.
+ *   out (n float64, device): the field.
+ * workspace: mvf_heat_graph_workspace_bytes(n, nnz), 256-byte aligned.  Refused, with nothing launched: "bad shape", "null
+ * pointer", "bad indptr" (not from 0, or falling), "index out of range", "workspace too small". */
+int mvf_heat_graph(const int64_t* indptr, const int32_t* indices, const double* values, const double* fixed_value, int64_t n,
+                   double max_err, double max_itr, double* out, int64_t* sweeps, double* err, int* hit_max_itr, void* workspace,
+                   size_t workspace_bytes, void* stream);
+/* Replaces: the dense `adj_mtx` (n x n float64) of `digitize_general`.  The status block, three vectors, the partial sums and the
+ * CSC arrays; 0 for a refused shape. */
+size_t mvf_heat_graph_workspace_bytes(int64_t n, int64_t nnz);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1148,6 +1148,52 @@ class HipKernels:
                             n_dropped=int(counts[1]), n_overlap=int(counts[2])))
         return res
 
+    # ---- digitization (mvf_heat.hip): the heat-equation loops, float64 whatever the cell dtype ----
+    def _heat_ws(self, need):
+        """A 256-byte aligned workspace of at least `need` bytes (torch's allocator aligns to 512)."""
+        ws = self.empty(max(-(-need // 8), 1), dtype=torch.float64)
+        assert ws.data_ptr() % 256 == 0
+        return ws
+
+    @_on_device
+    def heat_grid(self, init, border, mask, max_err, max_itr, block_steps=0):
+        """mvf_heat_grid: the whole loop of ``domain_heat_eqn_solver``.  init, border, mask: host (H, W) float64 (the field with
+        its boundary lines written, ``field_border``, ``field_mask``).  Returns (field * mask as a host (H, W) float64 array,
+        sweeps, last err, hit_max_itr).  block_steps: 0 (the library's choice) or the sweeps per launch, 1 .. HEAT_MAX_STEPS."""
+        init = np.ascontiguousarray(init, dtype=np.float64)
+        H, W = (int(v) for v in init.shape)
+        di, db, dm = (self.h2d(np.ascontiguousarray(a, dtype=np.float64)) for a in (init, border, mask))
+        out = self.empty(H, W, dtype=torch.float64)
+        need = int(self.lib.mvf_heat_grid_workspace_bytes(H, W))
+        ws = self._heat_ws(need)
+        sweeps, err, hit = C.c_int64(0), C.c_double(0.0), C.c_int(0)
+        _lib.check(self.lib.mvf_heat_grid(_ptr(di), _ptr(db), _ptr(dm), H, W, float(max_err), float(max_itr), int(block_steps), _ptr(out),
+                                          C.byref(sweeps), C.byref(err), C.byref(hit), _ptr(ws), ws.numel() * 8, self._stream()),
+                   "mvf_heat_grid")
+        return np.array(self.d2h(out)), int(sweeps.value), float(err.value), bool(hit.value)
+
+    @_on_device
+    def heat_graph(self, indptr, indices, data, fixed_value, max_err, max_itr):
+        """mvf_heat_graph: the whole loop of ``digitize_general`` on the CSC arrays of the adjacency (host: indptr (n + 1,) int64,
+        indices int32 in ascending row order per column, data float64) and fixed_value (n,) float64, the reference's
+        ``mask_field``.  Returns (field as a host (n,) float64 array, sweeps, last err, hit_max_itr)."""
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        fixed_value = np.ascontiguousarray(fixed_value, dtype=np.float64)
+        n = int(fixed_value.shape[0])
+        if indptr.shape != (n + 1,) or len(indices) != len(data) or (n and int(indptr[-1]) != len(data)):
+            raise ValueError("malformed CSC adjacency: indptr must have n + 1 entries that end at len(data) == len(indices)")
+        out = self.empty(n, dtype=torch.float64)
+        need = int(self.lib.mvf_heat_graph_workspace_bytes(n, len(data)))
+        ws = self._heat_ws(need)
+        sweeps, err, hit = C.c_int64(0), C.c_double(0.0), C.c_int(0)
+        hp = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        _lib.check(self.lib.mvf_heat_graph(hp(indptr), hp(indices), hp(data), hp(fixed_value), n, float(max_err), float(max_itr),
+                                           _ptr(out), C.byref(sweeps), C.byref(err), C.byref(hit), _ptr(ws), ws.numel() * 8,
+                                           self._stream()), "mvf_heat_graph")
+        return np.array(self.d2h(out)), int(sweeps.value), float(err.value), bool(hit.value)
+
     # ---- PCA across slices on the kernel-value cache (mvf_pca.hip + the cached Gram / apply kernels, unchanged) ----
     PCA_UPLOAD_BYTES = 256 << 20  # rows of a dense slice travel in chunks of at most this much (each chunk is a slice of its own)
 

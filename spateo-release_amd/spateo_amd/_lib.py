@@ -48,6 +48,7 @@ KDE_KERNELS = {"gaussian": 0, "exponential": 1, "tophat": 2, "epanechnikov": 3, 
 KDE_MAX_COLUMNS = 64  # MVF_KDE_MAX_COLUMNS: the columns (groups of sources) of one mvf_kde call
 SHAPE_MAX_NSUB = 128  # MVF_SHAPE_MAX_NSUB: the voxels per axis of mvf_shape_descriptors
 SHAPE_ORDERS = {"linear": 1, "quadratic": 2, "cubic": 3}
+HEAT_MAX_STEPS = 8  # MVF_HEAT_MAX_STEPS: the sweeps one launch of mvf_heat_grid's kernel runs in LDS at most
 EVAL_V, EVAL_JAC, EVAL_DIV, EVAL_CURL, EVAL_ACC, EVAL_CURV, EVAL_TORS, EVAL_JDET = 1, 2, 4, 8, 16, 32, 64, 128
 
 _p, _i64, _i, _d, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_size_t
@@ -180,6 +181,12 @@ SIGNATURES = {
     "mvf_kde": (_i, [_p, _i64, _p, _i64, _i, _i, _d, _p, _p, _i, _p, _p, _sz, _i, _p]),
     "mvf_shape_descriptors_workspace_bytes": (_sz, [_i64, _i]),
     "mvf_shape_descriptors": (_i, [_p, _i64, _p, _p, _i, _i, C.POINTER(C.c_double), _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "mvf_heat_grid_workspace_bytes": (_sz, [_i64, _i64]),
+    "mvf_heat_grid": (_i, [_p, _p, _p, _i64, _i64, _d, _d, _i, _p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                           _p, _sz, _p]),
+    "mvf_heat_graph_workspace_bytes": (_sz, [_i64, _i64]),
+    "mvf_heat_graph": (_i, [_p, _p, _p, _p, _i64, _d, _d, _p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int), _p,
+                            _sz, _p]),
 }
 
 _lib = None
