@@ -8,7 +8,7 @@ import torch
 
 import _assign_edge_cases as ec
 import _assign_label_case as lab
-from _kernel_scaffold import dev, guarded, intact, kernel_cache, nan_workspace, written
+from _kernel_scaffold import called, dev, guarded, intact, kernel_cache, nan_workspace, watch, written
 
 LABEL, PROBS = 5, {"gauss": 0, "cos": 1, "prob": 2}  # MVF_ASSIGN_LABEL and the probability types of include/mvf.h
 kernels = kernel_cache()  # one cache for the nine alignment modules
@@ -27,6 +27,7 @@ def prepare(k, layer, metric, side):
     Lp, ab = guarded(n * ld, k.tdtype), guarded(n)
     _lib.check(k.lib.mvf_assign_prepare(L.data_ptr(), n, g, ec.METRICS[metric], side, Lp.data_ptr(), ld, ab.data_ptr(), k.cdtype,
                                         k._stream()), "mvf_assign_prepare")
+    called()
     torch.cuda.synchronize()
     assert intact(Lp, n * ld) and intact(ab, n), "mvf_assign_prepare wrote behind a buffer"
     assert written(Lp, n * ld) and written(ab, n), "mvf_assign_prepare left an element unwritten"
@@ -74,6 +75,12 @@ def device_case(key, make, dtype):
     return _CASES[(key, dtype)]
 
 
+def watch_case(dc):
+    """Under a ``convention`` of tests/_kernel_scaffold.py: the operands of a DeviceCase or LabelCase, which the library takes
+    as ``const``, must leave the block unchanged."""
+    watch(dc.xa4, dc.xb4, dc.mm, *[t for layer in dc.layers for t in layer[:4] if torch.is_tensor(t)])
+
+
 def layer_struct(dc):
     from spateo_amd._kernels import layer_array
 
@@ -103,6 +110,7 @@ def assign(dc, dense=False, ws=None, ws_bytes=None):
         _lib.check(k.lib.mvf_assign_dense(*head, bufs["P"].data_ptr(), *tail), "mvf_assign_dense")
     else:
         _lib.check(k.lib.mvf_assign(*head, *tail), "mvf_assign")
+    called()
     torch.cuda.synchronize()
     for q, n in sizes.items():
         assert intact(bufs[q], n), f"{dc.name}: wrote behind {q}[{n}]"
@@ -127,6 +135,7 @@ def label_prepare(k, labels, classes):
     out = guarded(len(labels))
     _lib.check(k.lib.mvf_assign_label_prepare(lab32.data_ptr(), len(labels), int(classes), out.data_ptr(), k._stream()),
                "mvf_assign_label_prepare")
+    called()
     torch.cuda.synchronize()
     assert intact(out, len(labels))
     return out[: len(labels)]
@@ -195,6 +204,7 @@ class LabelCase:
             status = lib.mvf_assign_topk(*head, k, *outs, rows.data_ptr(), bufs["vals"].data_ptr(), *tail)
         else:
             status = lib.mvf_assign(*head, *outs, *tail)
+        called()
         torch.cuda.synchronize()
         if status != 0 or not check:
             return status, None

@@ -20,8 +20,9 @@ import torch
 
 import _align_loop_case as lc
 from _align_kernel_scaffold import kernels as _k
-from _kernel_scaffold import (DEV, DTYPES, GUARD, SENTINEL, dev as _dev, deviation_table, guarded as _guarded,
-                              intact as _intact, same_bits as _same_bits)
+from _kernel_scaffold import (DEV, DTYPES, GUARD, MODES, SENTINEL, called as _called, dev as _dev, deviation_table,
+                              guarded as _guarded, intact as _intact, same_bits as _same_bits, take as _take, under as _under,
+                              x4 as _sx4)
 
 pytestmark = pytest.mark.gpu
 
@@ -180,6 +181,53 @@ def test_alpha(n, variant):
     pos = ra > 0
     if pos.any():
         _note(f"alpha {variant}", "float64", float((np.abs(runs[0][0] - ra)[pos] / ra[pos]).max() / 1e-12))
+
+
+CONVENTION_COVERS = {"mvf_align_alpha": MODES, "mvf_align_moments": MODES, "mvf_align_transform": MODES}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n", [257, 1025])   # one workgroup and a partial one; more than one block of partial sums
+def test_calling_conventions(n, dtype, mode):
+    """mvf_align_alpha, mvf_align_moments and mvf_align_transform of one slice pair: the plain calls' bits on a side stream
+    behind poisoned inputs, at displaced pointers (VnA one row, every other array one element), and with the inputs unchanged."""
+    import ctypes
+
+    k, lib = _k(dtype), _k(dtype).lib
+    inp = make_inputs(n, "base")
+    nb, tdt = inp["nb"], torch.float32 if dtype == "float32" else torch.float64
+    need = int(lib.mvf_align_workspace_bytes(n, nb))
+    org = (ctypes.c_double * 3)(*inp["origin"])
+    Rt = (ctypes.c_double * 12)(*inp["R"].reshape(9), *inp["t"])
+
+    def call():
+        d = {q: _dev(inp[q]) for q in ("A", "B", "K", "KB", "Ks", "K2", "sd", "PXB", "kappa")}
+        V4, extra = _sx4(inp["V"], dtype), _dev(np.array([3.25]))
+        al, mm = _guarded(n), _guarded(n)
+        rc = lib.mvf_align_alpha(d["kappa"].data_ptr(), d["Ks"].data_ptr(), d["sd"].data_ptr(), n, inp["Sp_spatial"], inp["sigma2"],
+                                 al.data_ptr(), mm.data_ptr(), k._stream())
+        _called()
+        assert rc == 0, lib.mvf_last_error()
+        ws, out = _guarded(need // 8, fill=float("nan")), _guarded(64)
+        rc = lib.mvf_align_moments(d["A"].data_ptr(), V4.data_ptr(), d["K"].data_ptr(), d["Ks"].data_ptr(), d["K2"].data_ptr(),
+                                   d["sd"].data_ptr(), d["PXB"].data_ptr(), n, d["B"].data_ptr(), d["KB"].data_ptr(), nb, org,
+                                   extra.data_ptr(), out.data_ptr(), ws.data_ptr(), need, k.cdtype, k._stream())
+        _called()
+        assert rc == 0, lib.mvf_last_error()
+        sizes = {"RnA": 3 * n, "XAHat": 3 * n, "xa4": 4 * n, "PXB_term": 3 * n, "Y4": 4 * n, "Pw": n}
+        bufs = {q: _guarded(sizes[q], tdt if q in ("xa4", "Y4", "Pw") else torch.float64) for q in sizes}
+        rc = lib.mvf_align_transform(d["A"].data_ptr(), V4.data_ptr(), d["PXB"].data_ptr(), d["K"].data_ptr(), n, Rt, org,
+                                     *(bufs[q].data_ptr() for q in sizes), k.cdtype, k._stream())
+        _called()
+        assert rc == 0, lib.mvf_last_error()
+        torch.cuda.synchronize()
+        assert _intact(ws, need // 8)
+        return [_take(al, n), _take(mm, n), _take(out, 64)] + [_take(bufs[q], sizes[q]) for q in sizes]
+
+    plain, got = _under(mode, call)
+    assert np.isfinite(plain[2]).all() and plain[2][50] == 3.25
+    assert all(_same_bits(a, b) for a, b in zip(plain, got))
 
 
 def test_empty_and_refusals():

@@ -19,9 +19,10 @@ import torch
 import _align_start_case as sc
 import _assign_case as ac
 import _assign_edge_cases as ec
-from _align_kernel_scaffold import kernels as _k, prepare as _prepare
-from _kernel_scaffold import (DEV, DTYPES, GUARD, dev as _dev, guarded as _guarded, intact as _intact,
-                              nan_workspace as _nan_workspace, written as _written)
+from _align_kernel_scaffold import kernels as _k, label_prepare as _label_prepare, prepare as _prepare
+from _kernel_scaffold import (DEV, DTYPES, GUARD, MODES, called as _called, dev as _dev, guarded as _guarded, intact as _intact,
+                              nan_workspace as _nan_workspace, same_bits as _same_bits, under as _under, watch as _watch,
+                              written as _written)
 
 pytestmark = pytest.mark.gpu
 
@@ -118,6 +119,7 @@ def _stats(ly, fields, na, nb, k, ws=None, ws_bytes=None):
     _lib.check(kk.lib.mvf_assign_layer_stats(arr, na, nb, k, bufs["cmin"].data_ptr(), rows.data_ptr() if k else None,
                                              bufs["vals"].data_ptr() if k else None, bufs["sums"].data_ptr(), ws.data_ptr(),
                                              int(ws_bytes), kk.cdtype, kk._stream()), "mvf_assign_layer_stats")
+    _called()
     torch.cuda.synchronize()
     for q, n in sizes.items():
         assert _intact(bufs[q], n), f"{ly.name}: wrote behind {q}[{n}]"
@@ -134,6 +136,32 @@ def _same(a, b):
     for q in ("cmin", "sums", "vals", "rows"):
         x, y = np.ascontiguousarray(a[q]), np.ascontiguousarray(b[q])
         assert x.shape == y.shape and x.tobytes() == y.tobytes(), q
+
+
+# mvf_assign_layer_stats reads a layer that the device prepared when the case was built: no displaced pointers for it, and on
+# the side stream its outputs and workspace, not its operands, are in flight.
+CONVENTION_COVERS = {"mvf_assign_layer_stats": ("side_stream", "inputs"), "mvf_assign_label_prepare": MODES}
+
+
+@pytest.mark.parametrize("mode", ["side_stream", "inputs"])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("na,nb,g,metric", [(63, 65, 17, "kl"), (200, 4, 16, "cos"), (65, 129, (3, 4), "label")])
+def test_layer_stats_calling_conventions(na, nb, g, metric, dtype, mode):
+    ly = _layer((na, nb, g, metric, dtype, 10), na, nb, g, metric, dtype, 10)
+
+    def call():
+        _watch(*[t for t in ly.fields[:4] if torch.is_tensor(t)])
+        return _stats(ly, ly.fields, na, nb, 10)
+
+    plain, got = _under(mode, call)
+    _same(plain, got)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_label_prepare_calling_conventions(mode):
+    labels = np.random.default_rng(3).integers(0, 7, 1025)
+    plain, got = _under(mode, lambda: _label_prepare(_k("float64"), labels, 7).cpu().numpy())
+    assert np.array_equal(plain, labels.astype(np.float64)) and _same_bits(plain, got)
 
 
 def _check(ly, d, got, k, what):

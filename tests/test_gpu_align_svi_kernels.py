@@ -17,7 +17,8 @@ import torch
 
 import _align_svi_case as sc
 from _align_kernel_scaffold import kernels as _k
-from _kernel_scaffold import DEV, DTYPES, dev as _dev, guarded as _guarded, intact as _intact, same_bits as _same_bits
+from _kernel_scaffold import (DEV, DTYPES, MODES, called as _called, dev as _dev, guarded as _guarded, intact as _intact,
+                              same_bits as _same_bits, take as _take, under as _under)
 
 pytestmark = pytest.mark.gpu
 
@@ -193,6 +194,78 @@ def test_transform_svi(n, dtype):
                 assert _same_bits(got, np.ascontiguousarray(want)) and _same_bits(got, again), (step, origin)
             if step < 1.0 and start is running:                   # rows without a partner keep the earlier batches' share
                 assert np.array_equal(runs[0][0][K == 0], ((1.0 - step) * running)[K == 0] + 0.0)
+
+
+CONVENTION_COVERS = {"mvf_align_gather": MODES, "mvf_align_alpha_svi": MODES, "mvf_align_transform_svi": MODES}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_gather_calling_conventions(dtype, mode):
+    """A batch of 65 of 202 cells that wraps around the end, two layers: the plain call's bits on a side stream behind poisoned
+    inputs, at displaced pointers (the rows of xb4 and of the layers 16 bytes, as the entry point asks; coordsB, b and the
+    permutation one element), and with the inputs unchanged."""
+    k, lib = _k(dtype), _k(dtype).lib
+    tdt, npdt, item = (torch.float32, np.float32, 4) if dtype == "float32" else (torch.float64, np.float64, 8)
+    nb, bs, lds, start = 202, 65, (16, 48), 170
+    rng = np.random.default_rng(202)
+    host = dict(xb4=rng.standard_normal((nb, 4)).astype(npdt), B=rng.standard_normal((nb, 3)),
+                Yp=[rng.standard_normal((nb, ld)).astype(npdt) for ld in lds], b=[rng.standard_normal(nb) for _ in lds],
+                perm=rng.permutation(nb).astype(np.int32))
+
+    def call():
+        xb4, B, perm = _dev(host["xb4"], None, unit=16 // item), _dev(host["B"]), _dev(host["perm"], None)
+        Yp, b = [_dev(y, None, unit=16 // item) for y in host["Yp"]], [_dev(c) for c in host["b"]]
+        outs = dict(xb4=_guarded(4 * bs, tdt, unit=16 // item), B=_guarded(3 * bs), Yp=[_guarded(bs * ld, tdt, unit=16 // item) for ld in lds],
+                    b=[_guarded(bs) for _ in lds])
+        rc = _gather(lib, k, perm, nb, start, bs, xb4, B, Yp, b, lds, outs)
+        _called()
+        assert rc == 0, lib.mvf_last_error()
+        torch.cuda.synchronize()
+        return [_take(outs["xb4"], 4 * bs), _take(outs["B"], 3 * bs)] + [_take(o, bs * ld) for o, ld in zip(outs["Yp"], lds)] + \
+               [_take(o, bs) for o in outs["b"]]
+
+    plain, got = _under(mode, call)
+    idx = host["perm"].astype(np.int64)[(start + np.arange(bs)) % nb]
+    assert _same_bits(plain[0].reshape(bs, 4), host["xb4"][idx]) and _same_bits(plain[3].reshape(bs, 48), host["Yp"][1][idx])
+    assert all(_same_bits(a, b) for a, b in zip(plain, got))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_alpha_and_transform_svi_calling_conventions(dtype, mode):
+    """mvf_align_alpha_svi and mvf_align_transform_svi at a step below 1 on running values of 257 cells; ``alpha`` and the
+    running term are read and overwritten (not ``const`` in include/mvf.h): they are left out of the input check."""
+    k, lib = _k(dtype), _k(dtype).lib
+    tdt = torch.float32 if dtype == "float32" else torch.float64
+    n = 257
+    inp = _alpha_inputs(n)
+    rng = np.random.default_rng(n + 1)
+    RnA = rng.standard_normal((n, 3)) + 3.0
+    K = rng.uniform(0.1, 1.5, n) * (rng.random(n) < 0.8)
+    PXB, running = K[:, None] * (RnA + 0.05 * rng.standard_normal((n, 3))), 0.1 * rng.standard_normal((n, 3))
+    org = (ctypes.c_double * 3)(0.5, -0.25, 3.0)
+
+    def call():
+        d = {q: _dev(inp[q]) for q in ("kappa", "Ks", "sd")}
+        al, mm = _guarded(n), _guarded(n)
+        al[:n] = _dev(inp["old"])
+        rc = lib.mvf_align_alpha_svi(d["kappa"].data_ptr(), d["Ks"].data_ptr(), d["sd"].data_ptr(), n, inp["Sp_spatial"], inp["sigma2"],
+                                     0.37, al.data_ptr(), mm.data_ptr(), k._stream())
+        _called()
+        assert rc == 0, lib.mvf_last_error()
+        t = {"RnA": _dev(RnA), "K": _dev(K), "PXB": _dev(PXB)}
+        term, Y4, Pw = _guarded(3 * n), _guarded(4 * n, tdt), _guarded(n, tdt)
+        term[: 3 * n] = _dev(running.reshape(-1))
+        rc = lib.mvf_align_transform_svi(t["RnA"].data_ptr(), t["PXB"].data_ptr(), t["K"].data_ptr(), n, org, 0.37, term.data_ptr(),
+                                         Y4.data_ptr(), Pw.data_ptr(), k.cdtype, k._stream())
+        _called()
+        assert rc == 0, lib.mvf_last_error()
+        torch.cuda.synchronize()
+        return [_take(al, n), _take(mm, n), _take(term, 3 * n), _take(Y4, 4 * n), _take(Pw, n)]
+
+    plain, got = _under(mode, call)
+    assert all(_same_bits(a, b) for a, b in zip(plain, got))
 
 
 def test_empty_and_refusals():

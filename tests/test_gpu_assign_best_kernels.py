@@ -19,9 +19,10 @@ import torch
 import _assign_best_case as bc
 import _assign_case as ac
 import _assign_edge_cases as ec
-from _align_kernel_scaffold import device_case as _case, kernels as _k, LabelCase as _LabelCase, layer_struct as _layer_array
-from _kernel_scaffold import (DEV, DTYPES, GUARD, SENTINEL, guarded as _guarded, intact as _intact,
-                              nan_workspace as _nan_workspace, written as _written)
+from _align_kernel_scaffold import (device_case as _case, kernels as _k, LabelCase as _LabelCase, layer_struct as _layer_array,
+                                    watch_case as _watch_case)
+from _kernel_scaffold import (DEV, DTYPES, GUARD, SENTINEL, called as _called, guarded as _guarded, intact as _intact,
+                              nan_workspace as _nan_workspace, under as _under, written as _written)
 
 pytestmark = pytest.mark.gpu
 
@@ -59,6 +60,7 @@ def _best(dc, rows=True, cols=True, ws=None, ws_bytes=None, struct=None, nlayers
                                       dc.mm.data_ptr(), float(c["sigma2"]), float(c["sigma2_variance"]), float(dc.outlier),
                                       ptr("row_idx"), ptr("row_val"), ptr("col_idx"), ptr("col_val"), ws.data_ptr(), int(ws_bytes),
                                       kk.cdtype, kk._stream()), "mvf_assign_best")
+    _called()
     torch.cuda.synchronize()
     out = {}
     for on, name, n, key, vkey in ((rows, "row", na, "rows", "row_values"), (cols, "col", nb, "cols", "col_values")):
@@ -79,6 +81,26 @@ def _same(a, b):
     for q in a:
         x, y = np.ascontiguousarray(a[q]), np.ascontiguousarray(b[q])
         assert x.shape == y.shape and x.tobytes() == y.tobytes(), q
+
+
+CONVENTION_COVERS = {"mvf_assign_best": ("side_stream", "inputs")}
+
+
+@pytest.mark.parametrize("mode", ["side_stream", "inputs"])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("na,nb", [(65, 63), (50, 4417)])   # one tile pair; the split plan
+def test_calling_conventions(na, nb, dtype, mode):
+    """The plain call's bits with the call on a side stream - the case's operands are made when the case is built, so the
+    outputs and the workspace, not the inputs, are in flight there: a launch on another stream is overwritten by their fill -,
+    and with every operand unchanged by the call."""
+    dc = _case(("best", na, nb), lambda: _shape_case(na, nb), dtype)
+
+    def call():
+        _watch_case(dc)
+        return _best(dc)
+
+    plain, got = _under(mode, call)
+    _same(plain, got)
 
 
 def _check(dc, got, what):

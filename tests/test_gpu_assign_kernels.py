@@ -25,9 +25,9 @@ import torch
 
 import _assign_case as ac
 import _assign_edge_cases as ec
-from _align_kernel_scaffold import assign as _assign, device_case, kernels as _k, prepare as _prepare
+from _align_kernel_scaffold import assign as _assign, device_case, kernels as _k, prepare as _prepare, watch_case as _watch_case
 from _kernel_scaffold import (DEV, DTYPES, deviation_table, guarded as _guarded, nan_workspace as _nan_workspace,
-                              same_bits as _same_bits)
+                              same_bits as _same_bits, under as _under)
 
 pytestmark = pytest.mark.gpu
 
@@ -36,6 +36,27 @@ _note, _deviation_table = deviation_table("| case family | dtype | largest devia
 
 def _device_case(name, dtype):
     return device_case(name, lambda: ec.case(name), dtype)
+
+
+CONVENTION_COVERS = {"mvf_assign": ("side_stream", "inputs"), "mvf_assign_dense": ("side_stream", "inputs")}
+
+
+@pytest.mark.parametrize("mode", ["side_stream", "inputs"])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dense", [False, True], ids=["mvf_assign", "mvf_assign_dense"])
+@pytest.mark.parametrize("case", ["cells-65x65", "layers-2", "split-50x4417"])   # one tile pair; two layers; the split plan
+def test_calling_conventions(case, dense, dtype, mode):
+    """The plain call's bits with the call on a side stream - the case's operands are made when the case is built, so the
+    outputs and the workspace, not the inputs, are in flight there: a launch on another stream is overwritten by their fill -,
+    and with every operand unchanged by the call."""
+    dc = _device_case(case, dtype)
+
+    def call():
+        _watch_case(dc)
+        return _assign(dc, dense=dense)
+
+    plain, got = _under(mode, call)
+    assert sorted(plain) == sorted(got) and all(_same_bits(plain[q], got[q]) for q in plain)
 
 
 # ------------------------------------------------------------------------------------------------------ A: prepare

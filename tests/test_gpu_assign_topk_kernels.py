@@ -18,9 +18,9 @@ import torch
 import _assign_case as ac
 import _assign_edge_cases as ec
 import _assign_topk_case as tk
-from _align_kernel_scaffold import assign as _assign, device_case as _case, layer_struct as _layer_array
-from _kernel_scaffold import (DEV, DTYPES, GUARD, guarded as _guarded, intact as _intact, nan_workspace as _nan_workspace,
-                              same_bits as _same_bits, written as _written)
+from _align_kernel_scaffold import assign as _assign, device_case as _case, layer_struct as _layer_array, watch_case as _watch_case
+from _kernel_scaffold import (DEV, DTYPES, GUARD, called as _called, guarded as _guarded, intact as _intact,
+                              nan_workspace as _nan_workspace, same_bits as _same_bits, under as _under, written as _written)
 
 pytestmark = pytest.mark.gpu
 
@@ -94,6 +94,7 @@ def _topk(dc, k, ws=None, ws_bytes=None):
                                       *(bufs[q].data_ptr() for q in ("K_NA", "K_NB", "K_NA_spatial", "K_NA_sigma2", "PXB", "scalar")),
                                       rows.data_ptr(), bufs["vals"].data_ptr(), ws.data_ptr(), int(ws_bytes), kk.cdtype,
                                       kk._stream()), "mvf_assign_topk")
+    _called()
     torch.cuda.synchronize()
     for q, n in sizes.items():
         assert _intact(bufs[q], n), f"{dc.name}: wrote behind {q}[{n}]"
@@ -113,6 +114,26 @@ def _same(a, b):
     for q in OUT:
         x, y = np.ascontiguousarray(a[q]), np.ascontiguousarray(b[q])
         assert x.shape == y.shape and x.tobytes() == y.tobytes(), q
+
+
+CONVENTION_COVERS = {"mvf_assign_topk": ("side_stream", "inputs")}
+
+
+@pytest.mark.parametrize("mode", ["side_stream", "inputs"])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("na,nb", [(65, 63), (50, 4417)])   # one tile pair; the split plan
+def test_calling_conventions(na, nb, dtype, mode):
+    """The plain call's bits with the call on a side stream - the case's operands are made when the case is built, so the
+    outputs and the workspace, not the inputs, are in flight there: a launch on another stream is overwritten by their fill -,
+    and with every operand unchanged by the call."""
+    dc = _case((na, nb), lambda: _shape_case(na, nb), dtype)
+
+    def call():
+        _watch_case(dc)
+        return _topk(dc, 8)
+
+    plain, got = _under(mode, call)
+    _same(plain, got)
 
 
 def _check(dc, got, k):

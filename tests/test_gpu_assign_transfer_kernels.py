@@ -20,9 +20,9 @@ import _assign_case as ac
 import _assign_edge_cases as ec
 import _assign_transfer_case as tc
 from _align_kernel_scaffold import (assign as _assign, device_case as _case, LabelCase as _LabelCase,
-                                    layer_struct as _layer_array)
-from _kernel_scaffold import (DEV, DTYPES, SENTINEL, dev as _dev, guarded as _guarded, intact as _intact,
-                              nan_workspace as _nan_workspace, written as _written)
+                                    layer_struct as _layer_array, watch_case as _watch_case)
+from _kernel_scaffold import (DEV, DTYPES, SENTINEL, called as _called, dev as _dev, guarded as _guarded, intact as _intact,
+                              nan_workspace as _nan_workspace, under as _under, written as _written)
 
 pytestmark = pytest.mark.gpu
 
@@ -89,6 +89,7 @@ def _apply(dc, FB=None, FA=None, ldfb=None, ldfa=None, k_na=True, k_nb=True, ws=
                                        ptr(bufs.get("to_A")), ptr(dFA), ca, ldfa, ptr(bufs.get("to_B")), ptr(bufs.get("K_NA")),
                                        ptr(bufs.get("K_NB")), ws.data_ptr(), int(ws_bytes), kk.cdtype, kk._stream()),
                "mvf_assign_apply")
+    _called()
     torch.cuda.synchronize()
     for q, n in sizes.items():
         assert _intact(bufs[q], n), f"wrote behind {q}[{n}]"
@@ -109,6 +110,26 @@ def _same(a, b):
     for q in a:
         x, y = np.ascontiguousarray(a[q]), np.ascontiguousarray(b[q])
         assert x.shape == y.shape and x.tobytes() == y.tobytes(), q
+
+
+CONVENTION_COVERS = {"mvf_assign_apply": ("side_stream", "inputs")}
+
+
+@pytest.mark.parametrize("mode", ["side_stream", "inputs"])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("na,nb", [(65, 63), (50, 4417)])   # one tile pair; the split plan
+def test_calling_conventions(na, nb, dtype, mode):
+    """The plain call's bits with the call on a side stream - the case's operands are made when the case is built, so the
+    outputs and the workspace, not the inputs, are in flight there: a launch on another stream is overwritten by their fill -,
+    and with every operand unchanged by the call."""
+    dc = _case(("transfer", na, nb), lambda: _shape_case(na, nb), dtype)
+
+    def call():
+        _watch_case(dc)
+        return _apply(dc, _features(nb, 17, 1), _features(na, 5, 2))
+
+    plain, got = _under(mode, call)
+    _same(plain, got)
 
 
 def _check(got, P, FB, FA, what):

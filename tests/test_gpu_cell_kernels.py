@@ -18,8 +18,9 @@ import torch
 
 import _cell_cases as cc
 from _cpu_kernels import CpuKernels
-from _kernel_scaffold import (DEV, DTYPES, GUARD, bits_equal as _bits_equal, dev as _dev, deviation_table,
-                              guarded as _guarded, intact as _intact, kernel_cache)
+from _kernel_scaffold import (DEV, DTYPES, GUARD, MODES, bits_equal as _bits_equal, called as _called, dev as _dev,
+                              deviation_table, guarded as _guarded, intact as _intact, kernel_cache, same_bits as _same_bits,
+                              take as _take, under as _under, x4 as _sx4)
 
 pytestmark = pytest.mark.gpu
 
@@ -132,8 +133,130 @@ def _eval_raw(k, x4, c4, Cd, case, flags):
 
     _lib.check(k.lib.mvf_eval_affine(x4.data_ptr(), n, c4.data_ptr(), m, float(case["beta"]), Cd.data_ptr(),
                                      k._affine_buf(case["affine"]), int(flags), *ptr, k.cdtype, k._stream()), "mvf_eval_affine")
+    _called()
     torch.cuda.synchronize()
     return bufs
+
+
+# ------------------------------------------------------------------------------------------------------ calling conventions
+CONVENTION_COVERS = {"mvf_eval_affine": MODES, "mvf_eval": MODES, "mvf_integrate": MODES, "mvf_apply": MODES, "mvf_estep_min": MODES,
+                     "mvf_estep_p": MODES, "mvf_estep": MODES, "mvf_read_back": MODES}
+
+
+def _scaffold_inputs(dtype, case):
+    """The inputs of a case from the scaffold's own allocations (not ``HipKernels.to_x4``), so that every mode reaches them."""
+    return _sx4(case["X"], dtype), _sx4(case["ctrl"], dtype), _dev(np.asarray(case["C"], dtype=np.float64).reshape(-1, 3))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("family,n,m", [("positive", 257, 259), ("affine", 300, 65)])
+def test_eval_calling_conventions(dtype, family, n, m, mode):
+    """Every output of mvf_eval_affine: the plain call's bits on a side stream behind poisoned inputs, at displaced pointers
+    (coordinates one row, coefficients and outputs one element), and with the inputs unchanged."""
+    case = cc.eval_case(n, m, family)
+    k = _k(dtype)
+
+    def call():
+        bufs = _eval_raw(k, *_scaffold_inputs(dtype, case), case, cc.EVAL_ALL)
+        return [_take(b, b.numel() - GUARD) for _, b in sorted(bufs.items())]
+
+    plain, got = _under(mode, call)
+    assert len(plain) == len(cc.EVAL_FLAGS) and all(_same_bits(a, b) for a, b in zip(plain, got))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_eval_without_affine_calling_conventions(dtype, mode):
+    """mvf_eval, the entry point without the affine epilogue, all outputs."""
+    from spateo_amd import _lib
+
+    n, m = 257, 259
+    case, k = cc.eval_case(n, m, "positive"), _k(dtype)
+    order = (cc.EVAL_V, cc.EVAL_JAC, cc.EVAL_DIV, cc.EVAL_CURL, cc.EVAL_ACC, cc.EVAL_CURV, cc.EVAL_TORS, cc.EVAL_JDET)
+
+    def call():
+        x4, c4, Cd = _scaffold_inputs(dtype, case)
+        bufs = [_guarded(int(np.prod(cc.EVAL_SHAPES[f](n)))) for f in order]
+        _lib.check(k.lib.mvf_eval(x4.data_ptr(), n, c4.data_ptr(), m, float(case["beta"]), Cd.data_ptr(), int(cc.EVAL_ALL),
+                                  *[b.data_ptr() for b in bufs], k.cdtype, k._stream()), "mvf_eval")
+        _called()
+        torch.cuda.synchronize()
+        return [_take(b, b.numel() - GUARD) for b in bufs]
+
+    plain, got = _under(mode, call)
+    assert all(_same_bits(a, b) for a, b in zip(plain, got))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_apply_and_estep_calling_conventions(dtype, mode):
+    """One E-step as a fit chains it, every buffer the scaffold's own: mvf_apply (V, r and sum P r), mvf_estep_min and
+    mvf_estep_p with the fill taken on the device, mvf_estep in one call, and the statistics through mvf_read_back - which
+    blocks (include/mvf.h): everything in front of it has returned while the inputs were in flight."""
+    from spateo_amd import _lib
+
+    n, m = 1000, 259
+    case, k = cc.eval_case(n, m, "positive"), _k(dtype)
+    rng = np.random.default_rng(7)
+    Y, Pw = np.asarray(case["X"]) * 0.01 + rng.standard_normal((n, 3)), rng.uniform(0.0, 1.0, n)
+    red = int(k.lib.mvf_reduce_scratch_doubles(n))
+    npdt = np.float32 if dtype == "float32" else np.float64
+
+    def call():
+        x4, c4, Cd = _scaffold_inputs(dtype, case)
+        y4, P = _sx4(Y, dtype), _dev(Pw, k.tdtype)
+        V4, r, stats, scratch = _guarded(4 * n, k.tdtype), _guarded(n, k.tdtype), _guarded(1, fill=0.0), _guarded(red)
+        _lib.check(k.lib.mvf_apply(x4.data_ptr(), n, c4.data_ptr(), m, float(case["beta"]), Cd.data_ptr(), V4.data_ptr(), y4.data_ptr(),
+                                   P.data_ptr(), r.data_ptr(), stats.data_ptr(), scratch.data_ptr(), k.cdtype, k._stream()), "mvf_apply")
+        _called()
+        mins, P1, st1 = _guarded(4098), _guarded(n, k.tdtype), _guarded(5, fill=0.0)
+        _lib.check(k.lib.mvf_estep_min(r.data_ptr(), n, 0.7, mins.data_ptr(), k.cdtype, k._stream()), "mvf_estep_min")
+        _called()
+        _lib.check(k.lib.mvf_estep_p(r.data_ptr(), n, 0.7, 0.9, 1e-3, 3, 1e-5, 0.75, 0.0, mins.data_ptr(), P1.data_ptr(), st1.data_ptr(),
+                                     scratch.data_ptr(), k.cdtype, k._stream()), "mvf_estep_p")
+        _called()
+        mins2, P2, st2 = _guarded(4098), _guarded(n, k.tdtype), _guarded(5)
+        _lib.check(k.lib.mvf_estep(r.data_ptr(), n, 0.7, 0.9, 1e-3, 3, 1e-5, 0.75, mins2.data_ptr(), P2.data_ptr(), st2.data_ptr(),
+                                   scratch.data_ptr(), k.cdtype, k._stream()), "mvf_estep")
+        _called()
+        back = np.full(5, -1.0)
+        _lib.check(k.lib.mvf_read_back(back.ctypes.data, st2.data_ptr(), 40, k._stream()), "mvf_read_back")
+        _called(synchronising=True)
+        torch.cuda.synchronize()
+        assert _intact(scratch, red) and _intact(mins, 4098) and _intact(mins2, 4098)
+        out = [_take(V4, 4 * n), _take(r, n), _take(stats, 1), mins[:2].cpu().numpy(), _take(P1, n), _take(st1, 5), _take(P2, n),
+               _take(st2, 5), back]
+        assert out[0].dtype == npdt and _same_bits(out[4], out[6]) and _same_bits(out[5], out[7]) and _same_bits(out[7], back)
+        return out
+
+    plain, got = _under(mode, call)
+    assert np.isfinite(plain[2]).all() and plain[2][0] > 0 and plain[5][2] > 0
+    assert all(_same_bits(a, b) for a, b in zip(plain, got))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("affine", [False, True])
+def test_rk4_calling_conventions(dtype, affine, mode):
+    from spateo_amd import _lib
+
+    n, m = cc.RK4_SHAPES[0]
+    case = cc.rk4_case(n, m, affine)
+    k = _k(dtype)
+
+    def call():
+        x4, c4, Cd = _scaffold_inputs(dtype, case)
+        buf = _guarded(n * cc.RK4_NOUT * 3)
+        _lib.check(k.lib.mvf_integrate(x4.data_ptr(), n, c4.data_ptr(), m, float(case["beta"]), Cd.data_ptr(),
+                                       k._affine_buf(case["affine"]), float(cc.RK4_DT), int(cc.RK4_SUBSTEPS), int(cc.RK4_NOUT),
+                                       buf.data_ptr(), k.cdtype, k._stream()), "mvf_integrate")
+        _called()
+        torch.cuda.synchronize()
+        return _take(buf, n * cc.RK4_NOUT * 3)
+
+    plain, got = _under(mode, call)
+    assert _same_bits(plain, got)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

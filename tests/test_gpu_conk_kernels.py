@@ -12,7 +12,8 @@ import pytest
 import torch
 
 import _prep_cases as pc
-from _kernel_scaffold import DTYPES, Out, deviation_table, dev as _dev, option, same_bits as _same_bits, stream as _stream
+from _kernel_scaffold import (DTYPES, MODES, Out, called as _called, deviation_table, dev as _dev, option, same_bits as _same_bits,
+                              stream as _stream, under as _under)
 
 pytestmark = pytest.mark.gpu
 
@@ -45,6 +46,7 @@ def _conk_raw(lib, xd, yd, n, m, d, beta, dtype, code=None, x=True, y=True, out=
     K = Out(max(n * m, 1), dtype=_T[dtype])
     rc = lib.mvf_con_k(xd.data_ptr() if x else None, n, yd.data_ptr() if y else None, m, d, ctypes.c_double(beta),
                        K.ptr if out else None, _code(dtype) if code is None else code, _stream())
+    _called()
     torch.cuda.synchronize()
     assert K.guards_intact(), "wrote outside K"
     return rc, K
@@ -141,9 +143,48 @@ def _conk_d_raw(lib, xd, yd, n, m, d, beta, dtype, D=True):
     K, Dd = Out(max(n * m, 1), dtype=_T[dtype]), Out(max(n * d * m, 1), dtype=_T[dtype])
     rc = lib.mvf_con_k_d(xd.data_ptr(), n, yd.data_ptr(), m, d, ctypes.c_double(beta), K.ptr, Dd.ptr if D else None, _code(dtype),
                          _stream())
+    _called()
     torch.cuda.synchronize()
     assert K.guards_intact() and Dd.guards_intact(), "wrote outside K or D"
     return rc, K, Dd
+
+
+# ================================================================================================== calling conventions
+CONVENTION_COVERS = {"mvf_con_k": MODES, "mvf_con_k_d": MODES}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("form", (1, 2, 3), ids=("rows", "flat", "2d"))
+def test_con_k_calling_conventions(lib, form, dtype, mode):
+    """The plain call's bits on a side stream behind poisoned inputs, at displaced pointers (x, y and K one element off: the
+    vector stores of every form must not rely on the allocation's alignment), and with the inputs unchanged."""
+    n, m, d = 37, 68, 3
+    x, y = pc.conk_points(n, m, d, dtype)
+
+    def call():
+        rc, K = _conk_raw(lib, _dev(x, None), _dev(y, None), n, m, d, pc.CONK_BETA, dtype)
+        assert rc == 0, _err(lib)
+        return K.host()
+
+    with option("conk_form", form):
+        plain, got = _under(mode, call)
+    assert _same_bits(plain, got)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_con_k_d_calling_conventions(lib, dtype, mode):
+    n, m, d = 37, 68, 3
+    x, y = pc.conk_points(n, m, d, dtype, seed=5)
+
+    def call():
+        rc, K, D = _conk_d_raw(lib, _dev(x, None), _dev(y, None), n, m, d, pc.CONK_BETA, dtype)
+        assert rc == 0, _err(lib)
+        return np.concatenate([K.host(), D.host()])
+
+    plain, got = _under(mode, call)
+    assert _same_bits(plain, got)
 
 
 @pytest.mark.parametrize("d", range(1, 9))

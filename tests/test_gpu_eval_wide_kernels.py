@@ -13,7 +13,8 @@ import torch
 
 import _eval_wide_cases as wc
 from _cell_cases import EVAL_JAC, EVAL_V, TOL, relmax
-from _kernel_scaffold import DEV, DTYPES, SENTINEL as _SENTINEL, guarded as _buf, intact as _intact, kernel_cache
+from _kernel_scaffold import (DEV, DTYPES, MODES, SENTINEL as _SENTINEL, called as _called, dev as _dev, guarded as _buf,
+                              intact as _intact, kernel_cache, same_bits as _same_bits, under as _under, x4 as _sx4)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,11 +38,18 @@ def _run(k, x4, c4, d, beta, C_ptr, ldc, dy, flags, v_ptr, ldv, jac_ptr):
         rc = k.lib.mvf_eval_wide(x4.data_ptr() or None, x4.shape[0], c4.data_ptr() or None, c4.shape[0], d, float(beta), C_ptr,
                                  ldc, dy, flags, v_ptr, ldv, jac_ptr, k.cdtype, k._stream())
     _lib.check(rc, "mvf_eval_wide")
+    _called()
 
 
-def _eval(dtype, n, m, dy, d, flags=EVAL_V | EVAL_JAC):
+def _scaffold_inputs(dtype, n, m, dy, d):
+    """``_inputs`` from the scaffold's own allocations (not ``HipKernels.to_x4``), so that every calling mode reaches them."""
+    c = wc.wide_case(n, m, dy, d)
+    return _k(dtype), c, _sx4(c["X"], dtype), _sx4(c["ctrl"], dtype), _dev(np.array(c["C"]))
+
+
+def _eval(dtype, n, m, dy, d, flags=EVAL_V | EVAL_JAC, inputs=None):
     """One plain call (contiguous C and v): {flag: host array}, guards checked."""
-    k, c, x4, c4, Cd = _inputs(dtype, n, m, dy, d)
+    k, c, x4, c4, Cd = (inputs or _inputs)(dtype, n, m, dy, d)
     vb, jb = _buf(n * dy), _buf(dy * d * n)
     _run(k, x4, c4, d, c["beta"], Cd.data_ptr() or None, dy, dy, flags, vb.data_ptr() if flags & EVAL_V else None, dy,
          jb.data_ptr() if flags & EVAL_JAC else None)
@@ -151,3 +159,16 @@ def test_empty_problems(dtype):
     v, j = vb.cpu().numpy(), jb.cpu().numpy()
     assert np.all(v[: n * dy] == 0.0) and np.all(j[: dy * d * n] == 0.0)
     assert np.all(v[n * dy:] == SENTINEL) and np.all(j[dy * d * n:] == SENTINEL)
+
+
+CONVENTION_COVERS = {"mvf_eval_wide": MODES}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dy,d", [(65, 3), (17, 2), (3, 1)])   # two column panels at d = 3; one tile and a partial one; one partial tile
+def test_calling_conventions(dtype, dy, d, mode):
+    """Values and Jacobian: the plain call's bits on a side stream behind poisoned inputs, at displaced pointers, and with the
+    inputs unchanged."""
+    plain, got = _under(mode, lambda: _eval(dtype, 65, 259, dy, d, inputs=_scaffold_inputs))
+    assert _same_bits(plain[EVAL_V], got[EVAL_V]) and _same_bits(plain[EVAL_JAC], got[EVAL_JAC])

@@ -17,9 +17,10 @@ import pytest
 import torch
 
 import _gram_cases as gc
-from _kernel_scaffold import (DEV, DTYPES, SENTINEL as _SENTINEL, WS_FILL, bits_equal as _bits_equal, deviation_table,
-                              guarded as _guarded, intact as _intact, kernel_cache, option as _option, Out as _Out,
-                              Ws as _Ws)
+from _kernel_scaffold import (DEV, DTYPES, MODES, SENTINEL as _SENTINEL, WS_FILL, bits_equal as _bits_equal, called as _called,
+                              dev as _dev, deviation_table, guarded as _guarded, intact as _intact, kernel_cache,
+                              option as _option, Out as _Out, same_bits as _same_bits, settle as _settle, take as _take,
+                              under as _under, Ws as _Ws, x4 as _sx4)
 
 pytestmark = pytest.mark.gpu
 
@@ -268,19 +269,71 @@ def test_the_reductions_read_no_word_the_tile_kernels_skip(dtype, m):
 
 
 # ------------------------------------------------------------------------------------------------------ stages, raw ABI
-def _raw(k, stages, x4, P, y4, c4, beta, G, R, ws, ws_bytes, ublk=None, n=None, m=None, cached=None):
+def _raw(k, stages, x4, P, y4, c4, beta, G, R, ws, ws_bytes, ublk=None, n=None, m=None, cached=None, sync=True):
     """mvf_gram_stages, or mvf_gram_cached when a cache is given, through the raw ABI (pointers as integers or None)."""
     n = x4.shape[0] if n is None else n
     m = c4.shape[0] if m is None else m
     args = (x4.data_ptr(), P.data_ptr(), y4.data_ptr() if y4 is not None else None, n, c4.data_ptr(), m, float(beta), G, R, ws,
             ws_bytes, k.cdtype, k._stream())
-    torch.cuda.synchronize()
+    _settle()
     if cached if cached is not None else ublk is not None:
         rc = k.lib.mvf_gram_cached(stages, ublk, *args)
     else:
         rc = k.lib.mvf_gram_stages(stages, *args)
-    torch.cuda.synchronize()
+    _called()
+    if sync:
+        torch.cuda.synchronize()
     return rc
+
+
+# ------------------------------------------------------------------------------------------------------ calling conventions
+CONVENTION_COVERS = {"mvf_gram": MODES, "mvf_gram_stages": MODES, "mvf_ublk_build": MODES, "mvf_gram_cached": MODES}
+# float32: the sharing kernel as the dispatcher launches it, with persistent workgroups, and the kernel without sharing
+GRAM_VARIANTS = [("float32", 0), ("float32", 3), ("float32", 1), ("float64", 0)]
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype,reg_cols", GRAM_VARIANTS)
+def test_calling_conventions(dtype, reg_cols, mode):
+    """mvf_ublk_build, then G and R from mvf_gram, mvf_gram_stages and mvf_gram_cached on inputs, outputs, a cache and
+    workspaces of the scaffold's own: the plain calls' bits on a side stream behind poisoned inputs, at displaced pointers
+    (coordinates one row, P one element, the cache 16 bytes - what include/mvf.h asks of it at mvf_ublk_pack -, workspaces 256
+    bytes), and with the inputs unchanged."""
+    n, m = 300, 129
+    c, k = gc.case("raw", n, m), _k(dtype)
+    inp = gc.inputs(n, m, c["p_kind"])
+    centre = np.asarray(inp["center"], dtype=np.float64)[None, :3]
+    item = 4 if dtype == "float32" else 8
+    need, nb = int(k.lib.mvf_gram_workspace_bytes(n, m, k.cdtype)), int(k.lib.mvf_ublk_bytes(n, m, k.cdtype))
+
+    def call():
+        x4, c4, y4 = _sx4(inp["X"] - centre, dtype), _sx4(inp["ctrl"] - centre, dtype), _sx4(inp["Y"], dtype)
+        P = _dev(inp["P"], k.tdtype)
+        ublk = _guarded(nb // item, k.tdtype, unit=16 // item)
+        rc = k.lib.mvf_ublk_build(x4.data_ptr(), n, c4.data_ptr(), m, float(c["beta"]), ublk.data_ptr(), nb, k.cdtype, k._stream())
+        _called()
+        assert rc == 0, k.lib.mvf_last_error()
+        bufs = [(_Out(m, m), _Out(m, 3), _Ws(need)) for _ in range(3)]
+        for entry, (G, R, ws) in zip(("gram", "stages", "cached"), bufs):   # (no synchronisation between the four calls)
+            if entry == "gram":
+                rc = k.lib.mvf_gram(x4.data_ptr(), P.data_ptr(), y4.data_ptr(), n, c4.data_ptr(), m, float(c["beta"]), G.ptr, R.ptr,
+                                    ws.ptr, need, k.cdtype, k._stream())
+                _called()
+            else:
+                rc = _raw(k, ALL, x4, P, y4, c4, c["beta"], G.ptr, R.ptr, ws.ptr, need, ublk.data_ptr() if entry == "cached" else None,
+                          sync=False)
+            assert rc == 0, (entry, k.lib.mvf_last_error())
+        torch.cuda.synchronize()
+        outs = []
+        for G, R, ws in bufs:
+            assert G.guards_intact() and R.guards_intact() and ws.guards_intact()
+            outs += [G.host(), R.host()]
+        assert _same_bits(outs[0], outs[2]) and _same_bits(outs[2], outs[4]) and _same_bits(outs[1], outs[5])
+        return outs + [_take(ublk, nb // item)]
+
+    with _option("gram_reg_cols", reg_cols):
+        plain, got = _under(mode, call)
+    assert all(_same_bits(a, b) for a, b in zip(plain, got))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

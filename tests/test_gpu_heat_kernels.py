@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import _heat_cases as hc
-from _kernel_scaffold import Out, Ws, dev, same_bits, stream
+from _kernel_scaffold import MODES, Out, Ws, called, dev, same_bits, stream, under
 
 pytestmark = pytest.mark.gpu
 ERR_RTOL = 1e-12
@@ -36,6 +36,7 @@ def run_grid(init, border, mask, max_err, max_itr, block):
     sweeps, err, hit = ctypes.c_int64(-1), ctypes.c_double(-1.0), ctypes.c_int(-1)
     check(lib().mvf_heat_grid(di.data_ptr(), db.data_ptr(), dm.data_ptr(), H, W, float(max_err), float(max_itr), block, out.ptr,
                               ctypes.byref(sweeps), ctypes.byref(err), ctypes.byref(hit), ws.ptr, ws.nbytes, stream()))
+    called()
     assert out.guards_intact() and ws.guards_intact()
     return out.host(), sweeps.value, err.value, hit.value
 
@@ -115,8 +116,33 @@ def run_graph(case):
     hp = lambda a: a.ctypes.data if a.size else None  # noqa: E731
     check(lib().mvf_heat_graph(hp(indptr), hp(indices), hp(data), hp(fv), n, float(case["max_err"]), float(case["max_itr"]), out.ptr,
                                ctypes.byref(sweeps), ctypes.byref(err), ctypes.byref(hit), ws.ptr, ws.nbytes, stream()))
+    called()
     assert out.guards_intact() and ws.guards_intact()
     return out.host(), sweeps.value, err.value, hit.value
+
+
+# ------------------------------------------------------------------------------------------------- calling conventions
+CONVENTION_COVERS = {"mvf_heat_grid": MODES, "mvf_heat_graph": MODES}
+
+
+def _same(a, b):
+    return same_bits(a[0], b[0]) and a[1] == b[1] and a[3] == b[3] and (a[2] == b[2] or (np.isnan(a[2]) and np.isnan(b[2])))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("block", (1, hc.T), ids=("one-sweep", "blocked"))
+def test_grid_calling_conventions(block, mode):
+    """The plain call's field, sweep count and err on a side stream behind poisoned inputs, at displaced pointers, and with the
+    inputs unchanged.  Both heat entries block (include/mvf.h): the side stream protects the launches of the first batch."""
+    plain, got = under(mode, lambda: run_grid_case(hc.grid_case("rect_12x15"), block), synchronising=True)
+    assert _same(plain, got)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_graph_calling_conventions(mode):
+    """As for the grid; the graph's arrays are host arrays, which the entry copies into its workspace on the stream."""
+    plain, got = under(mode, lambda: run_graph(hc.graph_case("n63")), synchronising=True)
+    assert _same(plain, got)
 
 
 @pytest.mark.parametrize("name", hc.GRAPH_NAMES)

@@ -17,8 +17,9 @@ import pytest
 import torch
 
 import _highd_cases as hc
-from _kernel_scaffold import (DEV, DTYPES, GUARD, bits_equal as _bits_equal, dev as _dev, deviation_table,
-                              guarded as _guarded, intact as _intact, kernel_cache, written as _written)
+from _kernel_scaffold import (DEV, DTYPES, GUARD, MODES, bits_equal as _bits_equal, called as _called, dev as _dev,
+                              deviation_table, guarded as _guarded, intact as _intact, kernel_cache, same_bits as _same_bits,
+                              settle as _settle, take as _take, under as _under, written as _written)
 
 pytestmark = pytest.mark.gpu
 
@@ -133,9 +134,10 @@ def _eval_raw(k, xd, cd, Cd, beta, flags, *, n=None, m=None, d=None, dy=None, nu
             size = int(np.prod(shapes[f])) if elems is None else elems
             bufs[f] = _guarded(size)
     ptr = [bufs[f].data_ptr() if f in bufs and f not in null else None for f in hc.HD_FLAGS]
-    torch.cuda.synchronize()
+    _settle()
     rc = k.lib.mvf_eval_d(xd.data_ptr(), n, None if nullin else cd.data_ptr(), m, d, float(beta),
                           None if nullin else Cd.data_ptr(), dy, int(flags), *ptr, k.cdtype, k._stream())
+    _called()
     torch.cuda.synchronize()
     return rc, bufs
 
@@ -271,12 +273,54 @@ def _build_raw(k, dtype, xd, cd, *, n=None, m=None, d=None, beta=hc.UBLK_BETA, s
     item = 4 if dtype == "float32" else 8
     need = k.ublk_bytes(tn, tm)
     live = need // item if elems is None else elems
-    buf = _guarded(live, k.tdtype)
-    torch.cuda.synchronize()
+    buf = _guarded(live, k.tdtype, unit=16 // item)   # (the cache: 16-byte aligned, as include/mvf.h asks at mvf_ublk_pack)
+    _settle()
     rc = k.lib.mvf_ublk_build_d(xd.data_ptr(), tn if n is None else n, cd.data_ptr(), tm if m is None else m,
                                 xd.shape[1] if d is None else d, float(beta), buf.data_ptr(), need - short, k.cdtype, k._stream())
+    _called()
     torch.cuda.synchronize()
     return rc, buf, live
+
+
+# ------------------------------------------------------------------------------------------------------ calling conventions
+CONVENTION_COVERS = {"mvf_eval_d": MODES, "mvf_ublk_build_d": MODES}
+
+
+def _rows(a, dtype):
+    """(n, d) host coordinates as plain rows of the cell dtype, from the scaffold's own allocation (not ``HipKernels.to_xd``)."""
+    return _dev(np.ascontiguousarray(a, dtype=np.float64).astype(dtype), None)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("d,dy", [(4, 1), (5, 3), (8, 8)])
+def test_eval_d_calling_conventions(dtype, d, dy, mode):
+    """The plain call's bits on a side stream behind poisoned inputs, at displaced pointers (plain rows: one element), and with
+    the inputs unchanged."""
+    case, k = hc.eval_case(65, 259, d, dy), _k(dtype)
+
+    def call():
+        rc, bufs = _eval_raw(k, _rows(case["X"], dtype), _rows(case["ctrl"], dtype), _dev(case["C"]), case["beta"], hc.grid_flags(d, dy))
+        assert rc == 0, k.lib.mvf_last_error()
+        return [_take(b, b.numel() - GUARD) for _, b in sorted(bufs.items())]
+
+    plain, got = _under(mode, call)
+    assert plain and all(_same_bits(a, b) for a, b in zip(plain, got))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("d", [4, 8])
+def test_ublk_build_d_calling_conventions(dtype, d, mode):
+    case, k = hc.eval_case(65, 259, d, 1), _k(dtype)
+
+    def call():
+        rc, buf, live = _build_raw(k, dtype, _rows(case["X"], dtype), _rows(case["ctrl"], dtype))
+        assert rc == 0, k.lib.mvf_last_error()
+        return _take(buf, live)
+
+    plain, got = _under(mode, call)
+    assert _same_bits(plain, got)
 
 
 def _check_cache(dtype, d, x, y):

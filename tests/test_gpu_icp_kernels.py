@@ -10,7 +10,8 @@ import pytest
 import torch
 
 import _icp_cases as ic
-from _kernel_scaffold import DEV, dev as _dev, guarded as _guarded, intact as _intact, stream as _stream, take as _take
+from _kernel_scaffold import (DEV, MODES, called as _called, dev as _dev, guarded as _guarded, intact as _intact,
+                              same_bits as _same_bits, stream as _stream, take as _take, under as _under)
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +56,7 @@ def run_batch(lib, pairs, want_T=True, **kw):
     rc = lib.mvf_icp_batch(recs, P, par["max_iter"], par["error_threshold"], par["inlier_threshold"], par["gamma_threshold"],
                            par["subsample"], int(par["allow_rotation"]), ws.data_ptr(), need, _stream())
     assert rc == 0, lib.mvf_last_error()
+    _called()
     torch.cuda.synchronize()
     assert _intact(ws, need // 8), "wrote past the end of the workspace"
     res = []
@@ -76,6 +78,20 @@ def check(got, c1, c2, **kw):
     assert got["T"].shape == want["T"].shape and err <= bound
     assert np.abs(got["translation"] - want["translation"]).max() <= bound
     return want
+
+
+CONVENTION_COVERS = {"mvf_icp_batch": MODES}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("rot", (False, True))
+def test_calling_conventions(lib, rot, mode):
+    """The plain call's bits on a side stream behind poisoned inputs, at displaced pointers, and with the inputs unchanged."""
+    pairs = [ic.icp_pair(n1, n2, 100 + n1 + 3 * n2) for n1, n2 in ((7, 2), (63, 64), (65, 63))]
+    plain, got = _under(mode, lambda: run_batch(lib, pairs, allow_rotation=rot))
+    for p, g in zip(plain, got):
+        assert (p["gamma"], p["iters"], p["inliers"]) == (g["gamma"], g["iters"], g["inliers"])
+        assert _same_bits(p["T"], g["T"]) and _same_bits(p["translation"], g["translation"])
 
 
 # sizes: the fewer-than-3-inliers exit (M < 3), around a wave, around the cap of a lane's first point, N != M both ways

@@ -9,8 +9,8 @@ import pytest
 import torch
 
 import _kde_cases as kc
-from _kernel_scaffold import (dev as _dev, guarded as _guarded, intact as _intact, ptr as _ptr, stream as _stream,
-                              take as _take, x4 as _x4)
+from _kernel_scaffold import (MODES, called as _called, dev as _dev, guarded as _guarded, intact as _intact, ptr as _ptr,
+                              same_bits as _same_bits, stream as _stream, take as _take, under as _under, x4 as _x4)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,6 +40,7 @@ def _raw(lib, case, dtype):
         rc = lib.mvf_kde(_ptr(t4), n, _ptr(s4), N, case["d"], kc.CODES[case["kernel"]], case["h"], _ptr(w), _ptr(g), cc, _ptr(o),
                          _ptr(ws), need, _lib.MVF_F32 if dtype == "float32" else _lib.MVF_F64, _stream())
         assert rc == 0, lib.mvf_last_error()
+        _called()
         torch.cuda.synchronize()
         _take(ws, need // 8)
         out[:, c0 : c0 + cc] = _take(o, n * cc).reshape(n, cc)
@@ -73,6 +74,19 @@ def test_case_within_its_bound_and_bit_stable(lib, name, dtype):
             assert np.isfinite(far).all() and (far < -790.0).all()   # where a plain sum gives log 0 = -inf
     raw2 = _raw(lib, case, dtype)
     assert np.array_equal(raw2.view(np.uint64), raw.view(np.uint64))
+
+
+CONVENTION_COVERS = {"mvf_kde": MODES}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", ("float64", "float32"))
+@pytest.mark.parametrize("name", ["n257_N255", "n40_N4097", "C2_shift_expo"])   # one split; two; weights and groups
+def test_calling_conventions(lib, name, dtype, mode):
+    """The plain call's bits on a side stream behind poisoned inputs, at displaced pointers, and with the inputs unchanged."""
+    assert kc.splits(len(kc.CASES[name]["T"]), len(kc.CASES[name]["X"])) == (2 if name == "n40_N4097" else 1)
+    plain, got = _under(mode, lambda: _raw(lib, kc.CASES[name], dtype))
+    assert _same_bits(plain, got)
 
 
 def test_a_column_does_not_depend_on_the_other_columns(lib):

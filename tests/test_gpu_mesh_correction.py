@@ -12,7 +12,8 @@ import pytest
 import torch
 
 import _icp_cases as ic
-from _kernel_scaffold import SENTINEL, dev as _dev, guarded as _guarded, intact as _intact, stream as _stream
+from _kernel_scaffold import (MODES, SENTINEL, Ws as _Ws, called as _called, dev as _dev, guarded as _guarded, intact as _intact,
+                              same_bits as _same_bits, stream as _stream, under as _under)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,6 +50,7 @@ def raw_contours(lib, case, param, heights, cap):
     rc = lib.mvf_mesh_contours(verts.data_ptr(), len(case["verts"]), edges.data_ptr(), len(case["edges"]), m3, p5,
                                _dev(heights).data_ptr(), nS, cap, pts.data_ptr(), cnt.data_ptr(), _stream())
     assert rc == 0, lib.mvf_last_error()
+    _called()
     torch.cuda.synchronize()
     assert _intact(pts, nS * cap * 2) and _intact(cnt, nS), "wrote past the end of an output"
     return pts[: nS * cap * 2].cpu().numpy().reshape(nS, cap, 2), cnt[:nS].cpu().numpy()
@@ -64,17 +66,18 @@ def raw_loss(lib, case, params, heights, contours, subsample=500, details=True):
     gamma = _guarded(nT * nS)
     count = _guarded(nT * nS, torch.int32)
     need = int(lib.mvf_mesh_loss_workspace_bytes(nT, nS))
-    ws = _guarded(need // 8, fill=0.0)
+    ws = _Ws(need, fill=0)   # exactly the bytes asked for, guards either side
     m3 = (ctypes.c_double * 3)(*case["mean"])
     keep = [_dev(params), _dev(heights), _dev(flat), _dev(off, torch.int64)]
     rc = lib.mvf_mesh_loss(verts.data_ptr(), len(case["verts"]), edges.data_ptr(), len(case["edges"]), m3, keep[0].data_ptr(), nT,
                            keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), len(flat), nS, 20, 1e-6, 0.1, 0.05, subsample,
                            loss.data_ptr(), gamma.data_ptr() if details else None, count.data_ptr() if details else None,
-                           ws.data_ptr(), need, _stream())
+                           ws.ptr, need, _stream())
     assert rc == 0, lib.mvf_last_error()
+    _called()
     torch.cuda.synchronize()
     assert _intact(loss, nT) and _intact(gamma, nT * nS) and _intact(count, nT * nS)
-    assert _intact(ws, need // 8), "wrote past the end of the workspace"
+    assert ws.guards_intact(), "wrote outside the workspace"
     if not details:
         assert _intact(gamma, 0) and _intact(count, 0)
         return loss[:nT].cpu().numpy()
@@ -145,6 +148,53 @@ def test_loss_equals_the_restatement(lib, case, n_T):
     f32 = loss.astype(np.float32)
     assert (np.abs(f32 - want.astype(np.float32)) <= np.spacing(want.astype(np.float32))).all()
     assert np.array_equal(raw_loss(lib, case, params, HEIGHTS, case["contours"], details=False), loss)   # NULL details; same bits
+
+
+@pytest.mark.parametrize("details", (True, False), ids=("details", "loss-only"))
+def test_more_transformations_than_one_launch_holds(lib, case, details):
+    """n_T = 4101 = 4096 + 5: the second chunk of the launch loop, whose pointers are displaced (params + t0 * 5, loss + t0,
+    gamma + t0 * n_S, count + t0 * n_S) and which reuses the workspace of the first.  8 distinct parameter sets, tiled: every
+    row equals the first of its kind bit for bit (no row depends on its place), and the 8 are the restatement's.  The workspace
+    is exactly the queried size between its guards (``raw_loss``)."""
+    n_T, heights, contours = 4101, HEIGHTS[:2], case["contours"][:2]
+    rng = np.random.default_rng(4101)
+    sets = np.concatenate([[IDENTITY, TRUTH], TRUTH + rng.uniform(-1.0, 1.0, (6, 5)) * [3.0, 3.0, 3.0, 1.0, 0.05]])
+    assert len(np.unique(sets, axis=0)) == 8
+    params = np.tile(sets, (n_T // 8 + 1, 1))[:n_T]
+    want, wgamma, wcount = ic.mesh_loss(case["verts"], case["edges"], case["mean"], sets, heights, contours)
+    assert int(lib.mvf_mesh_loss_workspace_bytes(n_T, 2)) == int(lib.mvf_mesh_loss_workspace_bytes(4096, 2))  # one chunk's worth
+    got = raw_loss(lib, case, params, heights, contours, details=details)
+    loss = got[0] if details else got
+    assert loss.shape == (n_T,)
+    for row in (0, 4095, 4096, 4100):
+        assert _same_bits(loss[row], loss[row % 8]), row
+    assert _same_bits(loss, np.tile(loss[:8], n_T // 8 + 1)[:n_T])
+    print("loss", loss[:8], "restated", want)
+    assert (np.abs(loss[:8] - want) <= _loss_bound(want, 2)).all()
+    if details:
+        gamma, count = got[1], got[2]
+        assert np.array_equal(count[:8], wcount) and np.array_equal(gamma[:8], wgamma)
+        for row in (0, 4095, 4096, 4100):
+            assert _same_bits(gamma[row], gamma[row % 8]) and _same_bits(count[row], count[row % 8]), row
+        assert _same_bits(gamma, np.tile(gamma[:8], (n_T // 8 + 1, 1))[:n_T])
+        assert _same_bits(count, np.tile(count[:8], (n_T // 8 + 1, 1))[:n_T])
+
+
+CONVENTION_COVERS = {"mvf_mesh_loss": MODES, "mvf_mesh_contours": MODES}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("entry", ["mvf_mesh_loss", "mvf_mesh_loss:loss-only", "mvf_mesh_contours"])
+def test_calling_conventions(lib, case, entry, mode):
+    """The plain call's bits on a side stream behind poisoned inputs, at displaced pointers, and with the inputs unchanged."""
+    if entry == "mvf_mesh_contours":
+        call = lambda: raw_contours(lib, case, TRUTH, HEIGHTS, len(case["edges"]))
+    else:
+        params = np.stack([IDENTITY, TRUTH, [8.0, 2.0, -5.0, -2.0, 0.95]])
+        call = lambda: raw_loss(lib, case, params, HEIGHTS, case["contours"], details=entry == "mvf_mesh_loss")
+    plain, got = _under(mode, call)
+    plain, got = (plain, got) if isinstance(plain, tuple) else ((plain,), (got,))
+    assert len(plain) == len(got) and all(_same_bits(a, b) for a, b in zip(plain, got))
 
 
 def test_a_height_that_misses_the_mesh_and_thinned_cuts(lib, case):

@@ -15,7 +15,8 @@ import pytest
 import torch
 
 import _pca_case as pc
-from _kernel_scaffold import DEV, bits as _bits, guarded as _guarded, intact as _guard_ok, stream as _stream
+from _kernel_scaffold import (DEV, MODES, bits as _bits, called as _called, dev as _dev, guarded as _guarded, intact as _guard_ok,
+                              same_bits as _same_bits, stream as _stream, under as _under)
 
 pytestmark = pytest.mark.gpu
 
@@ -60,27 +61,30 @@ class Run:
         self.ws = _guarded(self.ws_bytes // 8)
         self.ws[: self.ws_bytes // 8] = float("nan")  # a partial sum read before it was written would show
         self.mean = _guarded(g)
-        self.ublk = _guarded(self.ub_bytes // (4 if cell == "float32" else 8), TD[cell])
+        item = 4 if cell == "float32" else 8
+        self.ublk = _guarded(self.ub_bytes // item, TD[cell], unit=16 // item)   # (the cache must be 16-byte aligned)
         self.keep = []
 
     def means(self, X, row0=0):
-        xd = torch.from_numpy(X).to(DEV)
+        xd = _dev(X, None)
         self.keep.append(xd)
         _check(self.lib, self.lib.mvf_colmeans(xd.data_ptr(), int(X.dtype == np.float32), X.shape[0], self.g, self.n, row0,
                                                self.mean.data_ptr(), self.ws.data_ptr(), self.ws_bytes, _stream()), "mvf_colmeans")
+        _called()
 
     def pack(self, X, row0=0, centred=True):
-        xd = torch.from_numpy(X).to(DEV)
+        xd = _dev(X, None)
         self.keep.append(xd)
         _check(self.lib, self.lib.mvf_ublk_pack(xd.data_ptr(), int(X.dtype == np.float32), X.shape[0], self.g,
                                                 self.mean.data_ptr() if centred else None, self.n, row0, self.ublk.data_ptr(),
                                                 self.ub_bytes, _cd(self.cell), _stream()), "mvf_ublk_pack")
+        _called()
 
     def _csr(self, csr, stage_bytes):
         indptr, indices, data = csr
         if len(data) == 0:  # no entry at all: the arrays still need an address (indptr keeps them unread)
             indices, data = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=data.dtype)
-        dev =[torch.from_numpy(a).to(DEV) for a in (indptr, indices, data)]
+        dev = [_dev(a, None) for a in (indptr, indices, data)]
         stage = _guarded(-(-stage_bytes // 8))
         self.keep += dev + [stage]
         return dev, stage
@@ -90,6 +94,7 @@ class Run:
         _check(self.lib, self.lib.mvf_colmeans_csr(ip.data_ptr(), ix.data_ptr(), da.data_ptr(), int(csr[2].dtype == np.float32),
                                                    len(csr[0]) - 1, self.g, self.n, row0, self.mean.data_ptr(), self.ws.data_ptr(),
                                                    self.ws_bytes, stage.data_ptr(), stage_bytes, _stream()), "mvf_colmeans_csr")
+        _called()
         torch.cuda.synchronize()
         assert _guard_ok(stage, -(-stage_bytes // 8)), "written behind the staging area"
 
@@ -99,6 +104,7 @@ class Run:
                                                     len(csr[0]) - 1, self.g, self.mean.data_ptr() if centred else None, self.n, row0,
                                                     self.ublk.data_ptr(), self.ub_bytes, stage.data_ptr(), stage_bytes, _cd(self.cell),
                                                     _stream()), "mvf_ublk_pack_csr")
+        _called()
         torch.cuda.synchronize()
         assert _guard_ok(stage, -(-stage_bytes // 8)), "written behind the staging area"
 
@@ -110,6 +116,32 @@ class Run:
         assert _guard_ok(self.ws, self.ws_bytes // 8), "written behind the workspace"
         assert _guard_ok(self.ublk, nel), "written behind the cache"
         return self.mean[: self.g].cpu().numpy().copy(), self.ublk[:nel].cpu().numpy().copy()
+
+
+CONVENTION_COVERS = {"mvf_colmeans": MODES, "mvf_ublk_pack": MODES, "mvf_colmeans_csr": MODES, "mvf_ublk_pack_csr": MODES}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("cell", ["float32", "float64"])
+@pytest.mark.parametrize("form", ["dense", "csr"])
+def test_calling_conventions(lib, form, cell, mode):
+    """Means, then the cache from them (mvf_colmeans + mvf_ublk_pack, or their CSR twins at a staging area of 37 rows): the
+    plain calls' bits on a side stream behind poisoned inputs, at displaced pointers, and with the inputs unchanged."""
+    n, g = 257, 17
+    csr, dense = _csr_case(n, g, "float32", seed=n + g)
+
+    def call():
+        run = Run(lib, n, g, cell)
+        if form == "dense":
+            run.means(dense)
+            run.pack(dense)
+        else:
+            run.means_csr(csr, 37 * g * 4 + 5)
+            run.pack_csr(csr, 37 * g * 4 + 5)
+        return run.host()
+
+    plain, got = _under(mode, call)
+    assert _same_bits(plain[0], got[0]) and _same_bits(plain[1], got[1])
 
 
 def _expected_cache(X, mu, cell):

@@ -11,7 +11,8 @@ import pytest
 import torch
 
 import _prep_cases as pc
-from _kernel_scaffold import (SENTINEL, Out, Ws, deviation_table, dev as _dev, same_bits as _same_bits, stream as _stream)
+from _kernel_scaffold import (MODES, SENTINEL, Out, Ws, called as _called, deviation_table, dev as _dev, same_bits as _same_bits,
+                              stream as _stream, under as _under)
 
 pytestmark = pytest.mark.gpu
 
@@ -62,6 +63,7 @@ class _Unique:
                  ws=self.ws.ptr, ws_bytes=self.need)
         a.update(claim)
         self.rc = lib.mvf_unique_rows(a["X"], a["n"], a["d"], a["uid"], a["rows"], a["count"], a["ws"], a["ws_bytes"], _stream())
+        _called()
         torch.cuda.synchronize()
         assert self.guards_intact(), "wrote outside an output or the workspace"
 
@@ -149,6 +151,7 @@ def test_unique_rows_workspace_bytes(lib):
 def _knn_raw(lib, xd, m, d, k, X=True, out=True):
     o = Out(max(m, 1))
     rc = lib.mvf_knn_rowsum(xd.data_ptr() if X else None, m, d, k, o.ptr if out else None, _stream())
+    _called()
     torch.cuda.synchronize()
     assert o.guards_intact(), "wrote outside rowsum"
     return rc, o
@@ -196,9 +199,52 @@ def _hull_raw(lib, P, E, tol, n=None, nf=None, points=True, eq=True, out=True):
     o = Out(max(len(P), 1), dtype=torch.uint8)
     rc = lib.mvf_hull_mask(pd_.data_ptr() if points else None, n, ed.data_ptr() if eq else None, nf, ctypes.c_double(tol),
                            o.ptr if out else None, _stream())
+    _called()
     torch.cuda.synchronize()
     assert o.guards_intact(), "wrote outside the mask"
     return rc, o
+
+
+# ==================================================================================================== calling conventions
+CONVENTION_COVERS = {"mvf_unique_rows": MODES, "mvf_knn_rowsum": MODES, "mvf_hull_mask": MODES}
+
+
+def _unique_call(lib, name):
+    X = pc.unique_case(name)
+    u = _Unique(lib, _dev(X), *X.shape)
+    assert u.rc == 0, _err(lib)
+    count, uid, rows = u.host()
+    return np.array([count]), uid, rows
+
+
+def _knn_call(lib, name, k):
+    X = pc.knn_case(name)
+    rc, o = _knn_raw(lib, _dev(X), *X.shape, k)
+    assert rc == 0, _err(lib)
+    return (o.host(),)
+
+
+def _hull_call(lib, name):
+    case = pc.hull_exact_case(name)
+    rc, o = _hull_raw(lib, case["points"], case["eq"], case["tol"])
+    assert rc == 0, _err(lib)
+    return (o.host(),)
+
+
+# unique_rows: one chunk of one column; two chunks of three columns.  knn_rowsum: k below and above a wave's 256 candidates.
+# hull_mask: one chunk of facets; three.
+CONVENTION_CASES = {"mvf_unique_rows:n257_d1": (_unique_call, "n257_d1"), "mvf_unique_rows:n4097_d3": (_unique_call, "n4097_d3"),
+                    "mvf_knn_rowsum:k51": (_knn_call, "m257_d5", 51), "mvf_knn_rowsum:k257": (_knn_call, "m257_d5", 257),
+                    "mvf_hull_mask:f4": (_hull_call, "poly_f4_n255"), "mvf_hull_mask:f611": (_hull_call, "poly_f611_n513")}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("entry", list(CONVENTION_CASES))
+def test_calling_conventions(lib, entry, mode):
+    """The plain call's bits on a side stream behind poisoned inputs, at displaced pointers, and with the inputs unchanged."""
+    fn, *args = CONVENTION_CASES[entry]
+    plain, got = _under(mode, lambda: fn(lib, *args))
+    assert len(plain) == len(got) and all(_same_bits(a, b) for a, b in zip(plain, got))
 
 
 @pytest.mark.parametrize("name", pc.HULL_EXACT_NAMES)

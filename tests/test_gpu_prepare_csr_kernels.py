@@ -14,7 +14,7 @@ import torch
 
 import _assign_edge_cases as ec
 from _align_kernel_scaffold import kernels as _k
-from _kernel_scaffold import DEV, guarded, intact as _intact
+from _kernel_scaffold import DEV, MODES, called as _called, dev as _dev, guarded, intact as _intact, same_bits as _same_bits, under as _under
 
 pytestmark = pytest.mark.gpu
 
@@ -67,10 +67,11 @@ def _dense_prepare(k, dense, metric, side):
     n, g = dense.shape
     code = ec.METRICS[metric]
     ld = int(k.lib.mvf_assign_padded_features(g, code))
-    L = torch.from_numpy(np.ascontiguousarray(dense)).to(DEV)
+    L = _dev(dense)
     Lp, ab = _guarded(n * ld, k.tdtype), _guarded(n)
     _lib.check(k.lib.mvf_assign_prepare(L.data_ptr(), n, g, code, side, Lp.data_ptr(), ld, ab.data_ptr(), k.cdtype, k._stream()),
                "mvf_assign_prepare")
+    _called()
     return Lp[: n * ld].cpu().numpy(), ab[:n].cpu().numpy(), ld
 
 
@@ -82,6 +83,7 @@ def _csr_call(k, dev, n, g, metric_code, side, ld, ws_bytes, check=True):
     status = k.lib.mvf_assign_prepare_csr(indptr.data_ptr(), indices.data_ptr(), data.data_ptr(), int(data.dtype == torch.float32),
                                           n, g, metric_code, side, Lp.data_ptr(), ld, ab.data_ptr(), ws.data_ptr(), ws_bytes,
                                           k.cdtype, k._stream())
+    _called()
     torch.cuda.synchronize()
     if status != 0 or not check:
         return status, None, None
@@ -95,6 +97,30 @@ def _upload(indptr, indices, data):
     def up(a):
         return torch.from_numpy(np.concatenate([a, np.zeros(1, dtype=a.dtype)])).to(DEV)
     return up(indptr)[: len(indptr)], up(indices), up(data)
+
+
+CONVENTION_COVERS = {"mvf_assign_prepare": MODES, "mvf_assign_prepare_csr": MODES}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", CELL_DTYPES)
+@pytest.mark.parametrize("metric,side", [("kl", 0), ("cos", 1)])
+def test_calling_conventions(metric, side, dtype, mode):
+    """The dense prepare and the CSR prepare (four staging rows) of one 257 x 17 layer: the plain calls' bits on a side stream
+    behind poisoned inputs, at displaced pointers, and with the inputs unchanged."""
+    k, (n, g), code = _k(dtype), (257, 17), ec.METRICS[metric]
+    indptr, indices, data, dense = make_csr(n, g, np.float32, seed=5)
+
+    def call():
+        Lp, ab, ld = _dense_prepare(k, dense, metric, side)
+        dev = tuple(_dev(a, None) for a in (indptr, indices, data))
+        status, Lp2, ab2 = _csr_call(k, dev, n, g, code, side, ld, 4 * g * 8)
+        assert status == 0, k.lib.mvf_last_error()
+        return Lp, ab, Lp2, ab2
+
+    plain, got = _under(mode, call)
+    assert all(_same_bits(a, b) for a, b in zip(plain, got))
+    assert _same_bits(plain[0], plain[2]) and _same_bits(plain[1], plain[3])
 
 
 def _check_case(k, indptr, indices, data, dense, metric, side, what):

@@ -23,7 +23,8 @@ import pytest
 import torch
 
 import _rk45_cases as rc
-from _kernel_scaffold import DEV, bits as _bits, deviation_table, kernel_cache, Out as _Out, same_bits
+from _kernel_scaffold import (DEV, MODES, bits as _bits, called as _called, dev as _dev, deviation_table, kernel_cache,
+                              Out as _Out, same_bits, under as _under, x4 as _sx4)
 
 pytestmark = pytest.mark.gpu
 
@@ -371,3 +372,35 @@ def test_writes_nothing_around_its_buffers(dtype, n, chunked):
             got = o.host()
             assert not (got == o.sent).any()
             assert np.array_equal(_bits(got), _bits(ref.reshape(-1)))
+
+
+CONVENTION_COVERS = {"mvf_integrate_rk45": MODES}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("chunked", [False, True], ids=["one stage", "chunked"])
+def test_calling_conventions(dtype, chunked, mode):
+    """Times, trajectories and statistics of 257 starts: the plain call's bits on a side stream behind poisoned inputs, at
+    displaced pointers, and with the inputs unchanged."""
+    from spateo_amd import _lib
+
+    case = rc.count_case(dtype, rc.CAP[dtype] + 1) if chunked else rc.lane_case(dtype)
+    (starts, _), k, n, n_out = _tile(case, 257), _k(dtype), 257, 9
+    w = (ctypes.c_double * 6)(*case["scale"], *case["offset"])
+
+    def call():
+        x4, c4 = _sx4(np.asarray(starts).reshape(-1, 3), dtype), _sx4(np.asarray(case["ctrl"]).reshape(-1, 3), dtype)
+        Cd = _dev(np.ascontiguousarray(case["C"], dtype=np.float64).reshape(-1, 3))
+        tb, xb, sb = _Out(n * n_out), _Out(3 * n * n_out), _Out(4 * n, dtype=torch.int32)
+        _lib.check(k.lib.mvf_integrate_rk45(x4.data_ptr(), n, c4.data_ptr(), c4.shape[0], float(case["beta"]), Cd.data_ptr(),
+                                            k._affine_buf(case["affine"]), case["d"], w, case["t_bound"], rc.RTOL, rc.ATOL,
+                                            case["max_step"], MAX_STEPS, _lib.RK45_UNIFORM_TIME, n_out, tb.ptr, xb.ptr, sb.ptr,
+                                            k.cdtype, k._stream()), "mvf_integrate_rk45")
+        _called()
+        torch.cuda.synchronize()
+        assert tb.guards_intact() and xb.guards_intact() and sb.guards_intact()
+        return tb.host(), xb.host(), sb.host()
+
+    plain, got = _under(mode, call)
+    assert all(same_bits(a, b) for a, b in zip(plain, got))

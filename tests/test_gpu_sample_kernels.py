@@ -12,8 +12,8 @@ import pytest
 import torch
 
 import _sample_cases as sc
-from _kernel_scaffold import (dev as _dev, guarded as _guarded, intact as _intact, ptr as _ptr, stream as _stream,
-                              take as _take)
+from _kernel_scaffold import (MODES, called as _called, dev as _dev, guarded as _guarded, intact as _intact, ptr as _ptr,
+                              same_bits as _same_bits, stream as _stream, take as _take, under as _under)
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +55,7 @@ def _run_trn(lib, problems):
 
     recs = (_lib.TrnProblem * len(problems))(*[p.rec for p in problems])
     assert lib.mvf_trn(recs, len(problems), _stream()) == 0, lib.mvf_last_error()
+    _called()
     torch.cuda.synchronize()
     return [p.nodes() for p in problems]
 
@@ -67,6 +68,7 @@ def _nearest(lib, X, Q):
     idx = _guarded(len(Q), torch.int64)
     rc = lib.mvf_nearest_rows(_ptr(Xd), len(X), X.shape[1], _ptr(Qd), len(Q), _ptr(idx), _ptr(ws), need, _stream())
     assert rc == 0, lib.mvf_last_error()
+    _called()
     torch.cuda.synchronize()
     _take(ws, need // 8)
     return _take(idx, len(Q))
@@ -185,9 +187,40 @@ def _kmeans(lib, X, C0, iters):
     labels, counts = _guarded(N, torch.int32), _guarded(n, torch.int64)
     rc = lib.mvf_kmeans(_ptr(Xd), N, d, _ptr(C), n, iters, _ptr(labels), _ptr(counts), _ptr(ws), need, _stream())
     assert rc == 0, lib.mvf_last_error()
+    _called()
     torch.cuda.synchronize()
     _take(ws, need // 8)
     return _take(C, n * d).reshape(n, d), _take(labels, N), _take(counts, n)
+
+
+# ------------------------------------------------------------------------------------------------------ calling conventions
+CONVENTION_COVERS = {"mvf_trn": MODES, "mvf_nearest_rows": MODES, "mvf_kmeans": MODES}
+
+
+def _trn_call(lib):   # two problems of one launch, one of them with a cutoff table
+    return tuple(_run_trn(lib, [Trn(sc.uniform_cloud(N, d, seed=N), n, tmax=6, c=c) for N, d, n, c in ((400, 2, 33, 0), (700, 2, 64, 0.001))]))
+
+
+def _nearest_call(lib, N):   # 4096 candidates need no workspace, 5000 run in two chunks through one
+    return (_nearest(lib, sc.uniform_cloud(N, 3, seed=2), sc.uniform_cloud(300, 3, seed=3)),)
+
+
+def _kmeans_call(lib, n):   # up to 64 centroids and above: the two assignment kernels
+    X = sc.uniform_cloud(1000, 3, seed=n)
+    return _kmeans(lib, X, X[:n].copy(), 3)
+
+
+CONVENTION_CASES = {"mvf_trn": (_trn_call,), "mvf_nearest_rows:N4096": (_nearest_call, 4096), "mvf_nearest_rows:N5000": (_nearest_call, 5000),
+                    "mvf_kmeans:n64": (_kmeans_call, 64), "mvf_kmeans:n65": (_kmeans_call, 65)}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("entry", list(CONVENTION_CASES))
+def test_calling_conventions(lib, entry, mode):
+    """The plain call's bits on a side stream behind poisoned inputs, at displaced pointers, and with the inputs unchanged."""
+    fn, *args = CONVENTION_CASES[entry]
+    plain, got = _under(mode, lambda: fn(lib, *args))
+    assert len(plain) == len(got) and all(_same_bits(a, b) for a, b in zip(plain, got))
 
 
 KMEANS = [(1, 1, 3), (65, 2, 10), (1000, 64, 10), (1000, 65, 10), (100_003, 257, 3), (20_000, 2000, 3)]

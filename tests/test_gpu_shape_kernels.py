@@ -15,7 +15,8 @@ import pytest
 import torch
 
 import _shape_cases as sc
-from _kernel_scaffold import Ws, dev as _dev, guarded as _guarded, intact as _intact, ptr as _ptr, stream as _stream, take as _take
+from _kernel_scaffold import (MODES, Ws, called as _called, dev as _dev, guarded as _guarded, intact as _intact, ptr as _ptr,
+                              same_bits as _same_bits, stream as _stream, take as _take, under as _under)
 
 pytestmark = pytest.mark.gpu
 
@@ -52,9 +53,22 @@ def _raw(lib, pcs, nsub, order, ws_fill=0xA5):
     rc = lib.mvf_shape_descriptors(_ptr(pts), n, _ptr(dlo), _ptr(dhi), nsub, sc.ORDERS[order], g, *[_ptr(bufs[name]) for name, _ in OUTS],
                                    ws.ptr, need, _stream())
     assert rc == 0, lib.mvf_last_error()
+    _called()
     torch.cuda.synchronize()
     assert ws.guards_intact(), "wrote outside the workspace"
     return {name: _take(bufs[name], sizes[name]) for name, _ in OUTS}
+
+
+CONVENTION_COVERS = {"mvf_shape_descriptors": MODES}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name,order", [("E_k63", "cubic"), ("E_cubic", "cubic"), ("A", "cubic")])   # 1 voxel (twice); 4^3 voxels
+def test_calling_conventions(lib, name, order, mode):
+    """The plain call's bits on a side stream behind poisoned inputs, at displaced pointers, and with the inputs unchanged."""
+    case = sc.CASES[name]
+    plain, got = _under(mode, lambda: _raw(lib, case["pcs"], case["n"], order))
+    assert all(_same_bits(plain[k], got[k]) for k, _ in OUTS)
 
 
 def _kept(raw):

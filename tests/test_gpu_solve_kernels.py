@@ -22,8 +22,9 @@ import pytest
 import torch
 
 import _solve_cases as sc
-from _kernel_scaffold import (SENTINEL as _SENTINEL, WS_FILL, dev as _dev, deviation_table, kernel_cache, option as _option,
-                              Out as _Out, same_bits as _same_bits, stream as _stream, Ws as _Ws, x4 as _x4)
+from _kernel_scaffold import (MODES, SENTINEL as _SENTINEL, WS_FILL, called as _called, dev as _dev, deviation_table, kernel_cache,
+                              option as _option, Out as _Out, same_bits as _same_bits, settle as _settle, stream as _stream,
+                              under as _under, Ws as _Ws, x4 as _x4)
 
 pytestmark = pytest.mark.gpu
 
@@ -72,7 +73,7 @@ def _call(entry, Gd, Kd, ls2, R, *, jitter=0.0, shift=sc.SHIFT, rcond=2.0 ** -52
     nbytes = ws.nbytes if ws_bytes is None else ws_bytes
     C, info, piv = _Out(m, nrhs), _Out(1, dtype=torch.int32), _Out(2)
     einfo = _Out(12) if einfo is None else einfo
-    torch.cuda.synchronize()
+    _settle()
     if entry == "solve":
         rc = lib.mvf_solve(Gd.data_ptr(), Kd.data_ptr(), float(ls2), float(jitter), Rd.data_ptr(), m, nrhs, C.ptr, info.ptr,
                            piv.ptr if want_pivots else None, ws.ptr, nbytes, _stream())
@@ -87,6 +88,7 @@ def _call(entry, Gd, Kd, ls2, R, *, jitter=0.0, shift=sc.SHIFT, rcond=2.0 ** -52
     else:
         rc = lib.mvf_solve_minnorm_lrd_async(Gd.data_ptr(), Kd.data_ptr(), float(ls2), float(tolf), float(rcond), Rd.data_ptr(), m,
                                              nrhs, C.ptr, info.ptr, einfo.ptr, int(form_hint), ws.ptr, nbytes, _stream())
+    _called(synchronising=entry in ("minnorm", "lr", "lrd"))   # (include/mvf.h: these three read ranks and pivots back)
     torch.cuda.synchronize()
     for o in (C, info, piv, einfo) + ((basis,) if basis is not None else ()):
         assert o.guards_intact(), f"{entry}: an output guard was written"
@@ -117,6 +119,90 @@ def _within(entry, c, C, Cs, what=""):
     _note(entry, c["family"], r)
     assert r <= 1.0, (entry, c["id"], what, r)
     return r
+
+
+# ================================================================================================== calling conventions
+CONVENTION_COVERS = {"mvf_solve": MODES, "mvf_solve_minnorm": MODES, "mvf_solve_minnorm_lr": MODES, "mvf_solve_minnorm_lrd": MODES,
+                     "mvf_solve_minnorm_lrd_async": MODES, "mvf_lr_pivot_order": MODES, "mvf_pinv_diag": MODES}
+
+
+def _conv_solve(path):
+    c = sc.solve_cases([65])[0]
+    with _option("solve_small_off", 1 if path == "blocked" else 0):
+        a = _call("solve", _dev(c["G"]), _dev(c["K"]), c["ls2"], c["R"][:, :3])
+    assert a.rc == 0 and a.info == 0, _last_error()
+    return a.C, a.piv
+
+
+def _conv_pinv(a, lc, dtype, lowrank):
+    pc, n = lc["pc"], 257
+    x4, c4, out = _x4(lc["X"][:n], lc["X"].dtype), _x4(lc["ctrl"], lc["ctrl"].dtype), _Out(n)
+    rc = _lib().mvf_pinv_diag(x4.data_ptr(), n, c4.data_ptr(), len(lc["ctrl"]), pc["beta"], pc["rcond"], lowrank, out.ptr, a.ws.ptr,
+                              a.ws.nbytes, _k(dtype).cdtype, _stream())
+    _called(synchronising=bool(lowrank))   # (include/mvf.h: "Synchronises `stream` once on the lowrank path")
+    torch.cuda.synchronize()
+    assert rc == 0 and out.guards_intact() and a.ws.guards_intact(), _last_error()
+    return out.host()
+
+
+def _conv_minnorm(dtype):
+    """mvf_solve_minnorm, then mvf_pinv_diag on the decomposition it left."""
+    lc = _leverage_case(129, dtype)
+    a = _call("minnorm", _dev(lc["A"]), _dev(np.zeros((129, 129))), 0.0, np.ones((129, 3)), rcond=lc["pc"]["rcond"])
+    assert a.rc == 0 and a.info == 0, _last_error()
+    return a.C, a.einfo[:10], _conv_pinv(a, lc, dtype, 0)
+
+
+def _conv_lr(dtype):
+    """mvf_solve_minnorm_lr, then mvf_lr_pivot_order and mvf_pinv_diag on the factorisation it left."""
+    lc = _leverage_case(129, dtype)
+    a = _call("lr", _dev(lc["A"]), _dev(np.zeros((129, 129))), 0.0, np.ones((129, 3)), rcond=lc["pc"]["rcond"])
+    assert a.rc == 0 and a.info == 0, _last_error()
+    rc, order, vals, tol = _pivot_order(a.ws, 129)
+    _called(synchronising=True)   # (include/mvf.h: "Synchronises `stream`")
+    assert rc == 0
+    return a.C, a.einfo[:10], order, vals, np.array([tol]), _conv_pinv(a, lc, dtype, 1)
+
+
+def _conv_lrd(form):
+    """mvf_solve_minnorm_lrd on its Jacobi path, or in its factor form, then mvf_solve_minnorm_lrd_async and the synchronous
+    direct form on the state each call leaves to the next."""
+    m = 128
+    c = sc.make_case("well", m)
+    Gd, Kd, R = _dev(c["G"]), _dev(c["K"]), c["R"][:, :5]
+    if form == "jacobi":
+        with _option("lr_no_deflate", 1):
+            j = _call("lrd", Gd, Kd, c["ls2"], R, rcond=c["rcond"])
+        assert j.rc == 0 and int(j.einfo[8]) == 0
+        return j.C, j.einfo[:10]
+    ws = _Ws(_lib().mvf_solve_minnorm_lrd_workspace_bytes(m, 5), fill=0)
+    s0 = _call("lrd", Gd, Kd, c["ls2"], R, rcond=c["rcond"], ws=ws)
+    assert s0.rc == 0 and int(s0.einfo[8]) == 1
+    a1 = _call("lrd_async", Gd, Kd, c["ls2"], R, rcond=c["rcond"], form_hint=int(s0.einfo[8]), ws=ws)
+    assert a1.rc == 0 and a1.info == 0 and int(a1.einfo[8]) == 2, a1.einfo
+    s2 = _call("lrd", Gd, Kd, c["ls2"], R, rcond=c["rcond"], rank_hint=m, ws=ws)
+    assert s2.rc == 0 and int(s2.einfo[8]) == 2
+    return s0.C, s0.einfo[:10], a1.C, a1.einfo[:10], s2.C, s2.einfo[:10]
+
+
+CONVENTION_CASES = {"mvf_solve:small": (_conv_solve, "small"), "mvf_solve:blocked": (_conv_solve, "blocked"),
+                    "mvf_solve_minnorm+pinv_diag:float64": (_conv_minnorm, "float64"),
+                    "mvf_solve_minnorm+pinv_diag:float32": (_conv_minnorm, "float32"),
+                    "mvf_solve_minnorm_lr+pivot_order+pinv_diag:float64": (_conv_lr, "float64"),
+                    "mvf_solve_minnorm_lr+pivot_order+pinv_diag:float32": (_conv_lr, "float32"),
+                    "mvf_solve_minnorm_lrd:jacobi": (_conv_lrd, "jacobi"), "mvf_solve_minnorm_lrd:factor+async+direct": (_conv_lrd, "factor")}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("entry", list(CONVENTION_CASES))
+def test_calling_conventions(entry, mode):
+    """The plain calls' bits on a side stream behind poisoned inputs, at displaced pointers, and with the inputs unchanged.
+    The minimum-norm solves, mvf_lr_pivot_order and the low-rank mvf_pinv_diag synchronise their stream (include/mvf.h): the
+    side stream protects their launches up to that point; mvf_solve and mvf_solve_minnorm_lrd_async must return while the
+    inputs are still in flight."""
+    fn, arg = CONVENTION_CASES[entry]
+    plain, got = _under(mode, lambda: fn(arg))
+    assert len(plain) == len(got) and all(_same_bits(np.asarray(a), np.asarray(b)) for a, b in zip(plain, got))
 
 
 # ================================================================================================== mvf_solve

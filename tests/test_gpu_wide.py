@@ -15,7 +15,8 @@ import numpy as np
 import pytest
 import torch
 
-from _kernel_scaffold import DTYPES, bits_equal as _same_bits, fresh_kernels as _k
+from _kernel_scaffold import (DTYPES, bits_equal as _same_bits, called as _called, fresh_kernels as _k, under as _under,
+                              watch as _watch)
 
 pytestmark = pytest.mark.gpu
 
@@ -141,8 +142,29 @@ class Case:
         stats.fill_(s0)
         assert self.rhs(R) == 0, self.k.lib.mvf_last_error()
         assert self.apply(Vd, r, stats) == 0, self.k.lib.mvf_last_error()
+        _called()
         torch.cuda.synchronize()
         return R, Vd, r, stats
+
+
+# The operands of a Case are HipKernels allocations, made and synchronised when the case is built: no displaced pointers here,
+# and on the side stream the outputs, not the inputs, are in flight (a launch on another stream is overwritten by their fill).
+CONVENTION_COVERS = {"mvf_rhs_cached": ("side_stream", "inputs"), "mvf_apply_cached": ("side_stream", "inputs")}
+
+
+@pytest.mark.parametrize("mode", ["side_stream", "inputs"])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dy", [5, 65])   # one column tile; more than one panel
+def test_calling_conventions(dtype, dy, mode):
+    case = Case(dtype, 300, 129, dy)
+
+    def call():
+        _watch(case.k._ublk, case.P, case.Yd, case.Cd)
+        return case.run(s0=0.5)
+
+    plain, got = _under(mode, call)
+    for x, y in zip(plain, got):
+        assert _same_bits(x, y)
 
 
 def _ratio(name, dtype, err, bound):

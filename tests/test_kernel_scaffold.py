@@ -185,3 +185,125 @@ def test_deviation_table_with_another_arity(capsys):
     with pytest.raises(StopIteration):
         next(gen)
     assert capsys.readouterr().out == "\n| a | b | c | worst |x| |\n|---|---|---|---|\n| p | q | a | 2 |\n| p | q | r | 0.5 |\n"
+
+
+# ---- calling conventions (the side stream needs a device: tests/test_gpu_kernels.py holds its controls) ----
+def _start(t):
+    """Address of the first byte of the allocation a tensor lives in."""
+    return t.untyped_storage().data_ptr()
+
+
+def test_outside_any_mode_pointers_sit_at_the_allocation_start():
+    assert ks.convention.active is None and ks.MODES == ("side_stream", "displaced", "inputs")
+    t = ks.dev(np.arange(6.0).reshape(2, 3), device="cpu")
+    x = ks.x4(np.arange(6.0).reshape(2, 3), np.float32, device="cpu")
+    g = ks.guarded(7, torch.int32, device="cpu")
+    assert t.data_ptr() == _start(t) and t.shape == (2, 3) and t.dtype == torch.float64 and t._base is None
+    assert x.data_ptr() == _start(x) and x.shape == (2, 4) and x.dtype == torch.float32
+    assert g.data_ptr() == _start(g) and g.shape == (7 + ks.GUARD,) and g.dtype == torch.int32
+    out, ws = ks.Out(7, 3, device="cpu"), ks.Ws(24, device="cpu")
+    assert out.ptr == _start(out.big) + ks.GUARD * 8 and out.big.numel() == 21 + 2 * ks.GUARD
+    assert ws.ptr == _start(ws.big) + ks.GUARD_BYTES and ws.big.numel() == 24 + 2 * ks.GUARD_BYTES
+    ks.called()  # a no-op
+
+
+@pytest.mark.parametrize("tdtype", TDTYPES, ids=str)
+def test_displaced_pointers_start_one_unit_in_and_the_guards_still_bite(tdtype):
+    n, size = 7, torch.empty(0, dtype=tdtype).element_size()
+    with ks.convention("displaced"):
+        t = ks.dev(np.arange(6).reshape(2, 3), tdtype, device="cpu")
+        wide = ks.dev(np.arange(6), tdtype, device="cpu", unit=4)   # a pointer with a stated alignment of 4 elements
+        assert t.data_ptr() == _start(t) + size and t.shape == (2, 3) and t.flatten().tolist() == list(range(6))
+        assert wide.data_ptr() == _start(wide) + 4 * size
+        buf = ks.guarded(n, tdtype, device="cpu")
+        assert buf.data_ptr() == _start(buf) + size and buf.numel() == n + ks.GUARD and ks.intact(buf, n)
+        for at in (-1, n, n + ks.GUARD - 1):    # the element in front, the first and the last one behind
+            buf = ks.guarded(n, tdtype, device="cpu")
+            buf._base[1 + at] = _other(tdtype)
+            assert not ks.intact(buf, n)
+            with pytest.raises(AssertionError):
+                ks.take(buf, n)
+        buf = ks.guarded(n, tdtype, fill=_other(tdtype), device="cpu")
+        assert ks.written(buf, n) and ks.intact(buf, n) and ks.take(buf, n).tolist() == [_other(tdtype)] * n
+        out = ks.Out(n, dtype=tdtype, device="cpu")
+        assert out.ptr == _start(out.big) + (ks.GUARD + 1) * size and out.guards_intact() and out.untouched()
+        for at in (ks.GUARD, ks.GUARD + 1 + n, 0, 2 * ks.GUARD + n):
+            out = ks.Out(n, dtype=tdtype, device="cpu")
+            out.big[at] = _other(tdtype)
+            assert not out.guards_intact() and out.untouched()
+        for at in (0, n - 1):
+            out = ks.Out(n, dtype=tdtype, device="cpu")
+            out.t[at] = _other(tdtype)
+            assert out.guards_intact() and not out.untouched()
+    assert ks.convention.active is None and ks.guarded(n, tdtype, device="cpu").storage_offset() == 0
+
+
+def test_displaced_rows_and_workspaces_keep_their_alignment():
+    with ks.convention("displaced"):
+        for dtype, row in ((np.float32, 16), (np.float64, 32)):
+            x = ks.x4(np.arange(6.0).reshape(2, 3), dtype, device="cpu")
+            assert x.data_ptr() == _start(x) + row and x.shape == (2, 4) and x[1].tolist() == [3.0, 4.0, 5.0, 0.0]
+        ws = ks.Ws(24, device="cpu")
+        assert ws.ptr == _start(ws.big) + ks.GUARD_BYTES + ks.WS_ALIGN and ws.guards_intact()
+        for at in (ks.GUARD_BYTES + ks.WS_ALIGN - 1, ks.GUARD_BYTES + ks.WS_ALIGN + 24, 0, 2 * ks.GUARD_BYTES + ks.WS_ALIGN + 23):
+            ws = ks.Ws(24, device="cpu")
+            ws.big[at] = 0
+            assert not ws.guards_intact()
+        for at in (0, 23):
+            ws = ks.Ws(24, device="cpu")
+            ws.big[ks.GUARD_BYTES + ks.WS_ALIGN + at] = 0
+            assert ws.guards_intact()
+        buf = ks.guarded(24, device="cpu", unit=32)   # a workspace of doubles held in a one-sided buffer
+        assert buf.data_ptr() == _start(buf) + 256 and ks.intact(buf, 24)
+        buf._base[31] = 0.0
+        assert not ks.intact(buf, 24)
+
+
+@pytest.mark.parametrize("mode", ["inputs", "displaced"])
+def test_a_changed_input_is_caught_to_the_bit(mode):
+    with ks.convention(mode):
+        a = ks.dev(np.array([1.0, 0.0, -2.5]), device="cpu")
+        x = ks.x4(np.ones((2, 3)), np.float32, device="cpu")
+        io = ks.dev(np.arange(3), torch.int32, device="cpu", inout=True)
+        io[1] = 7     # not const in the header: the call may write it
+    for flip in ("sign of zero", "one mantissa bit", "padding of a row"):
+        with pytest.raises(ks.ConventionError, match="changed its input number"):
+            with ks.convention(mode):
+                a = ks.dev(np.array([1.0, 0.0, -2.5]), device="cpu")
+                x = ks.x4(np.ones((2, 3)), np.float32, device="cpu")
+                if flip == "sign of zero":
+                    a[1] = -0.0
+                elif flip == "one mantissa bit":
+                    a.view(torch.int64)[2] ^= 1
+                else:
+                    x.view(torch.int32)[1, 3] ^= 1
+    with pytest.raises(ZeroDivisionError):   # an exception of the block passes through, and the mode ends
+        with ks.convention(mode):
+            1 / 0
+    assert ks.convention.active is None
+
+
+def test_under_runs_plain_first_then_the_mode():
+    seen = []
+
+    def fn():
+        seen.append(None if ks.convention.active is None else ks.convention.active.mode)
+        return ks.dev(np.arange(3.0), device="cpu").data_ptr() % 8
+
+    assert ks.under("displaced", fn) == (0, 0) and seen == [None, "displaced"]
+    with pytest.raises(AssertionError):
+        ks.convention("sideways")
+
+
+def test_watched_tensors_must_keep_their_bits():
+    t = torch.arange(5, dtype=torch.float64)
+    ks.watch(t)                      # outside a block: nothing is kept
+    t[0] = 7.0
+    with ks.convention("inputs"):
+        ks.watch(t, None)
+        ks.called()                  # outside the side stream: no-ops, whatever the entry point is
+        ks.called(synchronising=True)
+    with pytest.raises(ks.ConventionError, match="changed its input number 0"):
+        with ks.convention("inputs"):
+            ks.watch(t)
+            t[4] = -t[4]
