@@ -982,6 +982,56 @@ int mvf_heat_graph(const int64_t* indptr, const int32_t* indices, const double* 
  * CSC arrays; 0 for a refused shape. */
 size_t mvf_heat_graph_workspace_bytes(int64_t n, int64_t nnz);
 
+/* ---- a kernel along the tissue: exact k nearest neighbours and graph distances on the device (mvf_graph.hip) ---------------
+ * Four additions to the table (mvf_version stays 7 by the rule above).  float64 throughout whatever the cell dtype, no
+ * floating-point atomics: two calls give equal bits.  mvf_knn and mvf_graph_sssp are asynchronous on `stream` and never block. */
+#define MVF_KNN_MAX_K 64
+#define MVF_SSSP_STATUS 4
+/* Replaces: `kneighbors_graph(points, knn, mode="distance", include_self=False)` of `construct_knn_graph`
+ * (spateo/alignment/methods/utils.py:1176), sklearn's KD-tree query on the host.
+ *   points (n x d float64 row-major, device, finite): d = 2 or 3, 1 <= k <= MVF_KNN_MAX_K, k < n < 2^31.
+ *   idx (n x k int32), dist (n x k float64): the k nearest OTHER points of each point, every row ascending by (distance, index).
+ *   A point is left out of its own list by index, not by distance: a duplicate of it is a neighbour at distance 0.  The distance
+ *   is sqrt((dx dx + dy dy) + dz dz) of explicit differences, no fused multiply-add: what sklearn's KD-tree computes.  Among
+ *   equal distances the smaller index wins (sklearn's order there is unspecified).
+ *   A uniform grid of about n / k cells (at most 2^24), the points ordered by cell with the radix sort of mvf_unique_rows; one
+ *   query per lane walks Chebyshev rings of cells until its k-th distance lies inside the region visited.  A cloud that falls
+ *   into one cell (n < 2 k, or a zero extent) is searched exactly all the same, merely slowly.  The cell edge comes from the
+ *   box's volume over the axes the cloud extends along, (V k / n)^(1/d'): a thin slab or a line keeps about k points per cell.
+ * workspace: mvf_knn_workspace_bytes(n, d, k), 256-byte aligned.  Refused, with nothing launched: "bad shape", "null pointer",
+ * "256-byte aligned", "workspace too small". */
+int mvf_knn(const double* points, int64_t n, int d, int k, int32_t* idx, double* dist, void* workspace, size_t workspace_bytes,
+            void* stream);
+/* Replaces: the dense N x N array `A.toarray()` of `construct_knn_graph` (utils.py:1177).  The sort buffers, the points in cell
+ * order with their indices, and one offset per cell; 0 for a refused shape. */
+size_t mvf_knn_workspace_bytes(int64_t n, int d, int k);
+/* Replaces: the loop of `networkx.single_source_dijkstra` calls of `con_K_graph` (utils.py:1207-1213), one per inducing variable.
+ *   indptr (n + 1 int64), indices (nnz int32), weights (nnz float64, >= 0): the CSR arrays of an undirected graph, on the device
+ *   (both directions of every edge stored); an index outside 0 .. n - 1 is skipped.  1 <= n < 2^31, m <= 2^20, n m <= 2^39 - 256.
+ *   sources (m int32, device, repeats allowed; one outside 0 .. n - 1 sets nothing), dist (n x ld float64, ld >= m): column s
+ *   holds the distances from sources[s], one row per node.  init != 0: +inf everywhere and 0 at (sources[s], s) first.
+ *   sweeps: the Bellman-Ford sweeps this call queues (0 .. 65536).  A sweep replaces every entry in place by
+ *   min(d[v], min over the edges (v, u) of d[u] + w): every stored value is the left-to-right sum along a path, and the fixed
+ *   point - the minimum of that sum over all paths, which is what Dijkstra returns - does not depend on the order of the
+ *   relaxations; values short of it do.  An unreachable node keeps +inf.
+ *   status (MVF_SSSP_STATUS int64, device, overwritten): [0] the entries lowered by the sweeps of this call, [1] those of its
+ *   last sweep, [3] the sweeps queued.  Only zero or non-zero means anything: a sweep that finds the sweep before it at zero
+ *   returns at once, and a caller that reads [0] == 0 (mvf_read_back) has the fixed point.  A path has at most n - 1 edges, so
+ *   n sweeps in all reach it.
+ * Refused, with nothing launched: "bad shape", "bad sweeps", "null pointer". */
+int mvf_graph_sssp(const int64_t* indptr, const int32_t* indices, const double* weights, int64_t n, int64_t nnz,
+                   const int32_t* sources, int64_t m, double* dist, int64_t ld, int init, int sweeps, int64_t* status,
+                   void* stream);
+/* Replaces: the same statement as mvf_pinv_diag (`SigmaDiag`, morpho_class.py:1295-1297) when U is not con_K of coordinates -
+ * the `kernel_type="geodist"` branch, where U = con_K_graph(graph, inducing_idx) (morpho_class.py:865-871).
+ *   diag_out[n] = (U pinv(A) U^T)_nn with the rows of U read from the operand cache `ublk` (mvf_ublk_build / mvf_ublk_pack for
+ *   these n and m, of `dtype`; ublk_bytes >= mvf_ublk_bytes(n, m, dtype)) instead of regenerated: the one consumer of U that had
+ *   no cache-reading form.  One kernel with mvf_pinv_diag behind the point where the kernel value is formed: on a cache that
+ *   mvf_ublk_build made of (x4, ctrl4, beta) the two give equal bits.  workspace, rcond, lowrank and the synchronisation on the
+ *   lowrank path as mvf_pinv_diag. */
+int mvf_pinv_diag_cached(const void* ublk, size_t ublk_bytes, int64_t n, int64_t m, double rcond, int lowrank, double* diag_out,
+                         void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1961,16 +1961,19 @@ __global__ __launch_bounds__(256) void pinv_weights_kernel(const double* __restr
 
 constexpr int PD_CT = 128;  // control points per LDS stage
 constexpr int PD_RB = 8;    // rows of Y per pass over the control points
-template <typename T>
+// CACHED: the kernel values are read from the operand cache Ublk[m/16][npad][16] of mvf_ublk_build / mvf_ublk_pack (ublk, npad =
+// n rounded up to 256; the padded rows and columns hold zeros) instead of being formed from x4 and ctrl4, which are not read;
+// everything behind the value - the staging of Y, the order of the sums - is the same code.
+template <typename T, bool CACHED>
 __global__ __launch_bounds__(256) void pinv_diag_kernel(const T* __restrict__ x4, int64_t n, const T* __restrict__ ctrl4,
                                                         int64_t m, T s, const double* __restrict__ Y, int64_t nrows,
                                                         int64_t mp, const double* __restrict__ gw,
-                                                        double* __restrict__ out) {
+                                                        double* __restrict__ out, const T* __restrict__ ublk, int64_t npad) {
     using V4T = typename Vec4<T>::type;
     __shared__ V4T sc[PD_CT];
     __shared__ double sy[PD_RB][PD_CT];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const V4T xv = (i < n) ? reinterpret_cast<const V4T*>(x4)[i] : V4T{0, 0, 0, 0};
+    const V4T xv = (!CACHED && i < n) ? reinterpret_cast<const V4T*>(x4)[i] : V4T{0, 0, 0, 0};
     const T px = xv.x * s, py = xv.y * s, pz = xv.z * s;
     double d = 0.0;
     for (int64_t rb = 0; rb < nrows; rb += PD_RB) {
@@ -1980,7 +1983,7 @@ __global__ __launch_bounds__(256) void pinv_diag_kernel(const T* __restrict__ x4
         for (int64_t m0 = 0; m0 < m; m0 += PD_CT) {
             const int mc = (int)min((int64_t)PD_CT, m - m0);
             __syncthreads();
-            if (threadIdx.x < PD_CT) {
+            if (!CACHED && threadIdx.x < PD_CT) {
                 const int j = threadIdx.x;
                 if (j < mc) {
                     const V4T cv = reinterpret_cast<const V4T*>(ctrl4)[m0 + j];
@@ -1995,8 +1998,13 @@ __global__ __launch_bounds__(256) void pinv_diag_kernel(const T* __restrict__ x4
             }
             __syncthreads();
             for (int j = 0; j < mc; ++j) {
-                const V4T cv = sc[j];
-                const double k = (double)kernel_value(px, py, pz, cv.x, cv.y, cv.z);
+                double k;
+                if constexpr (CACHED) {
+                    k = (double)ublk[(((m0 + j) >> 4) * npad + i) * 16 + ((m0 + j) & 15)];  // (i < npad: n is padded to the workgroup)
+                } else {
+                    const V4T cv = sc[j];
+                    k = (double)kernel_value(px, py, pz, cv.x, cv.y, cv.z);
+                }
 #pragma unroll
                 for (int q = 0; q < PD_RB; ++q) acc[q] = fma(k, sy[q][j], acc[q]);
             }
@@ -2953,27 +2961,23 @@ extern "C" int mvf_lr_pivot_order(const void* workspace, size_t workspace_bytes,
     return 0;
 }
 
-extern "C" int mvf_pinv_diag(const void* x4, int64_t n, const void* ctrl4, int64_t m, double beta, double rcond,
-                             int lowrank, double* diag_out, void* workspace, size_t workspace_bytes, mvf_dtype dtype,
-                             void* stream) {
-    MVF_REQUIRE(n >= 0 && m > 0, "mvf_pinv_diag: need n >= 0 and m > 0");
-    MVF_REQUIRE(beta >= 0.0 && std::isfinite(beta) && rcond >= 0.0, "mvf_pinv_diag: bad beta / rcond");
-    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "mvf_pinv_diag: bad dtype %d", (int)dtype);
-    if (n == 0) return 0;
-    MVF_REQUIRE(x4 && ctrl4 && diag_out && workspace, "mvf_pinv_diag: null pointer");
-    hipStream_t st = (hipStream_t)stream;
+// What mvf_pinv_diag and mvf_pinv_diag_cached share: the checks, the decomposition the last solve left in `workspace`, the
+// weights, the launch.  ublk == NULL: the kernel values are formed from x4 / ctrl4.
+static int pinv_diag_run(const char* who, const void* x4, int64_t n, const void* ctrl4, int64_t m, double beta, const void* ublk,
+                         double rcond, int lowrank, double* diag_out, void* workspace, size_t workspace_bytes, mvf_dtype dtype,
+                         hipStream_t st) {
     char* ws = (char*)workspace;
     const double *Y, *sig2, *scal;
     double* gw;
     int64_t nrows, mp;
     if (lowrank) {
         const LrPlan p = lr_plan(m);
-        MVF_REQUIRE(workspace_bytes >= p.total, "mvf_pinv_diag: not the workspace of mvf_solve_minnorm_lr for this m");
+        MVF_REQUIRE(workspace_bytes >= p.total, "%s: not the workspace of mvf_solve_minnorm_lr for this m", who);
         PcholState hs;
         MVF_CHECK_HIP(rb_copy(st, &hs, ws + p.off_state, sizeof(hs)));
         MVF_CHECK_HIP(rb_sync(st));
-        MVF_REQUIRE(hs.magic == PCHOL_MAGIC && hs.r >= 0 && hs.r <= m, "mvf_pinv_diag: the workspace holds no finished decomposition");
-        MVF_REQUIRE(!hs.defl, "mvf_pinv_diag: the workspace holds a deflated decomposition (mvf_solve_minnorm_lrd); run mvf_solve_minnorm_lr");
+        MVF_REQUIRE(hs.magic == PCHOL_MAGIC && hs.r >= 0 && hs.r <= m, "%s: the workspace holds no finished decomposition", who);
+        MVF_REQUIRE(!hs.defl, "%s: the workspace holds a deflated decomposition (mvf_solve_minnorm_lrd); run mvf_solve_minnorm_lr", who);
         mp = p.mp;
         nrows = cdiv(hs.r, 64) * 64;
         Y = (const double*)(ws + p.off_y);
@@ -2982,7 +2986,7 @@ extern "C" int mvf_pinv_diag(const void* x4, int64_t n, const void* ctrl4, int64
         gw = (double*)(ws + p.off_t);
     } else {
         const JacPlan p = jac_plan(m, 1);
-        MVF_REQUIRE(workspace_bytes >= p.total, "mvf_pinv_diag: not the workspace of mvf_solve_minnorm for this m");
+        MVF_REQUIRE(workspace_bytes >= p.total, "%s: not the workspace of mvf_solve_minnorm for this m", who);
         CholPlan cq;
         chol_layout(m, 0, workspace, &cq);
         mp = p.mp;
@@ -2999,12 +3003,47 @@ extern "C" int mvf_pinv_diag(const void* x4, int64_t n, const void* ctrl4, int64
     hipLaunchKernelGGL(pinv_weights_kernel, dim3(1), dim3(256), 0, st, sig2, nrows, scal, rcond, gw);
     const double s = std::sqrt(beta * LOG2E);
     const unsigned grid = (unsigned)cdiv(n, 256);
-    if (dtype == MVF_F32)
-        hipLaunchKernelGGL(pinv_diag_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x4, n, (const float*)ctrl4, m,
-                           (float)s, Y, nrows, mp, gw, diag_out);
-    else
-        hipLaunchKernelGGL(pinv_diag_kernel<double>, dim3(grid), dim3(256), 0, st, (const double*)x4, n,
-                           (const double*)ctrl4, m, s, Y, nrows, mp, gw, diag_out);
+    const int64_t npad = cdiv(n, 256) * 256;
+    if (ublk) {
+        if (dtype == MVF_F32)
+            hipLaunchKernelGGL((pinv_diag_kernel<float, true>), dim3(grid), dim3(256), 0, st, (const float*)nullptr, n, (const float*)nullptr,
+                               m, 0.0f, Y, nrows, mp, gw, diag_out, (const float*)ublk, npad);
+        else
+            hipLaunchKernelGGL((pinv_diag_kernel<double, true>), dim3(grid), dim3(256), 0, st, (const double*)nullptr, n,
+                               (const double*)nullptr, m, 0.0, Y, nrows, mp, gw, diag_out, (const double*)ublk, npad);
+    } else if (dtype == MVF_F32) {
+        hipLaunchKernelGGL((pinv_diag_kernel<float, false>), dim3(grid), dim3(256), 0, st, (const float*)x4, n, (const float*)ctrl4, m,
+                           (float)s, Y, nrows, mp, gw, diag_out, (const float*)nullptr, npad);
+    } else {
+        hipLaunchKernelGGL((pinv_diag_kernel<double, false>), dim3(grid), dim3(256), 0, st, (const double*)x4, n,
+                           (const double*)ctrl4, m, s, Y, nrows, mp, gw, diag_out, (const double*)nullptr, npad);
+    }
     MVF_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int mvf_pinv_diag(const void* x4, int64_t n, const void* ctrl4, int64_t m, double beta, double rcond,
+                             int lowrank, double* diag_out, void* workspace, size_t workspace_bytes, mvf_dtype dtype,
+                             void* stream) {
+    MVF_REQUIRE(n >= 0 && m > 0, "mvf_pinv_diag: need n >= 0 and m > 0");
+    MVF_REQUIRE(beta >= 0.0 && std::isfinite(beta) && rcond >= 0.0, "mvf_pinv_diag: bad beta / rcond");
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "mvf_pinv_diag: bad dtype %d", (int)dtype);
+    if (n == 0) return 0;
+    MVF_REQUIRE(x4 && ctrl4 && diag_out && workspace, "mvf_pinv_diag: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    return pinv_diag_run("mvf_pinv_diag", x4, n, ctrl4, m, beta, nullptr, rcond, lowrank, diag_out, workspace, workspace_bytes, dtype, st);
+}
+
+extern "C" int mvf_pinv_diag_cached(const void* ublk, size_t ublk_bytes, int64_t n, int64_t m, double rcond, int lowrank,
+                                    double* diag_out, void* workspace, size_t workspace_bytes, mvf_dtype dtype, void* stream) {
+    MVF_REQUIRE(n >= 0 && m > 0, "mvf_pinv_diag_cached: need n >= 0 and m > 0");
+    MVF_REQUIRE(rcond >= 0.0, "mvf_pinv_diag_cached: bad rcond");
+    MVF_REQUIRE(dtype == MVF_F32 || dtype == MVF_F64, "mvf_pinv_diag_cached: bad dtype %d", (int)dtype);
+    if (n == 0) return 0;
+    MVF_REQUIRE(ublk && diag_out && workspace, "mvf_pinv_diag_cached: null pointer");
+    MVF_REQUIRE(ublk_bytes >= mvf_ublk_bytes(n, m, dtype), "mvf_pinv_diag_cached: the cache is smaller than mvf_ublk_bytes(n, m) (%zu < %zu)",
+                ublk_bytes, mvf_ublk_bytes(n, m, dtype));
+    hipStream_t st = (hipStream_t)stream;
+    return pinv_diag_run("mvf_pinv_diag_cached", nullptr, n, nullptr, m, 0.0, ublk, rcond, lowrank, diag_out, workspace, workspace_bytes,
+                         dtype, st);
 }

@@ -513,6 +513,7 @@ class HipKernels:
 
     def drop_ublk(self):
         self._ublk = None
+        self._cache_bufs = None
         self._ublk_key = None
 
     @_on_device
@@ -1193,6 +1194,115 @@ class HipKernels:
                                            _ptr(out), C.byref(sweeps), C.byref(err), C.byref(hit), _ptr(ws), ws.numel() * 8,
                                            self._stream()), "mvf_heat_graph")
         return np.array(self.d2h(out)), int(sweeps.value), float(err.value), bool(hit.value)
+
+    # ---- a kernel along the tissue (mvf_graph.hip): float64 whatever the cell dtype ----
+    SSSP_BATCH = 32  # Bellman-Ford sweeps queued between two reads of the status block
+
+    @_on_device
+    def knn(self, points, k):
+        """mvf_knn: points a device (n, d) float64 tensor, d in {2, 3}.  Returns device (idx (n, k) int32, dist (n, k) float64),
+        every row ascending by (distance, index), the point itself left out by index.  Queued on the current stream."""
+        n, d = (int(v) for v in points.shape)
+        points = points.contiguous()
+        idx, dist = self.empty(n, int(k), dtype=torch.int32), self.empty(n, int(k), dtype=torch.float64)
+        need = int(self.lib.mvf_knn_workspace_bytes(n, d, int(k)))
+        ws = self._heat_ws(need)
+        _lib.check(self.lib.mvf_knn(_ptr(points), n, d, int(k), _ptr(idx), _ptr(dist), _ptr(ws), ws.numel() * 8, self._stream()),
+                   "mvf_knn")
+        return idx, dist
+
+    @_on_device
+    def graph_sssp(self, indptr, indices, weights, n, sources):
+        """Shortest-path distances from `sources` (device int32 (m,)) through the CSR graph (device indptr int64 (n + 1,), indices
+        int32, weights float64): mvf_graph_sssp queued SSSP_BATCH sweeps at a time, the status block read between the batches
+        (mvf_read_back), until a whole batch lowered nothing.  A path has at most n - 1 edges: after n sweeps in all without that
+        the graph's arrays are at fault, and this raises.  Returns (device (n, m) float64 with +inf where there is no path, sweeps
+        queued)."""
+        n, m, nnz = int(n), int(sources.shape[0]), int(indices.shape[0])
+        dist = self.empty(n, m, dtype=torch.float64)
+        status = self.zeros(_lib.SSSP_STATUS, dtype=torch.int64)
+        queued, init = 0, 1
+        while True:
+            _lib.check(self.lib.mvf_graph_sssp(_ptr(indptr), _ptr(indices) if nnz else None, _ptr(weights) if nnz else None, n, nnz,
+                                               _ptr(sources), m, _ptr(dist), m, init, self.SSSP_BATCH, _ptr(status), self._stream()),
+                       "mvf_graph_sssp")
+            queued, init = queued + self.SSSP_BATCH, 0
+            if int(self.read_host(status)[0]) == 0:
+                return dist, queued
+            if queued >= n + self.SSSP_BATCH:
+                raise _lib.MVFError(f"graph_sssp: no fixed point after {queued} sweeps over {n} nodes (a negative weight?)")
+
+    @_on_device
+    def pack_ublk(self, U):
+        """The rows of a device (n, m) float64 matrix as the Gram kernel's operand cache, in the cell dtype, uncentred
+        (mvf_ublk_pack, the way pca_pack fills it): what gram_on_cache, rhs_on_cache, apply_on_cache and pinv_diag_cached read."""
+        n, m = (int(v) for v in U.shape)
+        U = U.contiguous()
+        need = self.ublk_bytes(n, m)
+        self._ublk = None
+        self._ublk = torch.empty(need // self._ublk_itemsize(), dtype=self.tdtype, device=self.device)
+        self._ublk_key = None  # (no (x4, ctrl4, beta) builds this cache: `gram` must not mistake it for a fit's)
+        self._ublk_shape = (n, m)
+        self._cache_bufs = None
+        _lib.check(self.lib.mvf_ublk_pack(_ptr(U), 0, n, m, None, n, 0, _ptr(self._ublk), need, self.cdtype, self._stream()),
+                   "mvf_ublk_pack")
+
+    @_on_device
+    def gram_on_cache(self, P, G):
+        """G = U^T diag(P) U from the packed cache: the tile and reduce stages of mvf_gram_cached (neither reads x4 / ctrl4,
+        which must only be non-NULL: P stands in, as in pca_gram)."""
+        n, m = self._ublk_shape
+        need = int(self.lib.mvf_gram_workspace_bytes(n, m, self.cdtype))
+        if self._gram_ws is None or self._gram_ws.numel() < need:
+            self._gram_ws = None
+            self._gram_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.mvf_gram_cached(_lib.GRAM_TILES | _lib.GRAM_REDUCE, _ptr(self._ublk), _ptr(P), _ptr(P), None, n, _ptr(P), m,
+                                            0.0, _ptr(G), None, _ptr(self._gram_ws), self._gram_ws.numel(), self.cdtype,
+                                            self._stream()), "mvf_gram_cached")
+
+    def _cache_operands(self):
+        """The padded operands of the wide kernels on the packed cache, allocated once per pack_ublk: Yd (n rounded up to 256, 16)
+        and a zero twin, Vd (n, 16), r (n,), Cd (m rounded up to 128, 16 float64).  Only the live columns are ever written."""
+        if getattr(self, "_cache_bufs", None) is None:
+            n, m = self._ublk_shape
+            n_pad, m_pad = self.wide_pads(n, m)
+            self._cache_bufs = dict(Yd=self.zeros(n_pad, 16), zero=self.zeros(n_pad, 16), Vd=self.empty(n, 16), r=self.empty(n),
+                                    Cd=self.zeros(m_pad, 16, dtype=torch.float64))
+        return self._cache_bufs
+
+    def _cache_rows(self, Y4):
+        """Y4 (n, 4) as the padded (n rounded up to 256, 16) operand of the wide kernels (the other columns zero)."""
+        Yd = self._cache_operands()["Yd"]
+        Yd[: Y4.shape[0], :4] = Y4
+        return Yd
+
+    @_on_device
+    def rhs_on_cache(self, P, Y4, R):
+        """R (m, 3 float64) = U^T diag(P) Y4[:, :3] from the packed cache (mvf_rhs_cached)."""
+        self.rhs_wide(P, self._cache_rows(Y4), 3, self._ublk_shape[1], R)
+
+    @_on_device
+    def apply_on_cache(self, C):
+        """V4 (n, 4, cell dtype) = U C for C (m, 3 float64) from the packed cache (mvf_apply_cached against Yd = 0)."""
+        n, m = self._ublk_shape
+        b = self._cache_operands()
+        b["Cd"][:m, :3] = C
+        self.apply_wide(b["Cd"], 3, m, b["zero"], None, b["Vd"], b["r"], None)
+        return b["Vd"][:, :4].contiguous()
+
+    @_on_device
+    def pinv_diag_cached(self, rcond=None, lowrank=False):
+        """pinv_diag with the rows of U read from the packed cache (mvf_pinv_diag_cached)."""
+        ws = self._lr_ws if lowrank else self._mn_ws
+        if ws is None or self._ublk is None:
+            raise RuntimeError("pinv_diag_cached needs a previous decomposition and the packed cache")
+        n, m = self._ublk_shape
+        out = torch.empty(n, dtype=torch.float64, device=self.device)
+        rc = float(np.finfo(np.float64).eps) if rcond is None else float(rcond)
+        _lib.check(self.lib.mvf_pinv_diag_cached(_ptr(self._ublk), self._ublk.numel() * self._ublk_itemsize(), n, m, rc,
+                                                 1 if lowrank else 0, _ptr(out), _ptr(ws), ws.numel(), self.cdtype, self._stream()),
+                   "mvf_pinv_diag_cached")
+        return out
 
     # ---- PCA across slices on the kernel-value cache (mvf_pca.hip + the cached Gram / apply kernels, unchanged) ----
     PCA_UPLOAD_BYTES = 256 << 20  # rows of a dense slice travel in chunks of at most this much (each chunk is a slice of its own)

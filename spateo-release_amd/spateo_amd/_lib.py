@@ -49,6 +49,8 @@ KDE_MAX_COLUMNS = 64  # MVF_KDE_MAX_COLUMNS: the columns (groups of sources) of 
 SHAPE_MAX_NSUB = 128  # MVF_SHAPE_MAX_NSUB: the voxels per axis of mvf_shape_descriptors
 SHAPE_ORDERS = {"linear": 1, "quadratic": 2, "cubic": 3}
 HEAT_MAX_STEPS = 8  # MVF_HEAT_MAX_STEPS: the sweeps one launch of mvf_heat_grid's kernel runs in LDS at most
+KNN_MAX_K = 64  # MVF_KNN_MAX_K: the neighbours per point of mvf_knn
+SSSP_STATUS = 4  # MVF_SSSP_STATUS: int64 entries of mvf_graph_sssp's status block
 EVAL_V, EVAL_JAC, EVAL_DIV, EVAL_CURL, EVAL_ACC, EVAL_CURV, EVAL_TORS, EVAL_JDET = 1, 2, 4, 8, 16, 32, 64, 128
 
 _p, _i64, _i, _d, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_size_t
@@ -187,6 +189,10 @@ SIGNATURES = {
     "mvf_heat_graph_workspace_bytes": (_sz, [_i64, _i64]),
     "mvf_heat_graph": (_i, [_p, _p, _p, _p, _i64, _d, _d, _p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int), _p,
                             _sz, _p]),
+    "mvf_knn_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "mvf_knn": (_i, [_p, _i64, _i, _i, _p, _p, _p, _sz, _p]),
+    "mvf_graph_sssp": (_i, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _i64, _i, _i, _p, _p]),
+    "mvf_pinv_diag_cached": (_i, [_p, _sz, _i64, _i64, _d, _i, _p, _p, _sz, _i, _p]),
 }
 
 _lib = None

@@ -16,6 +16,8 @@ import torch
 
 from . import _lib
 from . import _runtime as _rt
+from ._graph import (GraphKernel, KnnGraph, check_graph_kernel as _check_graph_kernel, con_K_graph, construct_knn_graph,  # noqa: F401
+                     graph_distances, graph_kernel, knn)
 from ._kernels import Layer, is_sparse
 from .engine import SparseVFCEngine, _consistent_K
 from .vectorfield import vector_field_function
@@ -24,7 +26,8 @@ __all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_itera
            "optimal_mapping", "mapping_from_best", "apply_assignment", "label_transfer_matrix", "init_sigma2", "init_probability_parameters", "coarse_rigid_alignment", "morpho_start",
            "Morpho_pairwise", "morpho_align", "pca", "group_pca", "trn", "sample_by_kmeans", "sample", "downsampling",
            "solve_RT_by_correspondence", "morpho_align_transformation", "morpho_align_apply_transformation", "morpho_align_ref",
-           "icp", "icp_batch", "mesh_contours", "mesh_correction_loss", "Mesh_correction"]
+           "icp", "icp_batch", "mesh_contours", "mesh_correction_loss", "Mesh_correction",
+           "knn", "construct_knn_graph", "graph_distances", "con_K_graph", "graph_kernel", "KnnGraph", "GraphKernel"]
 
 RETURN_P_MAX_ENTRIES = 1 << 27  # return_P=True: at most this many entries of P (1 GiB of float64 on the device and the host)
 
@@ -501,14 +504,22 @@ def apply_assignment(XAHat, coordsB, exp_layers_A, exp_layers_B, *, features_A=N
     return _applied_to_host(k, dev, bool(normalize))
 
 
-def _nonrigid_solve(k, G, Gamma, reg, R):
+def _nonrigid_solve(k, G, Gamma, reg, R, indefinite=None):
     """The device-resident solve of update_nonrigid (and of morpho_iterate): C = pinv(G + reg Gamma) R with scipy.linalg.pinv's
-    cut-off.  Returns (C (m x 3 float64 device), rcond, lowrank); the decomposition stays in k's workspace for pinv_diag."""
+    cut-off.  Returns (C (m x 3 float64 device), rcond, lowrank); the decomposition stays in k's workspace for pinv_diag.
+
+    ``indefinite`` (the geodesic kernel): exp(-beta D^2) of a graph distance is no positive semi-definite kernel - Gamma of the
+    3-D golden case has eigenvalues down to -0.13 against 8.0, and SigmaInv six negative ones down to -4.1 against 1040 - and the
+    reference's ``pinv`` (an SVD) keeps such eigenpairs with their sign.  So does mvf_solve_minnorm (|lambda| against the cut-off)
+    once its shift makes the factorisation exist: the ladder of shifts then goes on past 2^-12 of the mean diagonal, by factors
+    of 4 up to 1/2, and the rank-revealing path, which needs a semi-definite matrix, is not taken.  ``indefinite`` is a dict the
+    caller keeps for its loop: the ladder starts at the shift that worked last time (``indefinite["shift"]``) instead of climbing
+    through a dozen failed factorisations, each a host read, in every iteration."""
     m = G.shape[0]
     f64 = torch.float64
     C, info, einfo = k.zeros(m, 3, dtype=f64), k.zeros(1, dtype=torch.int32), k.zeros(12, dtype=f64)
     rcond = m * float(np.finfo(np.float64).eps)
-    lowrank = m >= 1024 and hasattr(k, "solve_minnorm_lr")
+    lowrank = m >= 1024 and hasattr(k, "solve_minnorm_lr") and indefinite is None
     if lowrank:
         # rank-revealing factor + Jacobi on its columns (the faster path once the factor drops most columns)
         k.solve_minnorm_lr(G, Gamma, reg, R, C, info, einfo, rcond=rcond)
@@ -516,20 +527,22 @@ def _nonrigid_solve(k, G, Gamma, reg, R):
             raise _lib.MVFError("update_nonrigid: SigmaInv has non-finite entries")
         SparseVFCEngine._check_converged(float(einfo.cpu()[0]))
     else:
-        shift = 2.0 ** -36
+        shift = 2.0 ** -36 if indefinite is None else indefinite.get("shift", 2.0 ** -36)
         while True:
             k.solve_minnorm(G, Gamma, reg, shift, R, C, info, einfo, rcond=rcond)
             if int(info.cpu()[0]) == 0:
                 SparseVFCEngine._check_converged(float(einfo.cpu()[0]))
+                if indefinite is not None:
+                    indefinite["shift"] = shift
                 break
-            shift *= 16.0
-            if shift > 2.0 ** -12:
+            shift *= 16.0 if shift < 2.0 ** -12 else 4.0
+            if shift > (0.5 if indefinite is not None else 2.0 ** -12):
                 raise _lib.MVFError("update_nonrigid: SigmaInv is not numerically positive semi-definite")
     return C, rcond, lowrank
 
 
 def update_nonrigid(coordsA, inducing_variables, beta, K_NA, PXB_term, sigma2, lambdaVF, dtype: str = "float64",
-                    device=None, *, guidance=None, svi=None):
+                    device=None, *, guidance=None, svi=None, kernel_type="euc", graph_kernel=None):
     """The non-rigid update of Spateo's alignment, ``Morpho_pairwise._update_nonrigid``
     (``spateo/alignment/methods/morpho_class.py:1254-1298``), on the MI355X with the kernels of the SparseVFC M-step - it
     is the same computation (``SigmaInv = sigma2 lambdaVF Gamma + U^T diag(K_NA) U``,
@@ -554,9 +567,22 @@ def update_nonrigid(coordsA, inducing_variables, beta, K_NA, PXB_term, sigma2, l
 
     Returns ``{"SigmaInv", "PXB_term", "Coff", "VnA", "SigmaDiag"[, "V_AI"]}`` as host float64; ``SigmaDiag`` =
     ``sigma2 diag(U pinv(SigmaInv) U^T)`` (the n-vector feeding the alignment's variational sigma^2, ``:1295-1297``) comes
-    from the decomposition the solve left on the device (``mvf_pinv_diag``)."""
+    from the decomposition the solve left on the device (``mvf_pinv_diag``).
+
+    ``kernel_type="geodist"`` with ``graph_kernel=`` (what ``st.align.graph_kernel(coordsA, inducing_idx, beta)`` returns; pass
+    ``inducing_variables=graph_kernel.inducing_variables``): U and Gamma are the graph kernel's (``morpho_class.py:865-871``)
+    instead of con_K of the coordinates.  U is packed once into the Gram kernel's operand cache (``mvf_ublk_pack``) and the four
+    consumers read it there: ``mvf_gram_cached``, ``mvf_rhs_cached``, ``mvf_apply_cached``, ``mvf_pinv_diag_cached``.
+    ``ValueError`` unless the kernel fits the call (cells, inducing variables, ``beta``); ``guidance`` is refused with it (the
+    reference sets ``U_I = None`` in this branch)."""
     if dtype not in ("float32", "float64"):
         raise ValueError("dtype must be 'float32' or 'float64'")
+    _kernel_type_argument("update_nonrigid", kernel_type, graph_kernel)
+    if graph_kernel is not None:
+        _check_graph_kernel(graph_kernel, kernel_type, len(coordsA), len(inducing_variables), beta, "update_nonrigid")
+        if guidance is not None:
+            raise NotImplementedError("update_nonrigid: guidance pairs have no graph distance to the inducing variables "
+                                      "(the reference sets U_I = None with kernel_type='geodist')")
     X = np.asarray(coordsA, dtype=np.float64)
     ctrl = np.asarray(inducing_variables, dtype=np.float64)
     w = np.asarray(K_NA, dtype=np.float64).reshape(-1)
@@ -570,8 +596,21 @@ def update_nonrigid(coordsA, inducing_variables, beta, K_NA, PXB_term, sigma2, l
     npdt = np.float32 if dtype == "float32" else np.float64
     center = ctrl.mean(0)
     x4, c4 = k.to_x4(X, center), k.to_x4(ctrl, center)
-    Gamma = _consistent_K(k, ctrl, center, float(beta))  # generated like U (see SparseVFCEngine)
     f64 = torch.float64
+    gk = graph_kernel
+    if gk is None:
+        Gamma = _consistent_K(k, ctrl, center, float(beta))  # generated like U (see SparseVFCEngine)
+
+        def gram(P, Y, rhs_only=False):
+            k.gram(x4, P, k.to_x4(Y), c4, float(beta), G, R, rhs_only=rhs_only)
+    else:
+        Gamma = k.h2d(np.ascontiguousarray(gk.Gamma, dtype=np.float64))
+        k.pack_ublk(gk.device_U(k))
+
+        def gram(P, Y, rhs_only=False):
+            if not rhs_only:
+                k.gram_on_cache(P, G)
+            k.rhs_on_cache(P, k.to_x4(Y), R)
     G, R = k.zeros(m, m, dtype=f64), k.zeros(m, 3, dtype=f64)
     Pw = k.h2d(w.astype(npdt))
     ls2 = float(sigma2) * float(lambdaVF)
@@ -579,7 +618,7 @@ def update_nonrigid(coordsA, inducing_variables, beta, K_NA, PXB_term, sigma2, l
     if svi is None:
         # rhs = U^T PXB = U^T diag(K_NA) Y with Y = PXB / K_NA (rows with K_NA == 0 have PXB == 0: cells without a partner)
         Y = np.divide(B, w[:, None], out=np.zeros_like(B), where=w[:, None] != 0)
-        k.gram(x4, Pw, k.to_x4(Y), c4, float(beta), G, R)
+        gram(Pw, Y)
     else:
         step = float(svi["step_size"])
         S_prev = np.ascontiguousarray(svi["SigmaInv_prev"], dtype=np.float64)
@@ -588,9 +627,9 @@ def update_nonrigid(coordsA, inducing_variables, beta, K_NA, PXB_term, sigma2, l
             raise ValueError("svi needs 0 < step_size <= 1, SigmaInv_prev (M, M) and PXB_prev shaped like PXB_term")
         B = step * B + (1.0 - step) * B_prev  # the blended n x D term (host, O(n)): rows without a partner NOW may carry
         # the previous batches' share, so its rhs is taken with unit weights
-        k.gram(x4, Pw, k.to_x4(np.zeros_like(B)), c4, float(beta), G, R)
+        gram(Pw, np.zeros_like(B))
         ones = torch.ones(n, dtype=Pw.dtype, device=k.device)
-        k.gram(x4, ones, k.to_x4(B), c4, float(beta), G, R, rhs_only=True)
+        gram(ones, B, rhs_only=True)
         # G <- step G + (1 - step) (SigmaInv_prev);  the regulariser enters the solve as (step ls2) Gamma
         k.lincomb3(G, step, G, 1.0 - step, k.h2d(S_prev))
     x4_I = None
@@ -606,11 +645,16 @@ def update_nonrigid(coordsA, inducing_variables, beta, K_NA, PXB_term, sigma2, l
         k.gram(x4_I, torch.ones(n_i, dtype=Pw.dtype, device=k.device), k.to_x4(dXI), c4, float(beta), G_I, R_I)
         k.lincomb3(G, 1.0, G, wg, G_I)
         k.lincomb3(R, 1.0, R, wg, R_I)
-    C, rcond, lowrank = _nonrigid_solve(k, G, Gamma, step * ls2, R)
-    V4, _ = k.apply(x4, c4, float(beta), C)
+    C, rcond, lowrank = _nonrigid_solve(k, G, Gamma, step * ls2, R, indefinite=None if gk is None else {})
     SigmaInv = _rt._d2h(k, G) + step * ls2 * _rt._d2h(k, Gamma)
     # SigmaDiag = sigma2 diag(U pinv(SigmaInv) U^T) (morpho_class.py:1295-1297) from the decomposition the solve left
-    diag = k.pinv_diag(x4, c4, float(beta), rcond=rcond, lowrank=lowrank) if hasattr(k, "pinv_diag") else None
+    if gk is None:
+        V4, _ = k.apply(x4, c4, float(beta), C)
+        diag = k.pinv_diag(x4, c4, float(beta), rcond=rcond, lowrank=lowrank) if hasattr(k, "pinv_diag") else None
+    else:
+        V4 = k.apply_on_cache(C)
+        diag = k.pinv_diag_cached(rcond=rcond, lowrank=lowrank)
+        k.drop_ublk()
     out = {"SigmaInv": SigmaInv, "PXB_term": B, "Coff": _rt._d2h(k, C)[:, :D].copy(),
            "VnA": _rt._d2h(k, V4[:, :D].to(f64))}
     if diag is not None:
@@ -624,6 +668,10 @@ def BA_transform(vecfld, quary_points, deformation_scale: int = 1, dtype: str = 
     if dtype not in ("float32", "float64"):
         raise ValueError("dtype must be 'float32' or 'float64'")
     f = lambda a: np.asarray(a, dtype=np.float64)  # noqa: E731
+    if vecfld.get("kernel_type", "euc") == "geodist":
+        raise ValueError("BA_transform: this vecfld was fitted with kernel_type='geodist' - a new point has no graph distance to "
+                         "the inducing variables, and the Euclidean kernel (what the reference evaluates here) is not the fitted "
+                         "field; the fitted positions are the loop's XAHat and VnA")
     scale = f(vecfld["norm_dict"]["scale_transformed"])
     mean_ref = f(vecfld["norm_dict"]["mean_fixed"])
     mean_q = f(vecfld["norm_dict"]["mean_transformed"])
@@ -668,10 +716,23 @@ def _digamma(x):
     return ((math.log(x) - 0.5 * r) - p * r2) - s
 
 
+def _kernel_type_argument(who, kernel_type, graph_kernel):
+    """The kernels the loops and update_nonrigid know: 'euc', and 'geodist' when the kernel is handed over built."""
+    if kernel_type == "geodist" and graph_kernel is None:
+        raise NotImplementedError(f"{who}: kernel_type='geodist' needs graph_kernel=: the kernel is built first, from the indices "
+                                  f"of the inducing variables in slice A and the graph (gk = st.align.graph_kernel(coordsA, "
+                                  f"inducing_idx, beta)), and handed over with inducing_variables=gk.inducing_variables")
+    if kernel_type not in ("euc", "geodist"):
+        raise NotImplementedError(f"{who}: kernel_type={kernel_type!r} is not supported (the Euclidean 'euc' kernel, or 'geodist' "
+                                  f"with graph_kernel=)")
+    if graph_kernel is not None and kernel_type != "geodist":
+        raise ValueError(f"{who}: graph_kernel= goes with kernel_type='geodist' (got kernel_type={kernel_type!r})")
+
+
 def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type, probability_parameters,
                        inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, kappa, gamma_a, gamma_b,
                        partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype, record, SVI_mode, guidance,
-                       sparse_calculation_mode, kernel_type, origin, sparse_top_k=1024, label_transfer=None):
+                       sparse_calculation_mode, kernel_type, origin, sparse_top_k=1024, label_transfer=None, graph_kernel=None):
     """Validation of morpho_iterate (no device needed).  Returns the arguments as float64 arrays / floats."""
     if dtype not in ("float32", "float64"):
         raise ValueError("dtype must be 'float32' or 'float64'")
@@ -680,9 +741,7 @@ def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilari
                                   "morpho_iterate_svi runs; this function is the SVI_mode=False loop")
     if guidance is not None and guidance is not False:
         raise NotImplementedError("morpho_iterate: guidance pairs are not supported (update_nonrigid(guidance=) is the stage)")
-    if kernel_type != "euc":
-        raise NotImplementedError(f"morpho_iterate: kernel_type={kernel_type!r} is not supported (only the Euclidean 'euc' "
-                                  f"kernel; 'geodist' needs the graph distances of the inducing variables)")
+    _kernel_type_argument("morpho_iterate", kernel_type, graph_kernel)
     top_k = _sparse_top_k(sparse_calculation_mode, sparse_top_k)
     XA, XB, LA, LB, codes, table = _assignment_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity,
                                                          probability_type, probability_parameters, False, label_transfer)
@@ -692,6 +751,8 @@ def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilari
     ctrl = np.asarray(inducing_variables, dtype=np.float64)
     if ctrl.ndim != 2 or ctrl.shape[1] != D or len(ctrl) == 0:
         raise AssertionError("X and Y do not have the same number of features.")  # con_K's assertion (utils.py:1150)
+    if graph_kernel is not None:
+        _check_graph_kernel(graph_kernel, kernel_type, NA, len(ctrl), beta, "morpho_iterate")
     if int(max_iter) != max_iter or max_iter < 1:
         raise ValueError("max_iter must be a positive integer")
     if record not in (False, True, "arrays"):
@@ -723,7 +784,7 @@ def _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilari
     if origin is not None:
         org[:D] = np.asarray(origin, dtype=np.float64).reshape(D)
     return dict(XA=XA, XB=XB, LA=LA, LB=LB, codes=codes, table=table, ctrl=ctrl, kappa=kap, inliers=inl, samples_s=float(samples_s),
-                origin=org, sigma2_end=None if sigma2_end is None else float(sigma2_end), top_k=top_k)
+                origin=org, sigma2_end=None if sigma2_end is None else float(sigma2_end), top_k=top_k, graph_kernel=graph_kernel)
 
 
 def _moved_sums(blk, D, mu_XA, mu_Vn, mu_XB, move_Vn):
@@ -816,7 +877,7 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
                    gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                    update_R=True, dtype: str = "float64", device=None, record=True, origin=None, SVI_mode=False, guidance=None,
                    sparse_calculation_mode=False, kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False,
-                   optimal_mapping=False, apply=None):
+                   optimal_mapping=False, apply=None, graph_kernel=None):
     """The iteration loop of Spateo's pairwise alignment on the MI355X: the non-SVI, dense-path body of
     ``Morpho_pairwise.run`` (``spateo/alignment/methods/morpho_class.py:280-294``: assignment -> gamma -> alpha -> non-rigid
     -> rigid -> ``XAHat`` -> sigma2) for ``max_iter`` iterations from the state ``_initialize_variational_variables`` sets
@@ -868,8 +929,19 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
 
     Not supported (``NotImplementedError``): ``SVI_mode`` (``morpho_iterate_svi`` runs it), ``guidance``,
     ``sparse_calculation_mode`` with ``sparse_top_k`` above 64 (the default, 1024, is the reference constructor's,
-    ``morpho_class.py:140``), ``kernel_type="geodist"`` (anything but ``"euc"``), and what
+    ``morpho_class.py:140``), ``kernel_type="geodist"`` without ``graph_kernel=`` (and any ``kernel_type`` but these two), and what
     ``update_assignment`` / ``update_nonrigid`` refuse (more than 4 layers, D outside {2, 3}).
+
+    ``kernel_type="geodist", graph_kernel=gk`` with ``gk = st.align.graph_kernel(coordsA, inducing_idx, beta)`` and
+    ``inducing_variables=gk.inducing_variables``: the non-rigid field's kernel is ``exp(-beta D^2)`` of the shortest-path distance
+    through a k-nearest-neighbour graph of slice A (``morpho_class.py:865-871``) - the kernel for folded tissue, where two cells
+    close in space lie far apart along the tissue.  The loop receives the inducing variables as coordinates, the geodesic kernel
+    needs their indices in slice A and the graph, so it is built first and handed over.  ``gk.U`` is packed once into the Gram
+    kernel's operand cache (``mvf_ublk_pack``) and read there by ``mvf_gram_cached``, ``mvf_rhs_cached``, ``mvf_apply_cached`` and
+    ``mvf_pinv_diag_cached``; ``gk.Gamma`` is the regulariser; nothing else of the loop changes, and without ``graph_kernel`` every
+    launch is as before.  ``ValueError`` unless ``kernel_type="geodist"``, ``len(gk.U) == NA``, one inducing variable per column and
+    ``gk.beta == beta``.  The returned ``vecfld`` carries ``kernel_type="geodist"`` and ``BA_transform`` refuses it (a new point has
+    no graph distance): the fitted positions are ``XAHat`` and ``VnA``.
 
     Returns a dict of host float64: ``R``, ``t``, ``Coff``, ``VnA``, ``RnA``, ``XAHat``, ``optimal_R``, ``optimal_t``,
     ``optimal_RnA``, ``sigma2``, ``gamma``, ``alpha``, ``SigmaDiag``, ``sigma2_variance``, the last assignment's ``K_NA``,
@@ -878,7 +950,8 @@ def morpho_iterate(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimilarit
     a = _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
                            probability_parameters, inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter,
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
-                           record, SVI_mode, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer)
+                           record, SVI_mode, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer,
+                           graph_kernel)
     return_P = _return_P_argument(return_P, a["top_k"], len(a["XA"]), len(a["XB"]))
     apply = _apply_argument(apply, len(a["XA"]), len(a["XB"]), "morpho_iterate")
     return _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter, gamma_a, gamma_b,
@@ -922,7 +995,13 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
     A64, B64 = k.h2d_padded(XA, 3, f64), k.h2d_padded(XB, 3, f64)
     center = ctrl.mean(0)
     x4c, c4 = k.to_x4(XA, center), k.to_x4(ctrl, center)     # what the Gram / apply / pinv_diag kernels read (update_nonrigid)
-    Gamma = _consistent_K(k, ctrl, center, beta)
+    gk = a.get("graph_kernel")
+    if gk is None:
+        Gamma = _consistent_K(k, ctrl, center, beta)
+    else:                                                      # U along the tissue: packed once, read from the cache below
+        Gamma = k.h2d(np.ascontiguousarray(gk.Gamma, dtype=np.float64))
+        k.pack_ublk(gk.device_U(k))
+    ladder = None if gk is None else {}                        # the shift of the last solve that worked (_nonrigid_solve)
     kap = k.h2d(a["kappa"])
     # ---- the state that stays on the device ----
     alpha, model_mul = (torch.ones(NA, dtype=f64, device=k.device) for _ in range(2))   # alpha = 1, SigmaDiag = 0 (:723, :734)
@@ -987,10 +1066,24 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
 
     def field_and_variance(Coff, rcond, lowrank):
         """After the solve, in both modes: V4 = U Coff, SigmaDiag = sigma2 diag(U pinv(SigmaInv) U^T)  (:1296).  (Coff, V4)."""
-        V4, _ = k.apply(x4c, c4, beta, Coff)
-        diag = k.pinv_diag(x4c, c4, beta, rcond=rcond, lowrank=lowrank)
+        if gk is None:
+            V4, _ = k.apply(x4c, c4, beta, Coff)
+            diag = k.pinv_diag(x4c, c4, beta, rcond=rcond, lowrank=lowrank)
+        else:
+            V4 = k.apply_on_cache(Coff)
+            diag = k.pinv_diag_cached(rcond=rcond, lowrank=lowrank)
         k.lincomb3(SigmaDiag, sigma2, diag)
         return Coff, V4
+
+    def gram(P, tiles_only=False, rhs_only=False):
+        """G = U^T diag(P) U and / or Rhs = U^T diag(P) Y4: U regenerated from the coordinates, or read from the packed cache."""
+        if gk is None:
+            k.gram(x4c, P, Y4, c4, beta, G, Rhs, tiles_only=tiles_only, rhs_only=rhs_only)
+            return
+        if not rhs_only:
+            k.gram_on_cache(P, G)
+        if not tiles_only:
+            k.rhs_on_cache(P, Y4, Rhs)
 
     ph.mark("setup")
     closing = svi is not None and svi["return_mapping"]       # a full assignment follows the loop
@@ -1006,18 +1099,18 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
                 # PXB_term <- step (P coordsB[batch] - RnA K_NA) + (1 - step) PXB_term; rows without a partner in THIS batch keep
                 # the earlier batches' share, so the right-hand side is U^T PXB_term with unit weights (:1270-1279)
                 k.align_transform_svi(RnA, dev["PXB"], dev["K_NA"], step, PXB_term, Y4, Pw, origin=org)
-                k.gram(x4c, Pw, Y4, c4, beta, G, Rhs, tiles_only=True)
-                k.gram(x4c, ones, Y4, c4, beta, G, Rhs, rhs_only=True)
+                gram(Pw, tiles_only=True)
+                gram(ones, rhs_only=True)
                 # SigmaInv <- step (sigma2 lambdaVF Gamma + U^T diag(K_NA) U) + (1 - step) SigmaInv (:1273): G takes the blend
                 # without the regulariser, which enters the solve as (step sigma2 lambdaVF) Gamma and the stored value after it
                 k.lincomb3(G, step, G, 1.0 - step, S_run)
-                solved = _nonrigid_solve(k, G, Gamma, step * sigma2 * lambdaVF, Rhs)
+                solved = _nonrigid_solve(k, G, Gamma, step * sigma2 * lambdaVF, Rhs, indefinite=ladder)
                 k.lincomb3(S_run, 1.0, G, step * sigma2 * lambdaVF, Gamma)
             else:
                 # PXB_term = P coordsB - RnA K_NA with the RnA of the previous iteration's R, t; Y = PXB_term / K_NA; Pw = K_NA
                 k.align_transform(A64, V4, dev["PXB"], dev["K_NA"], R3, t3, origin=org, PXB_term=PXB_term, Y4=Y4, Pw=Pw)
-                k.gram(x4c, Pw, Y4, c4, beta, G, Rhs)
-                solved = _nonrigid_solve(k, G, Gamma, sigma2 * lambdaVF, Rhs)
+                gram(Pw)
+                solved = _nonrigid_solve(k, G, Gamma, sigma2 * lambdaVF, Rhs, indefinite=ladder)
             Coff, V4 = field_and_variance(*solved)
             ph.mark("nonrigid")
         blk = moments(dev, B_cur)
@@ -1104,8 +1197,10 @@ def _iterate(a, dissimilarity, beta, lambdaVF, sigma2, max_iter, nonrigid_start_
         "gamma": gamma, "NA": NA, "sigma2_variance": sigma2_variance, "method": "Spateo",
         "norm_dict": {"mean_transformed": np.zeros(D), "mean_fixed": np.zeros(D), "scale": 1.0, "scale_transformed": 1.0,
                       "scale_fixed": 1.0},
-        "kernel_type": "euc",
+        "kernel_type": "euc" if gk is None else "geodist",
     }
+    if gk is not None:
+        k.drop_ublk()
     return out
 
 
@@ -1147,7 +1242,8 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
                        gamma_b=1.0, partial_robust_level=10, sigma2_end=None, samples_s=None, inliers=None, nn_init_weight=1.0,
                        update_R=True, dtype: str = "float64", device=None, record=True, origin=None, batch_size=None,
                        batch_perm=None, seed=None, return_mapping=False, guidance=None, sparse_calculation_mode=False,
-                       kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False, optimal_mapping=False, apply=None):
+                       kernel_type="euc", sparse_top_k=1024, label_transfer=None, return_P=False, optimal_mapping=False, apply=None,
+                       graph_kernel=None):
     """The SVI mode of the same loop - the reference constructor's default, ``SVI_mode=True``
     (``spateo/alignment/methods/morpho_class.py:136, 283-284, 749-760, 894-896``): every iteration sees ``batch_size`` cells
     of the B slice and blends what it learns into running averages with ``step_size = min(1, 10 / (iter + 1))``.
@@ -1187,7 +1283,8 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
     ``apply=dict(...)`` as in ``morpho_iterate``: the closing full assignment runs in the same way and is followed by
     ``mvf_assign_apply``; the result gains ``applied`` (``to_B`` has NB rows).
 
-    Not supported (``NotImplementedError``): what ``morpho_iterate`` refuses but ``SVI_mode``.
+    Not supported (``NotImplementedError``): what ``morpho_iterate`` refuses but ``SVI_mode``.  ``kernel_type="geodist"`` with
+    ``graph_kernel=`` as in ``morpho_iterate``.
 
     Returns ``morpho_iterate``'s dict - ``K_NA``, ``K_NB`` (``batch_size``,), ``K_NA_spatial``, ``K_NA_sigma2`` of the last
     batch, ``Sp``, ``Sp_spatial``, ``Sp_sigma2`` the running values (or all of them the full assignment's) - plus
@@ -1195,7 +1292,8 @@ def morpho_iterate_svi(coordsA, coordsB, exp_layers_A, exp_layers_B, *, dissimil
     a = _iterate_arguments(coordsA, coordsB, exp_layers_A, exp_layers_B, dissimilarity, probability_type,
                            probability_parameters, inducing_variables, beta, lambdaVF, sigma2, max_iter, nonrigid_start_iter,
                            kappa, gamma_a, gamma_b, partial_robust_level, sigma2_end, samples_s, inliers, nn_init_weight, dtype,
-                           record, False, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer)
+                           record, False, guidance, sparse_calculation_mode, kernel_type, origin, sparse_top_k, label_transfer,
+                           graph_kernel)
     bs, perm = _svi_arguments(len(a["XB"]), batch_size, batch_perm, seed)
     apply = _apply_argument(apply, len(a["XA"]), len(a["XB"]), "morpho_iterate_svi")
     return_mapping = bool(return_mapping) or bool(optimal_mapping) or apply is not None
