@@ -609,8 +609,8 @@ class HipKernels:
     def solve_minnorm_lr(self, G, K, lambda_sigma2, R, C_out, info, einfo, rcond=None, reuse=False, max_sweeps=60,
                          rank_hint=0, tolf=0.25, deflate=False):
         """The same truncated minimum-norm solve through the rank-revealing factor (pivoted Cholesky stopped at
-        tolf * eps * lambda_max, Jacobi on the r kept columns only).  einfo[6] = r; pass it back as ``rank_hint`` for
-        the next, nearby matrix.  deflate=True (mvf_solve_minnorm_lrd): only the invariant subspace below the cut-off
+        tolf * eps * lambda_max, Jacobi on the r kept columns only).  einfo[_lib.EINFO_FACTOR_RANK] = r; pass it back as
+        ``rank_hint`` for the next, nearby matrix.  deflate=True (mvf_solve_minnorm_lrd): only the invariant subspace below the cut-off
         is computed and projected out - same truncation, no full eigendecomposition (no pinv_diag afterwards).
         Synchronises the stream."""
         m, nrhs = R.shape
@@ -630,8 +630,9 @@ class HipKernels:
     @_on_device
     def solve_minnorm_lrd_async(self, G, K, lambda_sigma2, R, C_out, info, einfo, form_hint, rcond=None, tolf=0.25):
         """The direct form of the deflated solve without any host synchronisation (mvf_solve_minnorm_lrd_async): form_hint =
-        the previous call's einfo[8] on this workspace (1 factor form / 2 direct form, with einfo[6] == m).  einfo[9] == 1
-        afterwards means NOT accepted: repeat through solve_minnorm_lr(deflate=True).  Needs the workspace of a previous call."""
+        the previous call's einfo[_lib.EINFO_FORM] on this workspace (LRD_FORM_FACTOR / LRD_FORM_DIRECT, with EINFO_FACTOR_RANK
+        == m; + LRD_HINT_MOVED: the matrix moved).  einfo[_lib.EINFO_REJECTED] == 1 afterwards means NOT accepted: repeat through
+        solve_minnorm_lr(deflate=True).  Needs the workspace of a previous call."""
         m, nrhs = R.shape
         if self._lr_ws is None or self._lr_ws.numel() < self.lib.mvf_solve_minnorm_lrd_workspace_bytes(m, nrhs):
             raise RuntimeError("solve_minnorm_lrd_async without the workspace of a previous deflated solve")

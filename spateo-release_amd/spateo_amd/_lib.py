@@ -52,6 +52,15 @@ HEAT_MAX_STEPS = 8  # MVF_HEAT_MAX_STEPS: the sweeps one launch of mvf_heat_grid
 KNN_MAX_K = 64  # MVF_KNN_MAX_K: the neighbours per point of mvf_knn
 SSSP_STATUS = 4  # MVF_SSSP_STATUS: int64 entries of mvf_graph_sssp's status block
 EVAL_V, EVAL_JAC, EVAL_DIV, EVAL_CURL, EVAL_ACC, EVAL_CURV, EVAL_TORS, EVAL_JDET = 1, 2, 4, 8, 16, 32, 64, 128
+# the status record `einfo` of mvf_solve_minnorm / _lr / _lrd / _lrd_async (mvf.h): 12 float64; a `reuse` call writes its own
+# values behind the first call's.  SWEEPS is x.5 when the sweep cap was hit (check_converged); DELTA the shift that was
+# subtracted again (mvf_solve_minnorm only); FACTOR_RANK the columns of the pivoted factor (the next call's rank_hint);
+# BLOCK, FORM, REJECTED: mvf_solve_minnorm_lrd(_async) only
+EINFO_DOUBLES = 12
+(EINFO_SWEEPS, EINFO_KEPT_RANK, EINFO_LMAX, EINFO_LMIN_KEPT, EINFO_DELTA, EINFO_LMIN, EINFO_FACTOR_RANK, EINFO_BLOCK,
+ EINFO_FORM, EINFO_REJECTED) = range(10)
+LRD_FORM_JACOBI, LRD_FORM_FACTOR, LRD_FORM_DIRECT = 0, 1, 2  # einfo[EINFO_FORM]: which form of mvf_solve_minnorm_lrd answered
+LRD_HINT_MOVED = 4  # added to mvf_solve_minnorm_lrd_async's form_hint: the matrix moved since the previous call
 
 _p, _i64, _i, _d, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_size_t
 
@@ -200,6 +209,14 @@ _lib = None
 
 class MVFError(RuntimeError):
     """Raised when a libmvf entry point returns a non-zero status."""
+
+
+def check_converged(sweeps):
+    """mvf_solve_minnorm(_lr) report a sweep count (einfo[EINFO_SWEEPS]) of x.5 when the Jacobi iteration hit its sweep cap
+    before a clean sweep: the factor is then not orthogonal and the truncated back-solve is not an eigen-solve - fail loudly."""
+    if float(sweeps) % 1.0 != 0.0:
+        raise MVFError(f"coefficient solve failed: the Jacobi eigensolver did not converge in {int(sweeps)} "
+                       f"sweeps (non-finite or wildly scaled Gram system?)")
 
 
 def load():

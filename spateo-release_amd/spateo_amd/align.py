@@ -19,7 +19,7 @@ from . import _runtime as _rt
 from ._graph import (GraphKernel, KnnGraph, check_graph_kernel as _check_graph_kernel, con_K_graph, construct_knn_graph,  # noqa: F401
                      graph_distances, graph_kernel, knn)
 from ._kernels import Layer, is_sparse
-from .engine import SparseVFCEngine, _consistent_K
+from .engine import _consistent_K
 from .vectorfield import vector_field_function
 
 __all__ = ["BA_transform", "update_nonrigid", "update_assignment", "morpho_iterate", "morpho_iterate_svi",
@@ -517,7 +517,7 @@ def _nonrigid_solve(k, G, Gamma, reg, R, indefinite=None):
     through a dozen failed factorisations, each a host read, in every iteration."""
     m = G.shape[0]
     f64 = torch.float64
-    C, info, einfo = k.zeros(m, 3, dtype=f64), k.zeros(1, dtype=torch.int32), k.zeros(12, dtype=f64)
+    C, info, einfo = k.zeros(m, 3, dtype=f64), k.zeros(1, dtype=torch.int32), k.zeros(_lib.EINFO_DOUBLES, dtype=f64)
     rcond = m * float(np.finfo(np.float64).eps)
     lowrank = m >= 1024 and hasattr(k, "solve_minnorm_lr") and indefinite is None
     if lowrank:
@@ -525,13 +525,13 @@ def _nonrigid_solve(k, G, Gamma, reg, R, indefinite=None):
         k.solve_minnorm_lr(G, Gamma, reg, R, C, info, einfo, rcond=rcond)
         if int(info.cpu()[0]) != 0:
             raise _lib.MVFError("update_nonrigid: SigmaInv has non-finite entries")
-        SparseVFCEngine._check_converged(float(einfo.cpu()[0]))
+        _lib.check_converged(float(einfo.cpu()[_lib.EINFO_SWEEPS]))
     else:
         shift = 2.0 ** -36 if indefinite is None else indefinite.get("shift", 2.0 ** -36)
         while True:
             k.solve_minnorm(G, Gamma, reg, shift, R, C, info, einfo, rcond=rcond)
             if int(info.cpu()[0]) == 0:
-                SparseVFCEngine._check_converged(float(einfo.cpu()[0]))
+                _lib.check_converged(float(einfo.cpu()[_lib.EINFO_SWEEPS]))
                 if indefinite is not None:
                     indefinite["shift"] = shift
                 break

@@ -219,10 +219,12 @@ class CpuKernels:
             return
         keep = lam > rc * lam.max()
         c = None
+        self._lr_fell_back = False
         if deflate and r >= 2 * self.DEFL_BLOCK:
             c, nsel = deflated_minnorm(self._lr_factor, _np(R), rc * lam.max(), self.DEFL_BLOCK)
             if nsel > self.DEFL_BLOCK - self.DEFL_BLOCK // 8:
                 c = None  # block too small for what lies below the cut: the SVD route, like the device's Jacobi path
+                self._lr_fell_back = True
         if c is None:
             c = (u[:, keep] / lam[keep]) @ (u[:, keep].T @ _np(R))
         C_out.copy_(torch.from_numpy(c))
@@ -427,3 +429,62 @@ class CpuKernelsWide(CpuKernels):
         if not tiles_only:
             self.calls["gram_rhs"] += 1
         super().gram(x4, P, y4, ctrl4, beta, G, R, rhs_only=rhs_only, tiles_only=tiles_only)
+
+
+class CpuKernelsDirect(CpuKernels):
+    """CpuKernels + what include/mvf.h says about the FORMS of mvf_solve_minnorm_lrd (einfo[7] block, [8] form, [9] rejected)
+    and its host-sync-free twin mvf_solve_minnorm_lrd_async, so that the engine's direct-form branch - the form hint, the
+    accept / reject decision, the speculative field update, the repeat through the synchronous call - runs on the CPU.  A
+    subclass: the plain class has no `solve_minnorm_lrd_async` and reports no form, so every test on it keeps its path.
+
+    The numbers are the class's own (pivoted factor + SVD of the same matrix); only the status record is modelled:
+      * a fresh `solve_minnorm_lr(deflate=True)` whose factor kept all m columns, 128 <= m <= 640: the direct form (block 64,
+        form 2) - unless the previous async call was rejected: the workspace then carries the cool-down mark and this call
+        goes to the factor form at once (form 1), which clears the mark;
+      * otherwise the factor form (form 1; block 64 for factors of 128 .. 511 columns, else DEFL_BLOCK) from 128 columns on,
+        the Jacobi form (block 0, form 0) below that or when the block was too small for what lies below the cut;
+      * `solve_minnorm_lrd_async`: accepted (einfo[9] = 0, the direct form's record) except at the 1-based call numbers in
+        `reject_at`: einfo[9] = 1 and C_out is filled with NaN (a rejected call leaves C undefined).
+    `log` records every fresh solve as (entry point, lambda sigma^2, rank_hint or form_hint)."""
+
+    def __init__(self, device=None, dtype="float64", reject_at=()):
+        super().__init__(device, dtype)
+        self.reject_at = set(reject_at)
+        self.async_calls = 0
+        self.cooldown = False
+        self.log = []
+        self.form_hints = []
+
+    def solve_minnorm_lr(self, G, K, lambda_sigma2, R, C_out, info, einfo, rcond=None, reuse=False, max_sweeps=60,
+                         rank_hint=0, tolf=0.25, deflate=False):
+        super().solve_minnorm_lr(G, K, lambda_sigma2, R, C_out, info, einfo, rcond=rcond, reuse=reuse, max_sweeps=max_sweeps,
+                                 rank_hint=rank_hint, tolf=tolf, deflate=deflate)
+        if reuse or not deflate or int(info[0]) != 0:
+            return
+        self.log.append(("lr", float(lambda_sigma2), int(rank_hint)))
+        m, r = G.shape[0], self._lr[2]
+        if r == m and 128 <= m <= 640 and not self.cooldown:
+            block, form = 64, 2
+        elif r < 128 or self._lr_fell_back:
+            block, form = 0, 0
+        else:
+            block, form = (64 if r < 512 else self.DEFL_BLOCK), 1
+        self.cooldown = False
+        einfo[7:10] = torch.tensor([block, form, 0.0], dtype=torch.float64)
+
+    def solve_minnorm_lrd_async(self, G, K, lambda_sigma2, R, C_out, info, einfo, form_hint, rcond=None, tolf=0.25):
+        self.async_calls += 1
+        self.form_hints.append(int(form_hint))
+        self.log.append(("async", float(lambda_sigma2), int(form_hint)))
+        m = G.shape[0]
+        if self.async_calls in self.reject_at:
+            info.zero_()
+            einfo[9] = 1.0
+            C_out.fill_(float("nan"))
+            self.cooldown = True
+            return
+        # the same truncated solution as the synchronous call's (the class's pivoted factor + SVD), so that an engine with and
+        # one without the async branch differ by nothing but the branch
+        CpuKernels.solve_minnorm_lr(self, G, K, lambda_sigma2, R, C_out, info, einfo, rcond=rcond, tolf=tolf)
+        einfo[0] = 1.0
+        einfo[6:10] = torch.tensor([m, 64.0, 2.0, 0.0], dtype=torch.float64)

@@ -963,3 +963,157 @@ def test_wide_twin_refuses_what_the_entry_points_refuse():
             bad()
     with pytest.raises(RuntimeError, match="cache of these points is not built"):
         k.gram(k.to_x4(X), P, None, c4, 0.001, k.zeros(20, 20), None, tiles_only=True, cache_only=True)
+
+
+# ------------------------------------------------------------------------------------------------ the direct-form async branch
+def _direct_kernels(reject_at=(), base=None):
+    """CpuKernelsDirect whose Cholesky reports a pivot at rounding level (full rank is NOT certified) and that counts the
+    field applications (calls with a Y) and records the coefficients of each."""
+    from _cpu_kernels import CpuKernelsDirect
+
+    class Direct(base or CpuKernelsDirect):
+        def __init__(self, **kw):
+            super().__init__(**kw)
+            self.applies, self.applied_C = 0, []
+
+        def solve(self, G, K, ls2, jitter, R, C_out, info, pivots=None):
+            super().solve(G, K, ls2, jitter, R, C_out, info, pivots)
+            if pivots is not None:
+                pivots[0] = 1e-14 * pivots[1]
+
+        def apply(self, x4, ctrl4, beta, C, y4=None, P=None, stats=None):
+            if y4 is not None and ctrl4.shape[0]:
+                self.applies += 1
+                self.applied_C.append(C.clone())
+            return super().apply(x4, ctrl4, beta, C, y4, P, stats)
+
+    return Direct(reject_at=reject_at)
+
+
+def _direct_engine(k, M=128, dy=3, method="deflated", async_direct=True):
+    X, V = _data(600)
+    if dy != 3:
+        V = np.column_stack([np.sin(X[:, 0] / 80 + j) + 0.3 * np.cos(X[:, 1] / 60 * (j + 1)) for j in range(dy)])
+    valid, Xv, Yv, idx, ctrl, beta = vfm.sparsevfc_preprocess(X, V, M=M, seed=0)
+    eng = vfm.SparseVFCEngine(Xv, Yv, ctrl, beta, kernels=k)
+    eng.mn_method = method
+    eng.async_direct = async_direct
+    eng.init_state()
+    return eng
+
+
+def _expected_hints(log):
+    """form_hint of every async call in the stand-in's log: 2, + 4 exactly when lambda sigma^2 moved by more than 5 % since
+    the previous solve (whichever entry point that was)."""
+    return [2 | (4 if not abs(ls2 - log[i - 1][1]) <= 0.05 * abs(log[i - 1][1]) else 0)
+            for i, (kind, ls2, _) in enumerate(log) if kind == "async"]
+
+
+STEPS_DIRECT = 9
+
+
+def test_direct_form_async_branch_accepted():
+    """M = 128, deflated, full rank not certified: the first solve is the synchronous call (rank_hint 0), it keeps all 128
+    columns and reports the direct form; from then on EVERY solve is mvf_solve_minnorm_lrd_async with the speculative field
+    update behind it (one apply per iteration)."""
+    k = _direct_kernels()
+    eng = _direct_engine(k)
+    applies = []
+    for _ in range(STEPS_DIRECT):
+        n0 = k.applies
+        eng.em_step(lambda_=3.0)
+        applies.append(k.applies - n0)
+        assert eng.rank_hint == 128 and eng._solver_signature[0] == 3.0
+    assert [kind for kind, _, _ in k.log] == ["lr"] + ["async"] * (STEPS_DIRECT - 1) and k.log[0][2] == 0
+    assert k.form_hints == _expected_hints(k.log)
+    assert 6 in k.form_hints and 2 in k.form_hints   # both: sigma^2 moves at first and settles
+    # iteration 1: the speculation behind the refused certificate is thrown away (2 applies); afterwards it is used
+    assert applies == [2] + [1] * (STEPS_DIRECT - 1)
+    st_ = eng.solver_stats
+    assert st_["async"] == STEPS_DIRECT - 1 and st_["minnorm"] == STEPS_DIRECT and st_["cholesky"] == 0
+    assert st_["block"] == [64] * STEPS_DIRECT and st_["factor_rank"] == [128] * STEPS_DIRECT
+    assert st_["rank"] == [128] * STEPS_DIRECT and st_["sweeps"] == [1.0] * STEPS_DIRECT
+    assert eng._solver_signature == (3.0, 0.0, 1.0, 128.0, 128.0, 64.0)
+
+
+@pytest.mark.parametrize("reject", [1, 3])
+def test_direct_form_async_branch_rejected(reject):
+    """The async call number `reject` is refused (einfo[9] = 1, C = NaN): the engine repeats through
+    solve_minnorm_lr(rank_hint=M, deflate=True) - the factor form, the workspace carries the cool-down mark - applies the
+    repeat's coefficients, stays synchronous in the next iteration and resumes async only behind a call that reports the
+    direct form again.  The field is the one of an engine that never takes the async branch."""
+    import torch
+
+    k = _direct_kernels(reject_at=(reject,))
+    eng = _direct_engine(k)
+    kinds, applies, Cs = [], [], []
+    for _ in range(STEPS_DIRECT):
+        n0, l0 = k.applies, len(k.log)
+        eng.em_step(lambda_=3.0)
+        kinds.append([kind for kind, _, _ in k.log[l0:]])
+        applies.append(k.applies - n0)
+        Cs.append(eng.C[0].clone())
+        assert all(bool(torch.isfinite(c).all()) for c in eng.C) and np.isfinite(eng.sigma2) and np.isfinite(eng.E)
+    it = reject  # 0-based iteration of the refused call: iteration 0 is the first synchronous one
+    want = [["lr"]] + [["async"]] * (STEPS_DIRECT - 1)
+    want[it], want[it + 1] = ["async", "lr"], ["lr"]
+    assert kinds == want
+    # the repeat carries the previous factor rank as its hint; so does the synchronous iteration behind it
+    repeat = [e for e in k.log if e[0] == "lr"]
+    assert [e[2] for e in repeat] == [0, 128, 128]
+    assert k.form_hints == _expected_hints(k.log)
+    # the refused iteration: the speculative apply saw the NaN coefficients, the second one the repeat's
+    assert applies == [2] + [2 if i == it else 1 for i in range(1, STEPS_DIRECT)]
+    napp = sum(applies[:it])
+    assert bool(torch.isnan(k.applied_C[napp]).all()) and bool(torch.isfinite(k.applied_C[napp + 1]).all())
+    assert torch.equal(k.applied_C[napp + 1], Cs[it])
+    st_ = eng.solver_stats
+    assert st_["async"] == STEPS_DIRECT - 3 and st_["minnorm"] == STEPS_DIRECT
+    blocks = [64] * STEPS_DIRECT   # (the factor form of a 128-column factor takes the 64-vector block too)
+    assert st_["block"] == blocks and st_["factor_rank"] == [128] * STEPS_DIRECT
+    k2 = _direct_kernels()
+    ref = _direct_engine(k2, async_direct=False)
+    for _ in range(STEPS_DIRECT):
+        ref.em_step(lambda_=3.0)
+    assert k2.async_calls == 0
+    np.testing.assert_allclose(eng.results()[0], ref.results()[0], rtol=1e-9, atol=1e-12)
+
+
+@pytest.mark.parametrize("kw", [dict(dy=7), dict(async_direct=False), dict(M=127), dict(method="lowrank")],
+                         ids=["two_rhs_batches", "async_direct_off", "M127", "lowrank"])
+def test_direct_form_async_branch_not_taken(kw):
+    """More than one right-hand-side batch (Dy = 7: three column groups, solved two at a time), async_direct = False, fewer
+    than 128 control points and mn_method = "lowrank" never call the async entry point."""
+    k = _direct_kernels()
+    eng = _direct_engine(k, **kw)
+    for _ in range(5):
+        eng.em_step(lambda_=3.0)
+    assert eng.rank_deficient and eng.solver_stats["minnorm"] == 5
+    assert k.async_calls == 0 and "async" not in eng.solver_stats
+
+
+def test_direct_form_async_branch_with_one_six_column_batch():
+    """Dy = 5 is two column groups but ONE right-hand-side batch (six columns, the solvers take eight): the async branch is
+    taken with it."""
+    k = _direct_kernels()
+    eng = _direct_engine(k, dy=5)
+    for _ in range(4):
+        eng.em_step(lambda_=3.0)
+    assert len(eng._rhs_batches()) == 1 and k.async_calls == 3 and eng.solver_stats["async"] == 3
+
+
+def test_direct_form_async_nonzero_info_is_non_finite_input():
+    """info != 0 with einfo[9] == 0 behind the async call: the "non-finite entries" error."""
+    from _cpu_kernels import CpuKernelsDirect
+    from spateo_amd import _lib
+
+    class BadInfo(CpuKernelsDirect):
+        def solve_minnorm_lrd_async(self, G, K, ls2, R, C_out, info, einfo, form_hint, **kw):
+            super().solve_minnorm_lrd_async(G, K, ls2, R, C_out, info, einfo, form_hint, **kw)
+            info.fill_(1)
+
+    k = _direct_kernels(base=BadInfo)
+    eng = _direct_engine(k)
+    eng.em_step(lambda_=3.0)
+    with pytest.raises(_lib.MVFError, match="non-finite entries"):
+        eng.em_step(lambda_=3.0)
